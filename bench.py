@@ -2,9 +2,17 @@
 """Benchmark of the rltime Q-learning hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W          # any N: starts its own N ranks when not under torchrun
+    python bench.py --gpus N --steps K --warmup W --full   # + every side measurement (below)
+    python bench.py ... --dump-outputs DIR                 # + what the last timed step computed, as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --config {iqn_lstm,rainbow_iqn,dqn_uniform} [--scaling {both,strong,weak}]
     python bench.py --gpus N --dry-launch                  # print the launch command only
+
+A plain run does only what the headline needs: set up, pre-fill, W warm-up steps, K timed
+steps, the outputs when --dump-outputs is given, and the result line.  `--full` adds the
+side measurements, each a run or pass of its own after the timed region: the per-kernel
+table (`roofline_all`, `roofline_step`), the measured copy peak, the CPU baselines, the
+`other_configs` sub-records (N=1) and the `weak` / `overlapped_acting` sub-records (N>1).
 
 Workloads (`--config`, default = the one BASELINE.json's
 metric is quoted on):
@@ -35,14 +43,24 @@ reports it as the `weak` sub-record of the same line.  Gradients are all-reduced
 per step), importance weights globalised (rltime_amd/parallel.py).
 
 Prints ONE JSON line (rank 0).  `value` comes from the wall time of exactly K steps
-between barriers (max over ranks); `step_ms` holds median / p10 / p90 of the K
-per-step device times (HIP events).  `roofline` is the dominant HIP kernel of the
-path, the frame gather: algorithmic bytes per launch over the mean launch duration
-measured with HIP events on the launch stream inside the timed region.
-`roofline_all` lists every librltime_hip kernel (events around every launch, in a
-separate short pass after the timed region so that ~1500 event records per step do
-not perturb `value`).  `cpu_baseline` is the oracle (the reference's algorithm class
-restated, oracle/) timed on this box's host cores on a bounded sample.
+between barriers (max over ranks); `ms_per_step` is that wall time over K; `step_ms`
+holds median / p10 / p90 of the K per-step device times (HIP events).  `roofline` is
+the dominant HIP kernel of the path, the frame gather: algorithmic bytes per launch
+over the mean launch duration measured with HIP events on the launch stream inside the
+timed region.  With --full: `roofline_all` lists every librltime_hip kernel (events
+around every launch, in a separate short pass after the timed region so that ~1500
+event records per step do not perturb `value`); `cpu_baseline` is the oracle (the
+reference's algorithm class restated, oracle/) timed on this box's host cores on a
+bounded sample.
+
+--dump-outputs DIR (rank 0, after the timed steps, before any side pass): the policy's
+parameters and the clipped gradients of the last learner step (`param.<name>.npy`,
+`grad.<name>.npy`, float32), the device scalars that step logged (`logged.<key>.npy`,
+float64: qloss, td_mean, grad_norm, ...) and, under prioritized replay, the priority
+tree's leaves (`priorities.npy`, float64).  An array of more than 2^20 elements is
+stored as a fixed seeded sample of 2^20 of its flattened elements (the same indices in
+every run); 64 MB at most in all.
+The inputs are seeded, so two runs with the same arguments compare output for output.
 """
 import argparse
 import json
@@ -82,8 +100,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="iqn_lstm", choices=sorted(CONFIGS))
-    ap.add_argument("--scaling", default="both", choices=["both", "strong", "weak"],
-                    help="N>1: both = strong-scaling headline + a `weak` sub-record in the same line")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run every side measurement: per-kernel "
+                    "roofline table (--profile-steps 3), measured copy peak, CPU baselines, `other_configs` (N=1), `weak` and "
+                    "`overlapped_acting` sub-records (N>1).  Off: the headline line alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (see the module docstring)")
+    ap.add_argument("--scaling", default=None, choices=["both", "strong", "weak"],
+                    help="N>1: both = strong-scaling headline + a `weak` sub-record in the same line "
+                         "(default: both with --full, else strong)")
     ap.add_argument("--dry-launch", action="store_true", help="print the N-rank launch command as JSON and exit")
     ap.add_argument("--master-port", type=int, default=None)
     ap.add_argument("--share-gpu", action="store_true", help="launcher check on a box with fewer GPUs than ranks: ranks share "
@@ -99,7 +123,7 @@ def parse():
                     help="run the acting + ingest of iteration k+1 on a second HIP stream against iteration k's training "
                          "(MultiStepTrainer overlap_acting: the actor's weights are one learner step old, like the reference's async "
                          "actors).  off (default): the HEADLINE is the same algorithm at every N — the synchronous actor of "
-                         "rltime/acting/actor.py:108-147; at N > 1 the overlapped schedule is measured as the `overlapped_acting` "
+                         "rltime/acting/actor.py:108-147; at N > 1 with --full the overlapped schedule is measured as the `overlapped_acting` "
                          "sub-record when a rank trains at most 8192 rows per step (where it pays).  auto: on for such ranks "
                          "(the round-3 headline at N = 8); on: always")
     ap.add_argument("--no-policy-outputs", action="store_true", help="replay without the actor's q-values (keep_policy_outputs=False: "
@@ -114,18 +138,24 @@ def parse():
                          "extrapolation from B=16 the headline cpu_baseline figure uses (on by default)")
     ap.add_argument("--cpu-linearity-check", dest="cpu_linearity_check", action="store_true", help=argparse.SUPPRESS)
     ap.set_defaults(cpu_linearity_check=True)
-    ap.add_argument("--no-other-configs", action="store_true", help="default N=1 run: skip the `other_configs` sub-records "
+    ap.add_argument("--no-other-configs", action="store_true", help="--full at N=1: skip the `other_configs` sub-records "
                     "(BASELINE configs[1] DQN + uniform replay B=256 and configs[2] Rainbow-IQN B=512, each with its own "
                     "gather roofline and CPU baseline)")
     ap.add_argument("--other-steps", type=int, default=200, help="timed learner steps of each `other_configs` run (20 warm-up)")
-    ap.add_argument("--profile-steps", type=int, default=3, help="extra steps after the timed region with per-kernel HIP events (roofline_all); 0 = skip")
+    ap.add_argument("--profile-steps", type=int, default=None, help="extra steps after the timed region with per-kernel HIP events "
+                    "(roofline_all); 0 = skip (default: 3 with --full, else 0)")
     ap.add_argument("--miopen-find", action="store_true", help="torch.backends.cudnn.benchmark = True: MIOpen benchmarks its solvers "
                     "per conv shape instead of taking the immediate-mode pick (experiment)")
     ap.add_argument("--frame-dedup", action="store_true", help="SURVEY 8(f)2: stack-consistent synthetic frames and de-duplicated "
                     "storage (one 84x84 plane per transition in the ring, stacks rebuilt by the gather)")
     ap.add_argument("--train-arg", action="append", default=[], help="KEY=JSON extra training.args override (experiments)")
     ap.add_argument("--pmc-traffic", default=os.path.join(ROOT, "profiles", "gather_traffic.json"))
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.scaling is None:
+        args.scaling = "both" if args.full else "strong"
+    if args.profile_steps is None:
+        args.profile_steps = 3 if args.full else 0
+    return args
 
 
 def build_config(args, rank, world, scaling, overlap=None):
@@ -738,9 +768,43 @@ def library_roofline(one_step):
         return None
 
 
-def run_mode(args, scaling, rank, world, device, dp, want_tables, overlap=None):
+DUMP_MAX_ELEMENTS = 1 << 20        # --dump-outputs: larger arrays are stored as a fixed seeded sample of this many elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, trainer, hist, per, logged):
+    """--dump-outputs: what the timed path left after its last step (module docstring) -> {name: bytes written}."""
+    import zlib
+    arrays = {}
+    for key, val in sorted(logged.items()):
+        arrays["logged." + key] = np.array([float(val)], dtype=np.float64)
+    for name, p in trainer.policy.named_parameters():
+        arrays["param." + name] = p.detach().float().cpu().numpy()
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad.detach().float().cpu().numpy()
+    if per and hasattr(hist, "tree_nodes"):
+        nodes = hist.tree_nodes()[0]
+        arrays["priorities"] = nodes[len(nodes) // 2:]
+    os.makedirs(out_dir, exist_ok=True)
+    written, total = {}, 0
+    for name, a in arrays.items():
+        flat = np.ascontiguousarray(a).reshape(-1)
+        if flat.size > DUMP_MAX_ELEMENTS:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            flat = flat[np.sort(rng.choice(flat.size, DUMP_MAX_ELEMENTS, replace=False))]
+            a = flat
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError("--dump-outputs: more than %d bytes at %s" % (DUMP_MAX_BYTES, name))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = a.nbytes
+    return written
+
+
+def run_mode(args, scaling, rank, world, device, dp, want_tables, overlap=None, dump=None):
     """Build the trainer for one scaling mode, pre-fill its replay shard, run W
-    warm-up + K timed steps between barriers.  Returns the raw measurements."""
+    warm-up + K timed steps between barriers (then, with `dump`, write the last
+    step's outputs there).  Returns the raw measurements."""
     import gc
     import torch.distributed as dist
     torch.manual_seed(1234 + rank)
@@ -801,10 +865,18 @@ def run_mode(args, scaling, rank, world, device, dp, want_tables, overlap=None):
     hist.profile(True)
     steps_before = trainer.steps
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    logged, log_fn = {}, None
+
+    def keep_logged(key, value, *a, **kw):          # --dump-outputs: the device scalars (loss, norms) of the last step
+        if isinstance(value, torch.Tensor):
+            logged[key] = value
+        return log_fn(key, value, *a, **kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
+        if dump and i == args.steps - 1:
+            log_fn, trainer.value_log.log = trainer.value_log.log, keep_logged
         one_step()
         marks[i + 1].record()
     torch.cuda.synchronize()
@@ -812,6 +884,10 @@ def run_mode(args, scaling, rank, world, device, dp, want_tables, overlap=None):
         dist.barrier()
     dt = time.perf_counter() - t0
     launches, gather_ms = hist.profile(False)
+    if log_fn is not None:
+        del trainer.value_log.log
+    if dump:
+        dump_outputs(dump, trainer, hist, targs["history_mode"]["type"] == "prioritized_replay", logged)
     acted = trainer.steps - steps_before
     step_ms = np.array([marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)])
     if world > 1:
@@ -922,6 +998,7 @@ def other_config_record(args, name, rank, world, device):
     sub.config, sub.steps, sub.warmup = name, args.other_steps, 20
     sub.mbatch = sub.nstep_train = sub.burn_in = sub.nstep_target = sub.envs = None
     sub.train_arg, sub.frame_dedup, sub.replay_size, sub.no_acting = [], False, 1000000, False
+    sub.dump_outputs = None
     res = run_mode(sub, "strong", rank, world, device, None, want_tables=False)
     head = summary(res, world, sub.steps)
     algo, avg_ms, achieved = gather_roofline(res)
@@ -984,16 +1061,18 @@ def main():
     # so learner steps/s is comparable across N); the weak run (every rank keeps the full
     # configured batch on its own full-size shard) rides along as the `weak` sub-record.
     modes = [args.scaling] if args.scaling != "both" else (["strong", "weak"] if world > 1 else ["strong"])
-    runs = [run_mode(args, m, rank, world, device, dp, want_tables=(i == 0)) for i, m in enumerate(modes)]
+    dump = args.dump_outputs if rank == 0 else None
+    runs = [run_mode(args, m, rank, world, device, dp, want_tables=(i == 0), dump=dump if i == 0 else None)
+            for i, m in enumerate(modes)]
     res = runs[0]
-    # N > 1: the headline keeps the synchronous actor (same algorithm as N = 1); the overlapped schedule (actor weights
-    # one learner step stale) is measured next to it where a rank's batch is small enough for it to pay
+    # N > 1 (--full): the headline keeps the synchronous actor (same algorithm as N = 1); the overlapped schedule (actor
+    # weights one learner step stale) is measured next to it where a rank's batch is small enough for it to pay
     overlapped = None
-    if world > 1 and args.overlap_acting == "off" and not args.no_acting and modes[0] == "strong" \
+    if args.full and world > 1 and args.overlap_acting == "off" and not args.no_acting and modes[0] == "strong" \
             and 0 < res["B"] * res["T"] <= 8192 and res["T"] > 1:
         overlapped = run_mode(args, "strong", rank, world, device, dp, want_tables=False, overlap="on")
     measured_peak = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             import ctypes as C
             measured_peak = copy_peak(device, lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream))
@@ -1132,13 +1211,13 @@ def main():
                                                   "inside a replay); the per-kernel figures here come from the same step issued launch by launch"
         if args.config == "iqn_lstm":
             out["config"]["lstm_state"] = "2x512 f32 per transition"
-        if world == 1 and not args.no_cpu_baseline and args.config == "iqn_lstm":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config == "iqn_lstm":
             try:
                 out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
                 out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
             except Exception as e:            # the baseline must never sink the GPU number
                 out["cpu_baseline"] = {"error": repr(e)}
-        elif world == 1 and not args.no_cpu_baseline:
+        elif args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline_t1(args.config)
                 out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
@@ -1146,7 +1225,7 @@ def main():
                 out["cpu_baseline"] = {"error": repr(e)}
         plain = all(v is None for v in (args.mbatch, args.nstep_train, args.burn_in, args.nstep_target, args.envs)) \
             and not (args.train_arg or args.frame_dedup or args.no_acting or args.amp != "none" or args.replay_size != 1000000)
-        if world == 1 and dp is None and args.config == "iqn_lstm" and plain and not args.no_other_configs:
+        if args.full and world == 1 and dp is None and args.config == "iqn_lstm" and plain and not args.no_other_configs:
             # BASELINE configs[1] and [2] ride along in the driver's line (same protocol, own roofline and CPU baseline)
             out["other_configs"] = {}
             for name in ("dqn_uniform", "rainbow_iqn"):

@@ -8,11 +8,11 @@ OUT="gpurun_out/$TAG"; mkdir -p "$OUT"
 for w in $WHAT; do
   case $w in
     tests)   timeout 900 python -m pytest tests -m gpu -x -q --timeout 300 -o faulthandler_timeout=240 > "$OUT/pytest.log" 2>&1; echo "pytest rc=$?" | tee -a "$OUT/pytest.log"; tail -15 "$OUT/pytest.log";;
-    bench)   timeout 900 python bench.py --steps 20 --warmup 5 > "$OUT/bench_iqn_lstm.json" 2> "$OUT/bench_iqn_lstm.err"; echo "bench rc=$?"; tail -c 1500 "$OUT/bench_iqn_lstm.err"; head -c 6000 "$OUT/bench_iqn_lstm.json";;
-    bench23) for c in rainbow_iqn dqn_uniform; do timeout 600 python bench.py --config $c --steps 50 --warmup 10 > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err"; echo "bench $c rc=$?"; tail -c 800 "$OUT/bench_$c.err"; head -c 5000 "$OUT/bench_$c.json"; done;;
+    bench)   timeout 900 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_iqn_lstm.json" 2> "$OUT/bench_iqn_lstm.err"; echo "bench rc=$?"; tail -c 1500 "$OUT/bench_iqn_lstm.err"; head -c 6000 "$OUT/bench_iqn_lstm.json";;
+    bench23) for c in rainbow_iqn dqn_uniform; do timeout 600 python bench.py --full --config $c --steps 50 --warmup 10 > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err"; echo "bench $c rc=$?"; tail -c 800 "$OUT/bench_$c.err"; head -c 5000 "$OUT/bench_$c.json"; done;;
     ctests)  timeout 600 python -m pytest tests/test_conv_in_gpu.py tests/test_fused_gpu.py tests/test_models_gpu.py -x -q --timeout 300 > "$OUT/pytest_conv.log" 2>&1; echo "pytest conv rc=$?"; tail -25 "$OUT/pytest_conv.log";;
     cprobe)  timeout 300 python tools/conv_in_probe.py > "$OUT/conv_in_probe.jsonl" 2> "$OUT/conv_in_probe.err"; echo "cprobe rc=$?"; cat "$OUT/conv_in_probe.jsonl"; tail -3 "$OUT/conv_in_probe.err";;
-    benchq)  timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_quick.json" 2> "$OUT/bench_quick.err"; echo "benchq rc=$?"; tail -c 600 "$OUT/bench_quick.err"; python - "$OUT/bench_quick.json" <<'PY'
+    benchq)  timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_quick.json" 2> "$OUT/bench_quick.err"; echo "benchq rc=$?"; tail -c 600 "$OUT/bench_quick.err"; python - "$OUT/bench_quick.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print("ms/step", d["ms_per_step"], d["step_ms"], "value", d["value"])
@@ -47,8 +47,8 @@ PY
     probe)   timeout 300 python tools/convert_probe.py > "$OUT/convert_probe.jsonl" 2> "$OUT/convert_probe.err"; echo "probe rc=$?"; cat "$OUT/convert_probe.jsonl"; tail -3 "$OUT/convert_probe.err";;
     prof)    R="$(pwd)"; export TMPDIR=/tmp; (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/stats" -o bench -- python "$R/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --profile-steps 0 > "$R/$OUT/bench_under_rocprof.json" 2> "$R/$OUT/bench_under_rocprof.err"); echo "prof rc=$?"; python tools/summarize_prof.py "$OUT" > "$OUT/summary.txt" 2>&1; head -60 "$OUT/summary.txt"; find "$OUT" -name "*kernel_trace.csv" -delete; find "$OUT" -name "*.db" -delete;;
     gprobe)  for nt in 1 2; do PROBE_SIZE=1000000 PROBE_NT=$nt PROBE_ITERS=10 timeout 300 python tools/gather_probe.py >> "$OUT/gather_probe.jsonl" 2>> "$OUT/gather_probe.err"; done; echo "gprobe rc=$?"; cat "$OUT/gather_probe.jsonl";;
-    overlap) timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --train-arg overlap_acting=true > "$OUT/bench_overlap.json" 2> "$OUT/bench_overlap.err"; echo "overlap rc=$?"; tail -c 600 "$OUT/bench_overlap.err"; head -c 1500 "$OUT/bench_overlap.json"; echo;;
-    dedup)   timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --frame-dedup > "$OUT/bench_dedup.json" 2> "$OUT/bench_dedup.err"; echo "dedup rc=$?"; tail -c 600 "$OUT/bench_dedup.err"; head -c 2500 "$OUT/bench_dedup.json"; echo;;
+    overlap) timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --train-arg overlap_acting=true > "$OUT/bench_overlap.json" 2> "$OUT/bench_overlap.err"; echo "overlap rc=$?"; tail -c 600 "$OUT/bench_overlap.err"; head -c 1500 "$OUT/bench_overlap.json"; echo;;
+    dedup)   timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --frame-dedup > "$OUT/bench_dedup.json" 2> "$OUT/bench_dedup.err"; echo "dedup rc=$?"; tail -c 600 "$OUT/bench_dedup.err"; head -c 2500 "$OUT/bench_dedup.json"; echo;;
     tests1)  timeout 600 python -m pytest tests/test_multirank_gpu.py -x -q --timeout 300 -o faulthandler_timeout=240 > "$OUT/pytest_multirank.log" 2>&1; echo "pytest multirank rc=$?"; tail -40 "$OUT/pytest_multirank.log";;
     find)    timeout 900 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --profile-steps 0 --miopen-find > "$OUT/bench_miopen_find.json" 2> "$OUT/bench_miopen_find.err"; echo "find rc=$?"; tail -c 400 "$OUT/bench_miopen_find.err"; head -c 700 "$OUT/bench_miopen_find.json"; echo;;
     actprobe) R="$(pwd)"; export TMPDIR=/tmp; (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/act_stats" -o act -- python "$R/tools/acting_probe.py" 200 > "$R/$OUT/acting_probe.json" 2> "$R/$OUT/acting_probe.err"); echo "actprobe rc=$?"; cat "$OUT/acting_probe.json"; python - "$OUT" <<'PY'
@@ -98,7 +98,7 @@ PY
              find "$OUT" -name "*kernel_trace.csv" -delete; find "$OUT" -name "*counter_collection.csv" -size +1M -delete; find "$OUT" -name "*.db" -delete;;
     dist1)   BENCH_FORCE_DIST=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29577 bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --profile-steps 0 > "$OUT/bench_rccl_forced_world1.json" 2> "$OUT/bench_rccl_forced_world1.err"; echo "dist1 rc=$?"; tail -c 500 "$OUT/bench_rccl_forced_world1.err"; head -c 600 "$OUT/bench_rccl_forced_world1.json"; echo;;
     selflaunch) BENCH_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --profile-steps 0 > "$OUT/bench_selflaunch_world1.json" 2> "$OUT/bench_selflaunch_world1.err"; echo "selflaunch rc=$?"; tail -c 500 "$OUT/bench_selflaunch_world1.err"; head -c 1500 "$OUT/bench_selflaunch_world1.json"; echo
-             timeout 900 python bench.py --gpus 2 --share-gpu --steps 5 --warmup 2 --no-cpu-baseline --profile-steps 0 > "$OUT/bench_gpus2_shared_gloo.json" 2> "$OUT/bench_gpus2_shared_gloo.err"; echo "gpus2 rc=$?"; tail -c 800 "$OUT/bench_gpus2_shared_gloo.err"; python - "$OUT/bench_gpus2_shared_gloo.json" <<'PY'
+             timeout 900 python bench.py --full --gpus 2 --share-gpu --steps 5 --warmup 2 --no-cpu-baseline --profile-steps 0 > "$OUT/bench_gpus2_shared_gloo.json" 2> "$OUT/bench_gpus2_shared_gloo.err"; echo "gpus2 rc=$?"; tail -c 800 "$OUT/bench_gpus2_shared_gloo.err"; python - "$OUT/bench_gpus2_shared_gloo.json" <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -176,6 +176,6 @@ print(json.dumps(res, indent=1)); json.dump(res, open(os.path.join(out, "conv3_p
 PY
              find "$OUT" -path "*c3pmc*" -name "*.csv" -size +1M -delete; find "$OUT" -path "*c3pmc*" -name "*.db" -delete;;
     f32pipe) MIRL_GEMM3=0 MIRL_CONV1_BF16=0 MIRL_CONV3=0 timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --profile-steps 0 > "$OUT/bench_f32_pipe_only.json" 2> "$OUT/bench_f32_pipe_only.err"; echo "f32pipe rc=$?"; head -c 700 "$OUT/bench_f32_pipe_only.json"; echo;;
-    noact)   timeout 600 python bench.py --steps 20 --warmup 5 --no-acting --no-cpu-baseline > "$OUT/bench_noacting.json" 2> "$OUT/bench_noacting.err"; echo "noact rc=$?"; head -c 3000 "$OUT/bench_noacting.json";;
+    noact)   timeout 600 python bench.py --full --steps 20 --warmup 5 --no-acting --no-cpu-baseline > "$OUT/bench_noacting.json" 2> "$OUT/bench_noacting.err"; echo "noact rc=$?"; head -c 3000 "$OUT/bench_noacting.json";;
   esac
 done

@@ -31,7 +31,7 @@ for w in "$@"; do
       env $X timeout 300 python tools/acting_probe.py 400 --envs=$E > "$OUT/$w.json" 2> "$OUT/$w.err"; echo "$w rc=$?"; cat "$OUT/$w.json"; tail -2 "$OUT/$w.err";;
     share8|share8old|share4|share2|share8serial|share4serial|share2serial)
       N=${w#share}; N=${N%old}; N=${N%serial}; X=""; F=""; case $w in *old) X="MIRL_ACT_FUSED=0";; *serial) F="--train-arg overlap_passes=false";; esac
-      env $X timeout 600 python bench.py --steps 30 --warmup 10 --no-cpu-baseline $F --mbatch $((512/N)) --envs $((256/N)) --replay-size $((1000000/N)) > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"; echo "$w rc=$?"; tail -c 400 "$OUT/bench_$w.err"
+      env $X timeout 600 python bench.py --full --steps 30 --warmup 10 --no-cpu-baseline $F --mbatch $((512/N)) --envs $((256/N)) --replay-size $((1000000/N)) > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"; echo "$w rc=$?"; tail -c 400 "$OUT/bench_$w.err"
       python - "$OUT/bench_$w.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -40,7 +40,7 @@ PY
       ;;
     benchq|benchqold|benchq_nopol|benchq_noact)
       X=""; F=""; case $w in *old) X="MIRL_ACT_FUSED=0";; *_nopol) F="--no-policy-outputs";; *_noact) F="--no-acting";; esac
-      env $X timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline $F > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"; echo "$w rc=$?"; tail -c 400 "$OUT/bench_$w.err"
+      env $X timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline $F > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"; echo "$w rc=$?"; tail -c 400 "$OUT/bench_$w.err"
       python - "$OUT/bench_$w.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -49,8 +49,8 @@ for k in d["roofline_all"]["kernels"][:14]:
     print(k["kernel"], k["launches_per_step"], k["avg_us"], k["ms_per_step"], k.get("frac_of_roofline"))
 PY
       ;;
-    bench)   timeout 900 python bench.py --steps 20 --warmup 5 > "$OUT/bench_iqn_lstm.json" 2> "$OUT/bench_iqn_lstm.err"; echo "bench rc=$?"; tail -c 800 "$OUT/bench_iqn_lstm.err"; head -c 3000 "$OUT/bench_iqn_lstm.json"; echo;;
-    bench23) for c in rainbow_iqn dqn_uniform; do timeout 600 python bench.py --config $c --steps 200 --warmup 20 > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err"; echo "bench $c rc=$?"; tail -c 400 "$OUT/bench_$c.err"; python - "$OUT/bench_$c.json" <<'PY'
+    bench)   timeout 900 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_iqn_lstm.json" 2> "$OUT/bench_iqn_lstm.err"; echo "bench rc=$?"; tail -c 800 "$OUT/bench_iqn_lstm.err"; head -c 3000 "$OUT/bench_iqn_lstm.json"; echo;;
+    bench23) for c in rainbow_iqn dqn_uniform; do timeout 600 python bench.py --full --config $c --steps 200 --warmup 20 > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err"; echo "bench $c rc=$?"; tail -c 400 "$OUT/bench_$c.err"; python - "$OUT/bench_$c.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print("ms/step", round(d["ms_per_step"], 3), d["step_ms"], "roofline", d["roofline"]["frac"], "roofline_step", (d.get("roofline_step") or {}).get("frac"))
