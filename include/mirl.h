@@ -347,6 +347,33 @@ int mirl_loss_iqn(int64_t M, int32_t N, int32_t Nt, int32_t A, const float* z,
                   const float* weights, double kappa, double row_scale,
                   float* row_loss, float* dz, float* abs_td, void* stream);
 
+/* ---- distributional DQN (C51), csrc/c51.hip ---------------------------------
+ * Target distribution (training/torch/dist_dqn.py:30-97).  logits_target /
+ * logits_select [M][A][Z] (the same pointer without double-Q), support [Z] (the
+ * policy's linspace(vmin, vmax, Z) buffer, read as given).  Selection:
+ * first-maximum argmax_a sum_j softmax(select)_aj * support_j; p = softmax of the
+ * target logits of that action; Tz_j = (r + mask * gamma^n) * support_j
+ * (projection 0, the reference's formula, :82-83) or r + mask * gamma^n *
+ * support_j (projection 1, the paper's), clamped to [vmin, vmax]; b = (Tz - vmin)
+ * / delta_z; l = floor(b), u = ceil(b); bin l += p (u - b) over ascending j, then
+ * bin u += p (b - l) (:89-94: two index_add_ passes, the same order, no atomics).
+ * Where b is an integer the reference drops the atom's mass (both shares are 0);
+ * projection 1 gives it all to bin b.  targets [M][Z].  2 <= Z <= 256.          */
+int mirl_q_target_c51(int64_t M, int32_t A, int32_t Z, const float* logits_target, const float* logits_select,
+                      const float* support, const float* returns, const float* nsteps, const float* masks,
+                      double gamma, double vmin, double vmax, double delta_z, int32_t projection,
+                      float* targets, void* stream);
+/* DistDQN._compute_grads loss (dist_dqn.py:99-142), forward and analytic
+ * backward in one pass.  logits [M][A][Z], targets [M][Z]; p = softmax of the
+ * chosen action's atoms.  mode: 0 = cross-entropy -sum_j t_j log(clamp(p_j,
+ * 1e-5, 1 - 1e-5)), 1 = mse, 2 = huber (kappa) of p - t, summed over atoms.
+ * weights (importance weights) may be NULL; row_scale as in mirl_loss_dqn.
+ * Outputs: row_loss[M] (weighted), dlogits[M][A][Z] = d loss / d logits (zero
+ * outside the chosen action), report[M] = the unweighted row loss (:116).  Z <= 256. */
+int mirl_loss_c51(int64_t M, int32_t A, int32_t Z, const float* logits, const int64_t* actions,
+                  const float* targets, const float* weights, int32_t mode, double kappa, double row_scale,
+                  float* row_loss, float* dlogits, float* report, void* stream);
+
 /* ---- recurrent core: fused LSTM-cell pointwise step --------------------------
  * Replaces the per-step elementwise chain of torch.nn.LSTMCell inside
  * rltime/models/torch/modules/lstm.py:83-116 (time loop with state reset on
@@ -691,6 +718,15 @@ int mirl_actor_head(int32_t E, int32_t N, int32_t A, const float* adv, const flo
 int mirl_actor_head_rng(int32_t E, int32_t N, int32_t A, const float* adv, int32_t adv_pitch, const float* val, int32_t Q,
                         const double* eps, const double* expo, double eps_min, uint64_t rng_seed,
                         const uint64_t* rng_step, int32_t* actions, float* qvalues, float* eps_used, void* stream);
+/* The distributional acting head (policies/torch/dist_dqn.py:_actor_predict_postprocess after dqn.py:74-87):
+ * adv [E] rows of A*Z outputs (pitch adv_pitch floats), val [E][Z] (pitch val_pitch) or NULL; per atom V + A -
+ * mean_a A when val is given, softmax over the Z atoms, q_a = sum_j p_aj support_j -> qvalues [E][A], first
+ * maximum, then epsilon-greedy as mirl_actor_head_rng (rng_step given: the same Philox draws, so C51 and DQN
+ * actors make the same exploration decisions from the same seed) or as mirl_actor_head (u / rnd).  Z <= 256. */
+int mirl_actor_head_c51(int32_t E, int32_t A, int32_t Z, const float* adv, int32_t adv_pitch, const float* val,
+                        int32_t val_pitch, const float* support, const double* eps, const double* expo, double eps_min,
+                        const float* u, const int64_t* rnd, uint64_t rng_seed, const uint64_t* rng_step,
+                        int32_t* actions, float* qvalues, float* eps_used, void* stream);
 /* The frame-stack wrapper's shift for a device-resident vector env (env_wrappers/common.py:141-178
  * with auto-reset): out[e] = [in[e] planes 1..P-1 — or zeros where dones[e] —, newest[e]].  One launch
  * (the synthetic env's torch expression of it is four).                                              */

@@ -151,6 +151,9 @@ _SIGNATURES = {
     "mirl_q_target_iqn": [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp],
     "mirl_loss_dqn": [_i64, _i32, _vp, _vp, _vp, _vp, _f64, _i32, _f64, _vp, _vp, _vp, _vp],
     "mirl_loss_iqn": [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp],
+    "mirl_q_target_c51": [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _f64, _i32, _vp, _vp],
+    "mirl_loss_c51": [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp],
+    "mirl_actor_head_c51": [_i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _f64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp],
     "mirl_lstm_cell_fwd": [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mirl_lstm_seq_supported": [_i32, _i32, _i32],
     "mirl_lstm_seq_workspace_bytes": [_i32, _i32, _P(_i64)],

@@ -237,7 +237,8 @@ class Actor(ActingInterface):
         from rltime_amd._lib import lib, check
         adv, val, n = pol.actor_head_raw(state, 1)
         adv = adv.contiguous()
-        A = adv.shape[1]
+        Z = getattr(pol, "num_atoms", None)                  # C51: A * Z outputs per row, Z per value row
+        A = adv.shape[1] // Z if Z else adv.shape[1]
         E = adv.shape[0] // n
         dev = adv.device
         actions = torch.empty(E, dtype=torch.int32, device=dev)
@@ -253,6 +254,12 @@ class Actor(ActingInterface):
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)   # noqa: E731
         if val is not None:
             val = val.contiguous()
+        if Z:
+            check(lib.mirl_actor_head_c51(E, A, Z, p(adv), A * Z, p(val), Z, p(pol.support),
+                                          p(eps) if expl is not None else C.c_void_p(None), p(expo), eps_min, p(u), p(rnd),
+                                          0, C.c_void_p(None), p(actions), p(qvalues), C.c_void_p(None),
+                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mirl_actor_head_c51")
+            return actions, qvalues
         check(lib.mirl_actor_head(E, n, A, p(adv), p(val), val.shape[1] if val is not None else 0,
                                   p(eps) if expl is not None else C.c_void_p(None), p(expo), eps_min, p(u), p(rnd),
                                   p(actions), p(qvalues), C.c_void_p(None),

@@ -136,8 +136,12 @@ class FastActingStep:
         head's VALUE stream is then skipped — argmax_a mean_N (V + A - mean_a A) = argmax_a mean_N A (dqn.py:74-87), so the
         chosen actions are the same while the head's widest GEMM is half as wide."""
         self.actor = actor
-        self.need_q = bool(need_q)
         pol = self.pol = actor._policy
+        # C51 (policies/dist_dqn.py): A * Z advantage outputs, Z value outputs; the softmax over atoms follows the dueling
+        # combine, so the advantage stream alone does not rank the actions — the full head is always evaluated
+        self.c51 = hasattr(pol, "num_atoms")
+        self.Z = pol.num_atoms if self.c51 else 1
+        self.need_q = bool(need_q) or self.c51
         self.cnn, self.lstm, self.fc, self.dueling = self._parts(pol)
         self.fc_layer = pol.model.layers[-1]
         self.iqn = hasattr(pol, "num_sampling_quantiles")
@@ -181,7 +185,7 @@ class FastActingStep:
         self.fc_b = torch.empty(h1 + hv, **f32)
         # advantage and value outputs as ONE GEMM over the joint hidden activation: block-diagonal weights
         self.na, self.nq = pol.out_layer.out_features, (pol.value_layer.out_features if self.dueling else 0)
-        assert self.na == A and self.nq == (1 if self.dueling else 0)
+        assert self.na == A * self.Z and self.nq == (self.Z if self.dueling else 0)
         self.out_w = torch.zeros((self.na + self.nq, h1 + hv), **f32)
         self.out_b = torch.zeros(self.na + self.nq, **f32)
         self.adv_w = torch.zeros((self.na, h1), **f32)           # advantage stream alone (need_q=False)
@@ -214,7 +218,8 @@ class FastActingStep:
                 self.conv_dims = (h1o, w1o, h2o, w2o, h3o, w3o)
         self.f_lstm = fused and self.lstm is not None and bool(lib.mirl_act_lstm_supported(E, H, F + H))
         D = int(self.freq.shape[0]) if self.iqn else 0
-        self.f_head = fused and (mode == "2" or E * self.N <= 2048) and self.fc.in_features == W and self.dueling \
+        # (the output layer in the hidden layer's epilogue selects on scalar Q values: not for C51's distributions)
+        self.f_head = fused and not self.c51 and (mode == "2" or E * self.N <= 2048) and self.fc.in_features == W and self.dueling \
             and bool(lib.mirl_act_head_supported(E, self.N, W, D, h1 + hv, self.na + self.nq))
         # the quantile product as one launch at any batch (cos features + embedding product + ReLU + feature multiply)
         self.f_embed = fused and self.iqn and W % 16 == 0 and D % 16 == 0 and 0 < D <= 64 and E * self.N <= (1 << 24)
@@ -406,6 +411,12 @@ class FastActingStep:
             hidden = torch._addmm_activation(self.fc_b[:self.h1], feat, self.fc_w[:self.h1].t(), use_gelu=False)
             outs = torch.addmm(self.out_b[:self.na], hidden, self.adv_w.t())   # (rows, A): the advantage stream
             pitch, val = self.na, None
+        if self.c51:
+            check(lib.mirl_actor_head_c51(
+                E, self.A, self.Z, _p(outs), pitch, val, pitch, _p(pol.support), None if greedy else _p(self.eps),
+                None if greedy else _p(self.expo), self.eps_min, None, None, self.rng_seed, None if greedy else _p(self.rng_step),
+                _p(self.actions), _p(self.qvalues), None, _stream()), "mirl_actor_head_c51")
+            return
         check(lib.mirl_actor_head_rng(
             E, N, self.A, _p(outs), pitch, val, pitch, None if greedy else _p(self.eps), None if greedy else _p(self.expo),
             self.eps_min, self.rng_seed, None if greedy else _p(self.rng_step), _p(self.actions), _p(self.qvalues), None, _stream()),
@@ -432,8 +443,9 @@ class FastActingStep:
 
     def set_need_q(self, need_q):
         """Switch between the full dueling head and the advantage stream alone; the step graphs are re-captured."""
-        if bool(need_q) != self.need_q:
-            self.need_q = bool(need_q)
+        need_q = bool(need_q) or self.c51
+        if need_q != self.need_q:
+            self.need_q = need_q
             self._rollouts.clear()
             self._capture()
 

@@ -13,13 +13,16 @@ class DQN(TorchTrainer):
         """dqn.py:15-46."""
         assert loss_aggregation in ("mean", "sum")
         assert loss_timestep_aggregation in (None, False, "", "mean", "sum")
-        assert loss_mode in ("huber", "mse"), "%s is not a valid q-learning loss mode" % loss_mode
+        self._check_loss_mode(loss_mode)
         self.double_q = double_q
         self.loss_mode = loss_mode
         self.huber_kappa = huber_kappa
         self.loss_aggregation = loss_aggregation
         self.loss_timestep_aggregation = loss_timestep_aggregation or None
         super()._train(history_mode=history_mode, **kwargs)
+
+    def _check_loss_mode(self, loss_mode):
+        assert loss_mode in ("huber", "mse"), "%s is not a valid q-learning loss mode" % loss_mode
 
     @staticmethod
     def create_policy(**kwargs):

@@ -7,6 +7,7 @@ Reference arithmetic restated by the kernels:
   training/torch/iqn.py:36-52      IQN bootstrap value
   training/torch/dqn.py:98-130,141-161   DQN loss, IS weights, aggregation
   training/torch/iqn.py:77-120     IQN pairwise quantile-Huber loss
+  training/torch/dist_dqn.py:30-97,99-142   C51 target projection and loss (csrc/c51.hip)
 """
 import ctypes as C
 
@@ -63,6 +64,53 @@ def q_target_iqn(z_target, z_select, returns, nsteps, masks, gamma, vf_eps=None)
         _p(_f32(nsteps)), _p(_f32(masks)), float(gamma), float(vf_eps or 0.0),
         _p(out), _stream()), "mirl_q_target_iqn")
     return out
+
+
+_PROJECTIONS = {"reference": 0, "paper": 1}
+_C51_MODES = {"crossentropy": 0, "mse": 1, "huber": 2}
+
+
+def q_target_c51(logits_target, logits_select, support, returns, nsteps, masks, gamma, vmin, vmax,
+                 projection="reference"):
+    """dist_dqn.py:30-97 -> (M, Z) target distributions.  logits_* (M, A, Z); logits_select may be
+    logits_target itself (no double-Q).  projection="paper" is not the reference's formula (see
+    include/mirl.h mirl_q_target_c51)."""
+    same = logits_select is logits_target
+    logits_target = _f32(logits_target)
+    logits_select = logits_target if same else _f32(logits_select)
+    M, A, Z = logits_target.shape
+    assert logits_select.shape == (M, A, Z)
+    support = _f32(support)
+    assert support.shape == (Z,)
+    out = torch.empty((M, Z), dtype=torch.float32, device=logits_target.device)
+    delta_z = float(vmax - vmin) / (Z - 1)          # dist_dqn.py:81, a Python float like the reference's
+    check(lib.mirl_q_target_c51(
+        M, A, Z, _p(logits_target), _p(logits_select), _p(support), _p(_f32(returns)), _p(_f32(nsteps)),
+        _p(_f32(masks)), float(gamma), float(vmin), float(vmax), delta_z, _PROJECTIONS[projection], _p(out),
+        _stream()), "mirl_q_target_c51")
+    return out
+
+
+class _C51Loss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, actions, targets, weights, mode, kappa, scale):
+        xc = _f32(logits)
+        M, A, Z = xc.shape
+        rows = torch.empty(M, dtype=torch.float32, device=xc.device)
+        rep = torch.empty(M, dtype=torch.float32, device=xc.device)
+        dx = torch.empty_like(xc)
+        w = _f32(weights) if weights is not None else None
+        check(lib.mirl_loss_c51(
+            M, A, Z, _p(xc), _p(actions.to(torch.int64).contiguous()), _p(_f32(targets)), _p(w),
+            _C51_MODES[mode], float(kappa), float(scale), _p(rows), _p(dx), _p(rep), _stream()), "mirl_loss_c51")
+        ctx.save_for_backward(dx)
+        ctx.mark_non_differentiable(rep)
+        return rows.sum() * scale, rep
+
+    @staticmethod
+    def backward(ctx, g_loss, g_rep):
+        (dx,) = ctx.saved_tensors
+        return dx * g_loss, None, None, None, None, None, None
 
 
 class _DQNLoss(torch.autograd.Function):
@@ -125,3 +173,10 @@ def iqn_loss(z, taus, actions, targets, weights=None, kappa=1.0,
     """-> (scalar loss differentiable w.r.t. z, mean |td| report (M,))."""
     scale = row_scale(z.shape[0], timesteps, batch_mode, time_mode)
     return _IQNLoss.apply(z, taus, actions, targets, weights, kappa, scale)
+
+
+def c51_loss(logits, actions, targets, weights=None, mode="crossentropy", kappa=1.0,
+             timesteps=1, batch_mode="mean", time_mode=None):
+    """dist_dqn.py:99-142 -> (scalar loss differentiable w.r.t. logits (M, A, Z), unweighted row loss report (M,))."""
+    scale = row_scale(logits.shape[0], timesteps, batch_mode, time_mode)
+    return _C51Loss.apply(logits, actions, targets, weights, mode, kappa, scale)
