@@ -68,6 +68,57 @@ def test_target_kernel_shape_sweep(M, A, Z):
     np.testing.assert_allclose(got_p.sum(1).numpy(), 1.0, atol=1e-5)
 
 
+def _sweep_inputs(M, A, Z, seed):
+    """The input recipe of test_target_kernel_shape_sweep."""
+    g = torch.Generator().manual_seed(seed)
+    lt, ls = torch.randn(M, A, Z, generator=g) * 2, torch.randn(M, A, Z, generator=g) * 2
+    r = torch.where(torch.rand(M, generator=g) < 0.5, torch.randint(-1, 2, (M,), generator=g).float(), torch.randn(M, generator=g))
+    n = torch.randint(1, 4, (M,), generator=g).float()
+    mk = (torch.rand(M, generator=g) > 0.3).float()
+    return lt, ls, r, n, mk
+
+
+# a lane owns atoms l, l + 64, l + 128, l + 192: every strip boundary, the smallest supports and a single action
+STRIP_Z = (2, 3, 63, 64, 65, 127, 128, 129, 192, 193, 255, 256)
+
+
+@pytest.mark.parametrize("M,A,Z", [(m, a, z) for m in (7, 512, 4099) for a in (1, 2, 18) for z in STRIP_Z])
+def test_target_kernel_strip_boundaries(M, A, Z):
+    from rltime_amd.training import qops
+    lt, ls, r, n, mk = _sweep_inputs(M, A, Z, M * 7 + A * 3 + Z)
+    sup = torch.linspace(-10, 10, Z)
+    want = c51.target(lt, ls, sup, r, n, mk, 0.99, -10, 10)
+    if A == 1 or M < 512:
+        # one left-out row of 7 would be 14 %: nothing is left out, the float64 reference itself has no near-tie
+        if A > 1:
+            top64 = (torch.softmax(ls.double(), -1) * sup.double()).sum(2).topk(2, dim=1).values
+            assert bool(((top64[:, 0] - top64[:, 1]) > 1e-5).all())
+        clear = torch.ones(M, dtype=torch.bool)
+    else:
+        ev = (torch.softmax(ls, -1) * sup).sum(2)
+        top = ev.topk(2, dim=1).values
+        clear = (top[:, 0] - top[:, 1]) > 1e-5
+        assert clear.float().mean() > 0.99
+    dev = [t.cuda() for t in (lt, ls, sup, r, n, mk)]
+    got = qops.q_target_c51(*dev, 0.99, -10, 10).cpu()
+    err = float((got[clear] - want[clear]).abs().max())
+    print("reference projection M=%d A=%d Z=%d: max |kernel - restatement| %.3e" % (M, A, Z, err))
+    np.testing.assert_allclose(got[clear].numpy(), want[clear].numpy(), rtol=0, atol=1e-6)
+    assert np.array_equal(got[clear].numpy() == 0, want[clear].numpy() == 0)          # the dropped bins, exactly
+    # the paper's projection against float64: the float32 arithmetic of the restatement itself is e_ref away from it (up to
+    # 1.9e-5 at Z = 256 on these inputs), the kernel may be as far again
+    best = c51.select_actions(ls.double(), sup.double())
+    p64 = torch.softmax(lt.double()[torch.arange(M), best], -1)
+    want64 = c51.project(p64, r.double(), n.double(), mk.double(), sup.double(), 0.99, -10, 10, "paper")
+    ref_p = c51.target(lt, ls, sup, r, n, mk, 0.99, -10, 10, "paper")
+    e_ref = float((ref_p[clear].double() - want64[clear]).abs().max())
+    got_p = qops.q_target_c51(*dev, 0.99, -10, 10, "paper").cpu()
+    e_got = float((got_p[clear].double() - want64[clear]).abs().max())
+    print("paper projection M=%d A=%d Z=%d: e_ref %.3e kernel %.3e" % (M, A, Z, e_ref, e_got))
+    assert e_got <= 2.0 * e_ref + 1e-6, (e_got, e_ref)
+    np.testing.assert_allclose(got_p.sum(1).numpy(), 1.0, atol=1e-5)
+
+
 def test_target_kernel_refuses_too_many_atoms():
     from rltime_amd._lib import MirlError
     from rltime_amd.training import qops
@@ -101,6 +152,78 @@ def test_loss_kernel_matches_reference():
     # the fixture's rows 0 and 1 sit in the clamp: some atoms below 1e-5, one above 1 - 1e-5
     p = torch.softmax(torch.from_numpy(logits[[0, 1], 0]), -1)
     assert (p < 1e-5).any() and (p > 1 - 1e-5).any()
+
+
+@pytest.mark.parametrize("M", [1, 513])
+@pytest.mark.parametrize("A", [1, 18])
+@pytest.mark.parametrize("Z", [2, 64, 65, 128, 129, 256])
+def test_loss_kernel_strip_boundaries(M, A, Z):
+    """loss, report and gradient of the three modes against float64 autograd of the restatement, with rows in the clamp of
+    the cross-entropy whose peak sits in the last strip a lane owns."""
+    from rltime_amd.training import qops
+    g = torch.Generator().manual_seed(M * 5 + A * 3 + Z)
+    logits = torch.randn(M, A, Z, generator=g) * 2
+    actions = torch.randint(0, A, (M,), generator=g)
+    targets = torch.softmax(torch.randn(M, Z, generator=g) * 2, -1)
+    weights = torch.rand(M, generator=g) + 0.5
+    peaks = []
+    if M > 1:
+        # rows 0 and 1: one atom above 1 - 1e-5, every other below 1e-5; the peak in the highest strip and one strip lower
+        peaks = [Z - 1, max(Z - 1 - 64, 0)]
+        for row, j in enumerate(peaks):
+            logits[row, actions[row], j] = 40.0
+    p64 = torch.softmax(logits.double()[torch.arange(M), actions], -1)
+    for row, j in enumerate(peaks):
+        assert float(p64[row, j]) > 1 - 1e-5 and bool((p64[row, torch.arange(Z) != j] < 1e-5).all())
+        assert j // 64 == (Z - 1) // 64 - (row if Z > 64 else 0)
+    # no probability so close to a clamp bound that float32 and float64 could pass the gradient on different sides: a float32
+    # softmax of logits below 16 in magnitude is within about 16 * 2^-23 = 2e-6 of the exact one, relatively
+    assert float(torch.minimum((p64 - 1e-5).abs() / 1e-5, (p64 - (1 - 1e-5)).abs() / 1e-5).min()) > 5e-6
+    for use_w in (False, True):
+        for mode in ("crossentropy", "huber", "mse"):
+            tag = "M=%d A=%d Z=%d w%d %s" % (M, A, Z, use_w, mode)
+            x = logits.cuda().requires_grad_(True)
+            loss, rep = qops.c51_loss(x, actions.cuda(), targets.cuda(), weights.cuda() if use_w else None, mode, 1.0, 1, "mean", None)
+            loss.backward()
+            x64 = logits.double().requires_grad_(True)
+            l64, rep64 = c51.loss(x64, actions, targets.double(), weights.double() if use_w else None, mode, 1.0, 1, "mean", None)
+            l64.backward()
+            np.testing.assert_allclose(float(loss.detach()), float(l64.detach()), rtol=1e-5, atol=1e-5, err_msg=tag)
+            np.testing.assert_allclose(rep.cpu().double().numpy(), rep64.detach().numpy(), rtol=1e-5, atol=1e-5, err_msg=tag)
+            np.testing.assert_allclose(x.grad.cpu().double().numpy(), x64.grad.numpy(), rtol=0, atol=1e-5, err_msg=tag)
+
+
+@pytest.mark.parametrize("dueling", [False, True])
+@pytest.mark.parametrize("A", [1, 18])
+@pytest.mark.parametrize("Z", [64, 65, 129, 256])
+def test_acting_head_strip_boundaries(Z, A, dueling):
+    """mirl_actor_head_c51 against the dueling combine written out in float64: q_a = sum_j softmax_j(V_j + A_aj - mean_a A_aj) z_j,
+    without a value stream softmax_j(A_aj); greedy actions wherever the float64 q-values have a clear maximum."""
+    import ctypes as C
+    from rltime_amd._lib import lib, check
+    E = 67
+    g = torch.Generator().manual_seed(Z * 3 + A + dueling)
+    adv = torch.randn(E, A, Z, generator=g) * 3
+    val = torch.randn(E, Z, generator=g) * 3 if dueling else None
+    sup = torch.linspace(-10, 10, Z)
+    x64 = adv.double()
+    if dueling:
+        x64 = val.double().unsqueeze(1) + x64 - x64.mean(1, keepdim=True)
+    q64 = (torch.softmax(x64, -1) * sup.double()).sum(-1)
+    if A > 1:
+        top = q64.topk(2, dim=1).values
+        clear = (top[:, 0] - top[:, 1]) > 1e-4
+    else:
+        clear = torch.ones(E, dtype=torch.bool)
+    assert clear.float().mean() > 0.9
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)  # noqa: E731
+    adv_d, val_d, sup_d = adv.cuda(), (val.cuda() if dueling else None), sup.cuda()
+    acts = torch.full((E,), -1, dtype=torch.int32, device="cuda")
+    q = torch.full((E, A), float("nan"), device="cuda")
+    check(lib.mirl_actor_head_c51(E, A, Z, p(adv_d), A * Z, p(val_d), Z, p(sup_d), None, None, 0.0, None, None, 0, None,
+                                  p(acts), p(q), None, C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mirl_actor_head_c51")
+    np.testing.assert_allclose(q.cpu().double().numpy(), q64.numpy(), rtol=0, atol=1e-5)
+    assert torch.equal(acts.cpu().long()[clear], q64.argmax(1)[clear])
 
 
 def _policy(dueling, A=6, Z=51, fc=64):

@@ -156,6 +156,62 @@ def test_dueling_tail_matches_separate_layers(rows, f, h1, hv, a, q):
         _close(u, v, name)
 
 
+# which backward the autograd path must take: "w" = k_tail_bwd_w (outputs per branch <= 8: the weight gradients ride along,
+# two column-sum launches), "plain" = k_tail_bwd (9 .. 16), "torch" = neither (more outputs, or a joint width that is not 4 * 2^k)
+@pytest.mark.parametrize("rows,f,h1,hv,a,q,path", [
+    (300, 64, 32, 32, 9, 1, "plain"), (300, 64, 32, 32, 16, 1, "plain"), (300, 64, 32, 32, 18, 1, "torch"),
+    (300, 64, 96, 32, 6, 1, "w"), (300, 64, 32, 96, 6, 1, "w"), (300, 64, 32, 16, 5, 3, "torch")])
+def test_dueling_tail_takes_each_backward_branch_and_is_right_on_it(rows, f, h1, hv, a, q, path):
+    """The dispatch of _DuelingTail.backward: the profile table shows which kernel ran (both tail kernels report as
+    k_tail_bwd; k_tail_bwd_w is followed by two k_colsum_partials launches, the plain kernel by one), and all eleven tensors
+    agree with float64 autograd of the separate layers, and with the float32 layers as above."""
+    import copy
+    from rltime_amd import _lib
+    from rltime_amd.models.torch.fused import dueling_tail
+    torch.manual_seed(rows + a)
+    fc, out, vh, vl = (nn.Linear(f, h1).cuda(), nn.Linear(h1, a).cuda(), nn.Linear(f, hv).cuda(), nn.Linear(hv, q).cuda())
+    mods = (fc, out, vh, vl)
+    x = torch.randn(rows, f, device="cuda")
+    ua, uv = torch.randn(rows, a, device="cuda"), torch.randn(rows, q, device="cuda")
+    res = []
+    for fused in (True, False):
+        for mod in mods:
+            mod.zero_grad(set_to_none=True)
+        xi = x.clone().requires_grad_(True)
+        if fused:
+            adv, val = dueling_tail(xi, fc, out, vh, vl)
+        else:
+            adv, val = out(F.relu(fc(xi))), vl(F.relu(vh(xi)))
+        loss = (adv * ua).sum() + (val * uv).sum()
+        if fused:
+            torch.cuda.synchronize()
+            _lib.check(_lib.lib.mirl_profile_reset())
+            _lib.check(_lib.lib.mirl_profile_set(2))
+            try:
+                loss.backward()
+                torch.cuda.synchronize()
+                ran = {r["name"]: r["calls"] for r in _lib.profile_table()}
+            finally:
+                _lib.check(_lib.lib.mirl_profile_set(0))
+        else:
+            loss.backward()
+        res.append([adv.detach(), val.detach(), xi.grad] + [p.grad.clone() for mod in mods for p in mod.parameters()])
+    if path == "torch":
+        assert "k_tail_bwd" not in ran, ran
+    else:
+        assert ran.get("k_tail_bwd") == 1 and ran.get("k_colsum_partials") == (2 if path == "w" else 1), ran
+    fc64, out64, vh64, vl64 = mods64 = [copy.deepcopy(mod).double() for mod in mods]
+    x64 = x.double().requires_grad_(True)
+    adv64, val64 = out64(F.relu(fc64(x64))), vl64(F.relu(vh64(x64)))
+    ((adv64 * ua.double()).sum() + (val64 * uv.double()).sum()).backward()
+    want = [adv64.detach(), val64.detach(), x64.grad] + [p.grad for mod in mods64 for p in mod.parameters()]
+    names = ["adv", "val", "dx", "fc.W", "fc.b", "out.W", "out.b", "vh.W", "vh.b", "vl.W", "vl.b"]
+    assert len(res[0]) == len(want) == len(names) == 11
+    for name, u, v, w in zip(names, res[0], res[1], want):
+        _close(u, v, name)
+        _close(u.double(), w, name + " (float64)")
+
+
 def test_iqn_policy_fused_head_equals_unfused_head():
     """IQNPolicy.predict with the fused tail (one GEMM for the last FC layer and
     the dueling value branch, single-pass quantile product) against the layer-by-
