@@ -1,0 +1,363 @@
+"""Float64 restatements of the pointwise arithmetic that decides what is learned, written from the reference's formulas
+(not from the kernels), for tests/test_pointwise_restate_cpu.py (which proves them against oracle/qmath.py, torch autograd,
+torch.optim.Adam and torch.nn.LSTMCell) and the GPU tests of csrc/qmath.hip, optim.hip, lstm.hip and k_actor_head:
+
+  value rescaling h / h^-1            rltime/training/torch/torch_trainer.py:46-78
+  n-step target tail                  torch_trainer.py:96-147: h(ret + float32(gamma)^n * h^-1(v) * mask)
+  double-Q selection (first maximum)  training/torch/dqn.py:52-71
+  IQN selection (argmax of the mean)  training/torch/iqn.py:36-52
+  Huber / MSE and their derivative    dqn.py:105-111
+  pairwise quantile-Huber loss        iqn.py:77-120 (the indicator td < 0 is detached: td == 0 has penalty tau and gradient
+                                      0, |td| == kappa is the quadratic branch)
+  clip_grad_norm_ + Adam              torch_trainer.py:177-199, coef = min(clip / (norm + 1e-6), 1), bias corrections from
+                                      each tensor's own step
+  LSTM cell with state reset          models/torch/modules/lstm.py:83-116
+  actor head                          policies/torch/dqn.py:74-87,140-141, policies/torch/iqn.py, exploration/
+                                      epsilon_greedy.py:74-100
+
+Every function computes in the dtype of its inputs (call it with float64 tensors).  The module also holds the dyadic
+operand generators: operands for which every sum a kernel can form is a float32 number, so that float32 arithmetic in any
+order equals float64 bit for bit, with the ties and kinks planted that a kernel must break the reference's way."""
+import math
+
+import numpy as np
+import torch
+
+
+# ---- value rescaling and the target tail ---------------------------------------------------------------------------------------
+def vf_scale(x, eps):
+    if not eps:
+        return x
+    return torch.sign(x) * (torch.sqrt(torch.abs(x) + 1) - 1) + eps * x
+
+
+def vf_unscale(y, eps, round32=False):
+    """The closed-form h^-1.  The reference evaluates it in float64 and returns float32: round32 repeats that rounding."""
+    if not eps:
+        return y
+    a = torch.abs(y)
+    x = a / eps - (1 / (2. * eps ** 2)) * torch.sqrt(4 * eps * a + (2. * eps + 1) ** 2) + (2. * eps + 1) / (2. * eps ** 2)
+    x = x * torch.sign(y)
+    return x.float().to(y.dtype) if round32 else x
+
+
+def gamma32(gamma):
+    """The base the reference's float32 tensor arithmetic raises to the n-th power."""
+    return float(np.float32(gamma))
+
+
+def nstep_target(v, returns, nsteps, masks, gamma, vf_eps, round32=False):
+    """v (M,) or (M, Nt); returns / nsteps / masks (M,)."""
+    if v.dim() == 2:
+        returns, nsteps, masks = (t.unsqueeze(-1) for t in (returns, nsteps, masks))
+    disc = torch.pow(torch.full_like(nsteps, gamma32(gamma)), nsteps)
+    return vf_scale(returns + disc * vf_unscale(v, vf_eps, round32) * masks, vf_eps)
+
+
+def first_max(q):
+    """Index of the first maximum along the last dimension (what torch.argmax documents), without argmax."""
+    A = q.shape[-1]
+    idx = torch.arange(A).expand(q.shape)
+    return torch.where(q == q.max(-1, keepdim=True).values, idx, torch.full_like(idx, A)).min(-1).values
+
+
+def dqn_bootstrap(q_target, q_select):
+    return q_target.gather(-1, first_max(q_select).unsqueeze(-1)).squeeze(-1)
+
+
+def iqn_select(z_select):
+    """(M, Ns, A) -> (M,) first maximum of the quantile mean."""
+    return first_max(z_select.sum(1) / z_select.shape[1])
+
+
+def iqn_bootstrap(z_target, z_select, best=None):
+    best = iqn_select(z_select) if best is None else best
+    return z_target[torch.arange(z_target.shape[0]), :, best]                 # (M, Nt)
+
+
+# ---- losses ------------------------------------------------------------------------------------------------------------------
+def huber(e, kappa):
+    """-> (value, derivative); |e| == kappa is the quadratic branch."""
+    a = e.abs()
+    quad = a <= kappa
+    return torch.where(quad, 0.5 * e * e, kappa * (a - 0.5 * kappa)), torch.where(quad, e, kappa * torch.sign(e))
+
+
+def mse(e):
+    return e * e, 2 * e
+
+
+def dqn_loss(q, actions, targets, weights=None, kappa=1.0, mode="huber", row_scale=1.0):
+    """-> (weighted row loss (M,), signed td (M,), dense d(row_scale * sum_m row_m) / dq (M, A))."""
+    M, A = q.shape
+    rows = torch.arange(M)
+    td = q[rows, actions] - targets
+    val, grad = mse(td) if mode == "mse" else huber(td, kappa)
+    w = torch.ones_like(td) if weights is None else weights
+    dq = torch.zeros_like(q)
+    dq[rows, actions] = grad * w * row_scale
+    return val * w, td, dq
+
+
+def iqn_pairs(z, taus, actions, targets, kappa=1.0):
+    """The pairwise sums of one transition: td[m, i, j] = y_i - theta_j, penalty |tau_j - 1{td < 0}|.
+    -> dict(td, loss_sum (M,) = sum_ij pen huber / kappa, abs_sum (M,) = sum_ij |td|,
+            gsum (M, N) = -sum_i pen huber' / kappa, the derivative of loss_sum in theta_j)."""
+    M, N, _ = z.shape
+    theta = z[torch.arange(M), :, actions]                                    # (M, N)
+    td = targets.unsqueeze(2) - theta.unsqueeze(1)                            # (M, Nt, N)
+    val, grad = huber(td, kappa)
+    pen = (taus.view(M, 1, N) - (td < 0).to(z.dtype)).abs()
+    return {"td": td, "loss_sum": (pen * val / kappa).sum((1, 2)), "abs_sum": td.abs().sum((1, 2)),
+            "gsum": -(pen * grad / kappa).sum(1), "loss_terms": pen * val / kappa, "g_terms": pen * grad / kappa}
+
+
+def iqn_loss(z, taus, actions, targets, weights=None, kappa=1.0, row_scale=1.0):
+    """-> (weighted row loss (M,), mean |td| (M,), dense d(row_scale * sum_m row_m) / dz (M, N, A))."""
+    M, N, _ = z.shape
+    Nt = targets.shape[1]
+    s = iqn_pairs(z, taus, actions, targets, kappa)
+    w = torch.ones_like(s["loss_sum"]) if weights is None else weights
+    dz = torch.zeros_like(z)
+    dz[torch.arange(M), :, actions] = s["gsum"] * (w * row_scale / Nt).unsqueeze(1)
+    return s["loss_sum"] / Nt * w, s["abs_sum"] / (Nt * N), dz
+
+
+# ---- clip + Adam -------------------------------------------------------------------------------------------------------------
+def global_norm(grads):
+    return math.sqrt(sum(float((g.double() ** 2).sum()) for g in grads))
+
+
+def clip_coef(norm, clip):
+    """clip_grad_norm_: min(clip / (norm + 1e-6), 1); clip 0 or None: no clipping."""
+    return min(clip / (norm + 1e-6), 1.0) if clip else 1.0
+
+
+def adam_step(p, g, m, v, step, lr, beta1, beta2, eps, coef=1.0):
+    """One Adam step (amsgrad off, no weight decay) of one tensor whose counter stands at `step` before it.
+    -> (p, clipped g, exp_avg, exp_avg_sq, step + 1)."""
+    t = step + 1
+    g = g * coef
+    m = beta1 * m + (1 - beta1) * g
+    v = beta2 * v + (1 - beta2) * g * g
+    bc1, bc2 = 1 - beta1 ** t, 1 - beta2 ** t
+    return p - (lr / bc1) * m / (v.sqrt() / math.sqrt(bc2) + eps), g, m, v, t
+
+
+# ---- LSTM cell ---------------------------------------------------------------------------------------------------------------
+def lstm_cell_fwd(pre, c_in, keep_next=None):
+    """pre (B, 4H) pre-activations in the order i, f, g, o -> (activated gates (B, 4H), h, c, h_next, c_next)."""
+    i, f, g, o = pre.chunk(4, dim=1)
+    i, f, g, o = torch.sigmoid(i), torch.sigmoid(f), torch.tanh(g), torch.sigmoid(o)
+    c = f * c_in + i * g
+    h = o * torch.tanh(c)
+    k = 1.0 if keep_next is None else keep_next.unsqueeze(1)
+    return torch.cat([i, f, g, o], 1), h, c, h * k, c * k
+
+
+def lstm_cell_bwd(gates, c_t, c_in, d_out=None, dh_rec=None, dc_rec=None, keep_next=None, first=False):
+    """gates: ACTIVATED (B, 4H).  d_out: gradient of the step's output h; dh_rec / dc_rec: gradients w.r.t. the next step's
+    masked inputs h * keep, c * keep (ignored when `first`, the sweep's first = the sequence's last step).
+    -> (d pre-activation (B, 4H), d c_in)."""
+    i, f, g, o = gates.chunk(4, dim=1)
+    k = 1.0 if keep_next is None else keep_next.unsqueeze(1)
+    zero = torch.zeros_like(c_t)
+    dh = (zero if d_out is None else d_out) + (zero if first else dh_rec * k)
+    tc = torch.tanh(c_t)
+    dc = (zero if first else dc_rec * k) + dh * o * (1 - tc * tc)
+    return torch.cat([dc * g * i * (1 - i), dc * c_in * f * (1 - f), dc * i * (1 - g * g), dh * tc * o * (1 - o)], 1), dc * f
+
+
+# ---- actor head --------------------------------------------------------------------------------------------------------------
+def actor_qvalues(adv, val=None):
+    """adv (E, N, A), val (E, N) or None -> (E, A): dueling combine V + A - mean_a A, then the mean over N."""
+    x = adv if val is None else val.unsqueeze(-1) + adv - adv.sum(-1, keepdim=True) / adv.shape[-1]
+    return x.sum(1) / x.shape[1]
+
+
+def eps_per_actor(eps, expo, eps_min, E):
+    """max(eps ** expo_e, eps_min) per actor in float64 (expo None: exponent 1)."""
+    ex = torch.ones(E, dtype=torch.float64) if expo is None else expo.double()
+    return torch.clamp(torch.pow(torch.full((E,), float(eps), dtype=torch.float64), ex), min=eps_min)
+
+
+def eps_greedy(greedy, eps_used32, u, rnd):
+    """Remap: the random action where u < float32(eps used)."""
+    return torch.where(u.float() < eps_used32.float(), rnd.to(greedy.dtype), greedy)
+
+
+# ---- dyadic operands ---------------------------------------------------------------------------------------------------------
+def _halves(g, lo, hi, *shape):
+    """Multiples of 1/2 in [lo, hi]."""
+    return torch.randint(int(2 * lo), int(2 * hi) + 1, shape, generator=g).double() / 2
+
+
+def exact_sum_margin(n_terms, max_term, granularity):
+    """max |partial sum| / granularity of any partial sum of n_terms multiples of `granularity` bounded by max_term: below
+    2^24 every such sum is a float32 number."""
+    return n_terms * max_term / granularity
+
+
+def dyadic_loss_iqn(seed, M, N, Nt, A, kappa, acted="lo", weights=True):
+    """theta, y: multiples of 1/2 in [-2, 2]; tau: multiples of 1/16 in [0, 1]; weights / row_scale: powers of two.
+    Planted: one pair with td == 0 and one with |td| == kappa (M * N * Nt >= 2).
+    Terms pen * huber / kappa are multiples of 2^-8 bounded by 4 (kappa in {0.5, 1, 2}), N * Nt <= 8192 of them."""
+    assert kappa in (0.5, 1.0, 2.0) and N * Nt <= 8192 and M * N * Nt >= 2
+    g = torch.Generator().manual_seed(seed)
+    z = _halves(g, -2, 2, M, N, A)
+    y = _halves(g, -2, 2, M, Nt)
+    taus = torch.randint(0, 17, (M, N), generator=g).double() / 16
+    actions = torch.full((M,), 0 if acted == "lo" else A - 1, dtype=torch.int64)
+    w = (2.0 ** torch.randint(-3, 3, (M,), generator=g).double()) if weights else None
+    a0, a1 = int(actions[0]), int(actions[M - 1])
+    if M == 1 and N == 1:                                    # one theta: plant through two targets (Nt >= 2)
+        th = float(z[0, 0, a0])
+        y[0, 0] = th
+        y[0, Nt - 1] = th + kappa if th + kappa <= 2 else th - kappa
+    else:
+        z[0, 0, a0] = y[0, 0]
+        yk = float(y[M - 1, Nt - 1])
+        z[M - 1, N - 1, a1] = yk - kappa if yk - kappa >= -2 else yk + kappa
+    return {"z": z, "taus": taus, "actions": actions, "targets": y, "weights": w, "kappa": kappa, "row_scale": 2.0 ** -(seed % 4),
+            "margin": exact_sum_margin(N * Nt, 4.0, 2.0 ** -8)}
+
+
+def dyadic_loss_dqn(seed, M, A, kappa, weights=True):
+    """q, y multiples of 1/2 in [-2, 2]; row 0 has td == 0, row M - 1 |td| == kappa when M >= 2 (M == 1: |td| == kappa)."""
+    g = torch.Generator().manual_seed(seed)
+    q, y = _halves(g, -2, 2, M, A), _halves(g, -2, 2, M)
+    actions = torch.randint(0, A, (M,), generator=g)
+    actions[0], actions[M - 1] = 0, A - 1
+    w = (2.0 ** torch.randint(-3, 3, (M,), generator=g).double()) if weights else None
+    if M >= 2:
+        q[0, 0] = y[0]
+    yk = float(y[M - 1])
+    q[M - 1, A - 1] = yk - kappa if yk - kappa >= -2 else yk + kappa
+    return {"q": q, "actions": actions, "targets": y, "weights": w, "kappa": kappa, "row_scale": 2.0 ** -(seed % 4)}
+
+
+def _tail(g, M):
+    """returns: multiples of 1/2, nsteps 1..5, masks 0 / 1 with both values present when M >= 2."""
+    ret, ns = _halves(g, -2, 2, M), torch.randint(1, 6, (M,), generator=g).double()
+    mk = torch.randint(0, 2, (M,), generator=g).double()
+    mk[0] = 1.0
+    if M >= 3:
+        mk[2] = 0.0
+    return ret, ns, mk
+
+
+def dyadic_target_dqn(seed, M, A):
+    """Row 0: the maximum of q_select tied between the first and the last action; row 1: between the last two actions."""
+    g = torch.Generator().manual_seed(seed)
+    qt, qs = _halves(g, -2, 2, M, A), _halves(g, -2, 1.5, M, A)
+    ret, ns, mk = _tail(g, M)
+    ties = 0
+    if A >= 2:
+        qs[0, 0] = qs[0, A - 1] = 2.0
+        qt[0, 0], qt[0, A - 1] = 1.0, -1.0
+        ties = 1
+        if M >= 2:
+            qs[1, A - 2] = qs[1, A - 1] = 2.0
+            qt[1, A - 2], qt[1, A - 1] = -1.5, 0.5
+            ties = 2
+    return {"qt": qt, "qs": qs, "returns": ret, "nsteps": ns, "masks": mk, "ties": ties}
+
+
+def dyadic_target_iqn(seed, M, Nt, Ns, A):
+    """z multiples of 1/2 in [-2, 2]: column sums over Ns <= 65 quantiles are multiples of 1/2 below 130.  Row 0: the largest
+    quantile MEAN tied between the first and the last action (different columns, equal sums when Ns >= 2); row 1 between the
+    last two."""
+    g = torch.Generator().manual_seed(seed)
+    zt, zs = _halves(g, -2, 2, M, Nt, A), _halves(g, -2, 1.0, M, Ns, A)
+    ret, ns, mk = _tail(g, M)
+    ties = 0
+    if A >= 2:
+        for row, (a, b) in enumerate([(0, A - 1), (A - 2, A - 1)][:min(M, 2)]):
+            zs[row, :, a] = 1.5
+            zs[row, :, b] = 1.5
+            if Ns >= 2:                                      # same sum, other summands
+                zs[row, 0, a], zs[row, 1, a] = 2.0, 1.0
+                zs[row, Ns - 1, b], zs[row, Ns - 2, b] = (2.0, 1.0) if Ns > 2 else (1.0, 2.0)
+            zt[row, :, a] = _halves(g, 0.5, 2, Nt)
+            zt[row, :, b] = -zt[row, :, a]
+            ties += 1
+    return {"zt": zt, "zs": zs, "returns": ret, "nsteps": ns, "masks": mk, "ties": ties,
+            "margin": exact_sum_margin(Ns, 2.0, 0.5)}
+
+
+def dyadic_actor_head(seed, E, N, A, dueling):
+    """adv, val multiples of 1/8 in [-4, 4], N and A powers of two: mean_a and mean_n are exact.  Every env has its maximum
+    planted on two actions (A >= 2), the first of them must win."""
+    assert N & (N - 1) == 0 and A & (A - 1) == 0
+    g = torch.Generator().manual_seed(seed)
+    adv = torch.randint(-32, 25, (E, N, A), generator=g).double() / 8          # <= 3
+    val = torch.randint(-32, 33, (E, N), generator=g).double() / 8 if dueling else None
+    first = torch.zeros(E, dtype=torch.int64)
+    if A >= 2:
+        for e in range(E):
+            a, b = sorted(torch.randperm(A, generator=g)[:2].tolist())
+            adv[e, :, a] = 3.5
+            adv[e, :, b] = 3.5
+            if N >= 2:
+                adv[e, 0, a], adv[e, 1, a] = 4.0, 3.0
+            first[e] = a
+    return {"adv": adv, "val": val, "first": first, "margin": exact_sum_margin(N, 12.0, 1.0 / (8 * A))}
+
+
+def dyadic_grads(seed, sizes, k=3, amp=7):
+    """Integers in [-amp, amp] times 2^-k: squares are multiples of 2^-2k, their sum over all tensors stays exact in float32
+    per lane and in float64 across lanes."""
+    g = torch.Generator().manual_seed(seed)
+    gs = [torch.randint(-amp, amp + 1, (n,), generator=g).double() * 2.0 ** -k for n in sizes]
+    return gs, exact_sum_margin(sum(sizes), (amp * 2.0 ** -k) ** 2, 2.0 ** (-2 * k))
+
+
+# ---- the cases of the bit-exact GPU tests (the CPU test proves the generators' claims on exactly these) ------------------------
+def loss_iqn_wave_cases():
+    """N x Nt over everything k_loss_iqn_wave takes; A, M, kappa, the acted action and the weights cycle through their values."""
+    out, k = [], 0
+    for N in (1, 2, 4, 8, 16, 32, 64):
+        for Nt in (1, 5, 31, 32, 33, 63, 64):
+            A, M = (1, 6, 18, 65)[k % 4], (1, 3, 5, 258)[(k // 4 + k) % 4]
+            if M * N * Nt < 2:
+                M = 3
+            out.append(dict(seed=100 + k, M=M, N=N, Nt=Nt, A=A, kappa=(0.5, 1.0, 2.0)[k % 3], acted=("lo", "hi")[(k // 3) % 2],
+                            weights=bool((k // 5) % 2)))
+            k += 1
+    return out
+
+
+def loss_iqn_generic_cases():
+    out = []
+    for k, (N, Nt) in enumerate([(3, 7), (24, 32), (48, 64), (65, 8), (70, 5), (128, 64), (32, 65), (8, 100)]):
+        out.append(dict(seed=200 + k, M=(1, 2, 3, 7)[k % 4], N=N, Nt=Nt, A=(6, 1, 18, 9)[(k // 2) % 4], kappa=(1.0, 0.5, 2.0)[k % 3],
+                        acted=("hi", "lo")[k % 2], weights=bool((k // 2) % 2)))
+        out.append(dict(seed=300 + k, M=(1, 2, 3, 7)[(k + 2) % 4], N=N, Nt=Nt, A=(6, 1, 18, 9)[(k // 2 + 1) % 4], kappa=(1.0, 0.5, 2.0)[(k + 1) % 3],
+                        acted=("hi", "lo")[(k + 1) % 2], weights=not bool((k // 2) % 2)))
+    return out
+
+
+def loss_dqn_cases():
+    return [dict(seed=400 + 16 * i + 4 * j + 2 * h + w, M=M, A=A, kappa=(0.5, 1.0, 2.0)[(i + j) % 3], mode=("huber", "mse")[h], weights=bool(w))
+            for i, A in enumerate((1, 2, 18)) for j, M in enumerate((1, 255, 256, 257)) for h in (0, 1) for w in (0, 1)]
+
+
+def target_iqn_cases():
+    """Ns, Nt and A each take all their values, M cycles; Ns * A + A <= 4096 (the LDS strip)."""
+    out, k = [], 0
+    for Ns in (1, 8, 63, 64, 65):
+        for j, Nt in enumerate((1, 32, 64, 65, 130)):
+            for A in ((1, 6, 64, 65, 100)[(k + j) % 5], (1, 6, 64, 65, 100)[(k + j + 2) % 5]):
+                if Ns * A + A <= 4096:
+                    out.append(dict(seed=500 + len(out), M=(1, 3, 6)[len(out) % 3], Nt=Nt, Ns=Ns, A=A))
+        k += 1
+    return out
+
+
+def target_dqn_cases():
+    return [dict(seed=600 + 4 * i + j, M=M, A=A) for i, A in enumerate((1, 2, 18)) for j, M in enumerate((1, 256, 257))]
+
+
+def actor_head_dyadic_cases():
+    return [dict(seed=700 + 8 * i + 2 * j + d, E=(1, 3, 4, 5, 33)[(i + j + d) % 5], N=N, A=A, dueling=bool(d))
+            for i, N in enumerate((1, 32, 64)) for j, A in enumerate((1, 8)) for d in (0, 1)]

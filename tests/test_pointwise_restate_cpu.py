@@ -1,0 +1,286 @@
+"""No GPU: tests/pointwise_restate.py is what it claims to be.  Targets and losses equal oracle/qmath.py run in float64,
+gradients equal float64 autograd of the plain expression, the Adam step equals clip_grad_norm_ + torch.optim.Adam, the cell
+equals torch.nn.LSTMCell with masked state and its autograd, the actor head equals the plain torch expression; and the
+dyadic operands of the bit-exact GPU tests keep every sum exact in float32 and hold the ties and kinks they promise."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import qmath
+from tests import pointwise_restate as R
+
+F64 = torch.float64
+
+
+def _g(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def _close(a, b, tol=1e-13):
+    assert a.shape == b.shape
+    assert float((a - b).abs().max()) <= tol * max(1.0, float(b.abs().max())), float((a - b).abs().max())
+
+
+# ---- targets -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("vf_eps", [None, 1e-3, 1e-2])
+@pytest.mark.parametrize("gamma", [0.97, 0.99])
+def test_targets_equal_the_oracle_in_float64(vf_eps, gamma):
+    g = _g(1)
+    M, N, Nt, A = 37, 8, 5, 6
+    ret, mk = torch.randn(M, generator=g, dtype=F64), torch.randint(0, 2, (M,), generator=g).double()
+    ns = torch.randint(1, 6, (M,), generator=g).double()
+    qt, qs = torch.randn(M, A, generator=g, dtype=F64) * 2, torch.randn(M, A, generator=g, dtype=F64) * 2
+    qs[0, 1] = qs[0, 4] = 9.0                                         # a tie: the first maximum
+    g32 = R.gamma32(gamma)
+    want = qmath.nstep_target(qmath.dqn_bootstrap(qt, qs), ret, mk, ns, g32, vf_eps)
+    got = R.nstep_target(R.dqn_bootstrap(qt, qs), ret, ns, mk, gamma, vf_eps, round32=True)
+    assert want.dtype == F64 and torch.equal(got, want)
+    assert int(R.first_max(qs)[0]) == 1
+    zt, zs = torch.randn(M, Nt, A, generator=g, dtype=F64) * 2, torch.randn(M, N, A, generator=g, dtype=F64) * 2
+    want = qmath.nstep_target(qmath.iqn_bootstrap(zt, zs), ret, mk, ns, g32, vf_eps)
+    got = R.nstep_target(R.iqn_bootstrap(zt, zs), ret, ns, mk, gamma, vf_eps, round32=True)
+    assert torch.equal(got, want)
+    # without the reference's float32 rounding of h^-1 the target moves by that rounding through h (slope <= 1/2 + eps)
+    full = R.nstep_target(R.iqn_bootstrap(zt, zs), ret, ns, mk, gamma, vf_eps)
+    v = R.vf_unscale(R.iqn_bootstrap(zt, zs), vf_eps)
+    assert bool(((full - got).abs() <= 2.0 ** -24 * v.abs() * (0.5 + (vf_eps or 0)) + 1e-15).all())
+    if vf_eps:                                                        # h^-1 inverts h
+        x = torch.randn(100, generator=g, dtype=F64) * 30
+        _close(R.vf_unscale(R.vf_scale(x, vf_eps), vf_eps), x, 1e-9)
+
+
+def test_first_max_is_argmax_with_ties():
+    q = torch.tensor([[1., 3., 3., 2.], [5., 5., 5., 5.], [0., -1., 0., 0.], [-2., -3., -1., -1.]], dtype=F64)
+    assert R.first_max(q).tolist() == [1, 0, 0, 2] == q.argmax(-1).tolist()
+
+
+# ---- losses ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["huber", "mse"])
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("kappa", [0.5, 1.0, 2.0])
+def test_dqn_loss_equals_the_oracle_and_autograd(mode, weighted, kappa):
+    g = _g(2)
+    M, A = 41, 5
+    q, y = torch.randn(M, A, generator=g, dtype=F64) * 2, torch.randn(M, generator=g, dtype=F64)
+    act = torch.randint(0, A, (M,), generator=g)
+    w = torch.rand(M, generator=g, dtype=F64) + 0.5 if weighted else None
+    q[0, act[0]], q[1, act[1]], q[2, act[2]] = y[0], y[1] + kappa, y[2] - kappa       # on the kinks
+    rs = 0.37
+    rows, td, dq = R.dqn_loss(q, act, y, w, kappa, mode, rs)
+    q1 = q.clone().requires_grad_(True)
+    loss, td_o = qmath.dqn_loss(q1, act, y, w, kappa, mode, 1, "sum", None)
+    assert torch.equal(td, td_o) and abs(float(rows.sum() - loss.detach())) <= 1e-12 * float(loss.detach().abs())
+    (loss * rs).backward()
+    _close(dq, q1.grad)
+    if mode == "huber":                                               # |td| == kappa is the quadratic branch, value and slope
+        assert float(rows[1]) == 0.5 * kappa * kappa * (float(w[1]) if weighted else 1.0) and float(rows[0]) == 0.0
+        assert float(dq[1, act[1]]) == kappa * (float(w[1]) if weighted else 1.0) * rs
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("kappa", [0.5, 1.0, 2.0])
+@pytest.mark.parametrize("N,Nt", [(8, 8), (5, 7), (70, 3)])
+def test_iqn_loss_equals_the_oracle_and_autograd(N, Nt, kappa, weighted):
+    g = _g(3)
+    M, A = 19, 4
+    z, y = torch.randn(M, N, A, generator=g, dtype=F64) * 2, torch.randn(M, Nt, generator=g, dtype=F64) * 2
+    taus = torch.rand(M, N, generator=g, dtype=F64)
+    act = torch.randint(0, A, (M,), generator=g)
+    w = torch.rand(M, generator=g, dtype=F64) + 0.5 if weighted else None
+    z[0, 0, act[0]] = y[0, 0]                                          # td == 0
+    z[1, 0, act[1]] = y[1, 0] - kappa                                  # td == +kappa
+    z[2, 0, act[2]] = y[2, 0] + kappa                                  # td == -kappa
+    rs = 1.7
+    rows, rep, dz = R.iqn_loss(z, taus, act, y, w, kappa, rs)
+    z1 = z.clone().requires_grad_(True)
+    loss, rep_o = qmath.iqn_loss(z1, taus.reshape(-1), act, y, w, kappa, 1, "sum", None)
+    _close(rep, rep_o)
+    assert abs(float(rows.sum() - loss.detach())) <= 1e-12 * float(loss.detach().abs())
+    (loss * rs).backward()
+    _close(dz, z1.grad)
+    # on the kinks: td == 0 has penalty tau and gradient 0, |td| == kappa the quadratic value kappa / 2 (per kappa)
+    s = R.iqn_pairs(z, taus, act, y, kappa)
+    assert float(s["td"][0, 0, 0]) == 0.0 and float(s["loss_terms"][0, 0, 0]) == 0.0 and float(s["g_terms"][0, 0, 0]) == 0.0
+    assert float(s["loss_terms"][1, 0, 0]) == float(taus[1, 0] * (0.5 * kappa * kappa) / kappa)
+    assert float(s["loss_terms"][2, 0, 0]) == float((taus[2, 0] - 1).abs() * (0.5 * kappa * kappa) / kappa)
+    assert float(s["g_terms"][1, 0, 0]) == float(taus[1, 0] * kappa / kappa)
+
+
+# ---- clip + Adam -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("clip", [None, 0.05, 40.0])
+def test_adam_step_equals_clip_grad_norm_and_torch_adam(clip):
+    g = _g(4)
+    sizes = [7, 130, 33]
+    lr, b1, b2, eps = 2.5e-4, 0.9, 0.999, 1.5e-4
+    ref = [torch.nn.Parameter(torch.randn(n, generator=g, dtype=F64)) for n in sizes]
+    opt = torch.optim.Adam(ref, lr=lr, betas=(b1, b2), eps=eps)
+    state = [[p.detach().clone(), torch.zeros(n, dtype=F64), torch.zeros(n, dtype=F64), 0] for p, n in zip(ref, sizes)]
+    for step in range(3):
+        grads = [torch.randn(n, generator=g, dtype=F64) * (0.3 if step % 2 else 0.01) for n in sizes]
+        live = [not (step == 1 and i == 1) for i in range(3)]                       # parameter 1 sits step 1 out
+        for p, gr, lv in zip(ref, grads, live):
+            p.grad = gr.clone() if lv else None
+        norm = R.global_norm([gr for gr, lv in zip(grads, live) if lv])
+        if clip is not None:
+            total = torch.nn.utils.clip_grad_norm_(ref, clip)
+            assert abs(float(total) - norm) <= 1e-13 * norm
+        opt.step()
+        coef = R.clip_coef(norm, clip)
+        for i, (st, gr, lv) in enumerate(zip(state, grads, live)):
+            if lv:
+                st[0], gc, st[1], st[2], st[3] = R.adam_step(st[0], gr, st[1], st[2], st[3], lr, b1, b2, eps, coef)
+                _close(gc, ref[i].grad)
+            _close(st[0], ref[i].detach(), 1e-12)
+            if opt.state[ref[i]]:
+                _close(st[1], opt.state[ref[i]]["exp_avg"])
+                _close(st[2], opt.state[ref[i]]["exp_avg_sq"])
+                assert float(opt.state[ref[i]]["step"]) == st[3]
+    assert [st[3] for st in state] == [3, 2, 3]
+    assert R.clip_coef(3.0, 0) == 1.0 and R.clip_coef(3.0, None) == 1.0
+
+
+# ---- LSTM cell ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("B,H", [(1, 1), (3, 5), (7, 37)])
+def test_cell_equals_torch_lstmcell_with_masked_state_and_its_autograd(B, H):
+    g = _g(5)
+    cell = torch.nn.LSTMCell(4 * H, H).double()
+    with torch.no_grad():                                             # gates = x: W_ih = I, W_hh = 0, no bias
+        cell.weight_ih.copy_(torch.eye(4 * H, dtype=F64))
+        cell.weight_hh.zero_(), cell.bias_ih.zero_(), cell.bias_hh.zero_()
+    pre = (torch.randn(B, 4 * H, generator=g, dtype=F64) * 2).requires_grad_(True)
+    c_prev = torch.randn(B, H, generator=g, dtype=F64)
+    keep, keep_next = (torch.rand(B, generator=g) > 0.4).double(), (torch.rand(B, generator=g) > 0.4).double()
+    keep_next[0] = 0.0
+    c_in = (c_prev * keep.unsqueeze(1)).requires_grad_(True)          # the masked state the step is given
+    h, c = cell(pre, (torch.zeros(B, H, dtype=F64), c_in))
+    gates, h_r, c_r, hn_r, cn_r = R.lstm_cell_fwd(pre.detach(), c_in.detach(), keep_next)
+    _close(h_r, h.detach()), _close(c_r, c.detach())
+    _close(hn_r, h.detach() * keep_next.unsqueeze(1)), _close(cn_r, c.detach() * keep_next.unsqueeze(1))
+    assert float(hn_r[0].abs().max()) == 0.0 and float(cn_r[0].abs().max()) == 0.0
+    d_out, dh_rec, dc_rec = (torch.randn(B, H, generator=g, dtype=F64) for _ in range(3))
+    loss = (d_out * h).sum() + (dh_rec * (h * keep_next.unsqueeze(1))).sum() + (dc_rec * (c * keep_next.unsqueeze(1))).sum()
+    loss.backward()
+    dpre, dcin = R.lstm_cell_bwd(gates, c_r, c_in.detach(), d_out, dh_rec, dc_rec, keep_next, first=False)
+    _close(dpre, pre.grad), _close(dcin, c_in.grad)
+    # first = 1 (nothing flows back from a later step), and no output gradient
+    pre.grad = c_in.grad = None
+    h, c = cell(pre, (torch.zeros(B, H, dtype=F64), c_in))
+    (d_out * h).sum().backward()
+    dpre, dcin = R.lstm_cell_bwd(gates, c_r, c_in.detach(), d_out, None, None, keep_next, first=True)
+    _close(dpre, pre.grad), _close(dcin, c_in.grad)
+    pre.grad = c_in.grad = None
+    h, c = cell(pre, (torch.zeros(B, H, dtype=F64), c_in))
+    ((dh_rec * h).sum() + (dc_rec * c).sum()).backward()
+    dpre, dcin = R.lstm_cell_bwd(gates, c_r, c_in.detach(), None, dh_rec, dc_rec, None, first=False)
+    _close(dpre, pre.grad), _close(dcin, c_in.grad)
+
+
+# ---- actor head --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dueling", [False, True])
+def test_actor_head_equals_the_plain_expression(dueling):
+    g = _g(6)
+    E, N, A = 9, 5, 7
+    adv = torch.randn(E, N, A, generator=g, dtype=F64)
+    val = torch.randn(E, N, generator=g, dtype=F64) if dueling else None
+    want = (val.unsqueeze(-1) + adv - adv.mean(-1, keepdim=True)).mean(1) if dueling else adv.mean(1)
+    got = R.actor_qvalues(adv, val)
+    _close(got, want)
+    got[0, 2] = got[0, 5] = 50.0
+    assert torch.equal(R.first_max(got), got.argmax(-1)) and int(R.first_max(got)[0]) == 2
+    expo = torch.linspace(1, 8, E, dtype=F64)
+    used = R.eps_per_actor(0.4, expo, 0.01, E)
+    assert torch.equal(used, torch.tensor([max(0.4 ** float(x), 0.01) for x in expo], dtype=F64))
+    assert float(used.min()) == 0.01 and float(used[0]) == 0.4
+    assert torch.equal(R.eps_per_actor(0.4, None, 0.01, E), torch.full((E,), 0.4, dtype=F64))
+    greedy, rnd = R.first_max(got), torch.randint(0, A, (E,), generator=g)
+    u = used.float().clone()                                          # u == eps: not below, keeps the greedy action
+    u[::2] = torch.nextafter(u[::2], torch.zeros(()))
+    act = R.eps_greedy(greedy, used.float(), u, rnd)
+    assert torch.equal(act[::2], rnd[::2]) and torch.equal(act[1::2], greedy[1::2])
+
+
+# ---- the dyadic operands of the bit-exact GPU tests --------------------------------------------------------------------------
+def _three_orders(terms, want64, seed):
+    """terms (rows, n) float64 dyadics: added one after the other in float32, in three shuffled orders, they give `want64`."""
+    t32 = terms.float().numpy()
+    assert np.array_equal(t32.astype(np.float64), terms.numpy())
+    rng = np.random.RandomState(seed)
+    for _ in range(3):
+        perm = rng.permutation(t32.shape[1])
+        got = np.cumsum(t32[:, perm], axis=1, dtype=np.float32)[:, -1]
+        assert got.dtype == np.float32 and np.array_equal(got.astype(np.float64), want64.numpy())
+
+
+@pytest.mark.parametrize("case", R.loss_iqn_wave_cases() + R.loss_iqn_generic_cases(), ids=lambda c: "N%d-Nt%d-A%d-M%d" % (c["N"], c["Nt"], c["A"], c["M"]))
+def test_dyadic_iqn_loss_operands(case):
+    d = R.dyadic_loss_iqn(**case)
+    assert d["margin"] < 2 ** 24
+    s = R.iqn_pairs(d["z"], d["taus"], d["actions"], d["targets"], d["kappa"])
+    M = case["M"]
+    assert float(s["loss_terms"].abs().max()) <= 4.0 and bool((s["loss_terms"] * 256 == (s["loss_terms"] * 256).round()).all())
+    _three_orders(s["loss_terms"].reshape(M, -1), s["loss_sum"], case["seed"])
+    _three_orders(s["td"].abs().reshape(M, -1), s["abs_sum"], case["seed"])
+    _three_orders(-s["g_terms"].permute(0, 2, 1).reshape(M * case["N"], -1), s["gsum"].reshape(-1), case["seed"])
+    assert bool((s["td"] == 0).any()) and bool((s["td"].abs() == d["kappa"]).any())
+    for t in (d["z"], d["targets"]):
+        assert float(t.abs().max()) <= 2.0 and bool((t * 2 == (t * 2).round()).all())
+    assert bool((d["taus"] * 16 == (d["taus"] * 16).round()).all())
+    assert d["weights"] is None or bool((torch.log2(d["weights"]) == torch.log2(d["weights"]).round()).all())
+
+
+@pytest.mark.parametrize("case", R.loss_dqn_cases(), ids=lambda c: "A%d-M%d-%s-w%d" % (c["A"], c["M"], c["mode"], c["weights"]))
+def test_dyadic_dqn_loss_operands(case):
+    d = R.dyadic_loss_dqn(case["seed"], case["M"], case["A"], case["kappa"], case["weights"])
+    td = d["q"][torch.arange(case["M"]), d["actions"]] - d["targets"]
+    assert bool((td.abs() == d["kappa"]).any()) and (case["M"] == 1 or bool((td == 0).any()))
+    assert (case["M"] == 1 or int(d["actions"][0]) == 0) and int(d["actions"][-1]) == case["A"] - 1
+
+
+@pytest.mark.parametrize("case", R.target_iqn_cases(), ids=lambda c: "Ns%d-Nt%d-A%d-M%d" % (c["Ns"], c["Nt"], c["A"], c["M"]))
+def test_dyadic_iqn_target_operands(case):
+    d = R.dyadic_target_iqn(**case)
+    assert d["margin"] < 2 ** 24 and case["Ns"] * case["A"] + case["A"] <= 4096
+    M, Ns, A = case["M"], case["Ns"], case["A"]
+    sums = d["zs"].sum(1)
+    _three_orders(d["zs"].permute(0, 2, 1).reshape(M * A, Ns), sums.reshape(-1), case["seed"])
+    top = sums.max(-1, keepdim=True).values
+    tied = ((sums == top).sum(-1) >= 2)
+    assert int(tied[:2].sum()) == d["ties"] == (0 if A == 1 else min(M, 2))
+    best = R.iqn_select(d["zs"])
+    if A >= 2:
+        assert int(best[0]) == 0 and (M < 2 or int(best[1]) == A - 2)
+        # the tied actions carry different targets: taking the other one shows
+        assert not torch.equal(d["zt"][0, :, 0], d["zt"][0, :, A - 1])
+
+
+@pytest.mark.parametrize("case", R.target_dqn_cases(), ids=lambda c: "A%d-M%d" % (c["A"], c["M"]))
+def test_dyadic_dqn_target_operands(case):
+    d = R.dyadic_target_dqn(**case)
+    A, M = case["A"], case["M"]
+    tied = (d["qs"] == d["qs"].max(-1, keepdim=True).values).sum(-1) >= 2
+    assert int(tied[:2].sum()) == d["ties"] == (0 if A == 1 else min(M, 2))
+    if A >= 2:
+        assert int(R.first_max(d["qs"])[0]) == 0 and float(d["qt"][0, 0]) != float(d["qt"][0, A - 1])
+        assert M < 2 or (int(R.first_max(d["qs"])[1]) == A - 2 and float(d["qt"][1, A - 2]) != float(d["qt"][1, A - 1]))
+
+
+@pytest.mark.parametrize("case", R.actor_head_dyadic_cases(), ids=lambda c: "E%d-N%d-A%d-d%d" % (c["E"], c["N"], c["A"], c["dueling"]))
+def test_dyadic_actor_head_operands(case):
+    d = R.dyadic_actor_head(**case)
+    assert d["margin"] < 2 ** 24
+    E, N, A = case["E"], case["N"], case["A"]
+    adv, val = d["adv"], d["val"]
+    x = adv if val is None else val.unsqueeze(-1) + adv - adv.sum(-1, keepdim=True) / A
+    q = R.actor_qvalues(adv, val)
+    _three_orders(x.permute(0, 2, 1).reshape(E * A, N), (q * N).reshape(-1), case["seed"])
+    assert torch.equal(q.float().double(), q)
+    if A >= 2:
+        assert bool(((q == q.max(-1, keepdim=True).values).sum(-1) == 2).all()) and torch.equal(R.first_max(q), d["first"])
+
+
+def test_dyadic_gradients_have_an_exact_sum_of_squares():
+    sizes = [1, 255, 4095, 4096, 4097, 8192, 12289] * 9 + [7, 33]
+    gs, margin = R.dyadic_grads(9, sizes)
+    assert margin < 2 ** 24
+    sq = torch.cat(gs) ** 2
+    _three_orders(sq.reshape(1, -1), sq.sum().reshape(1), 9)
