@@ -659,17 +659,24 @@ extern "C" int mirl_act_lstm_supported(int32_t E, int32_t H, int32_t K) {
   return E > 0 && E <= 64 && H > 0 && (H % 8) == 0 && K > 0 && (K % 16) == 0;
 }
 
-// K slices per column block: (H / 8) x KB workgroups ~ one per CU
-static int act_lstm_kb(int H, int K) {
+// K slices per column block: (H / 8) x KB workgroups ~ one per CU; *spb = 16-wide K steps per slice.  KB is then cut back to the
+// slices that hold a step, (KB - 1) SPB < steps <= KB SPB: a slice that starts at or past `steps` would redirect its loads to its
+// own first step, 16 floats past column K of every row (H = 64, K = 1296: steps = 81, 10 slices of 9 — the tenth starts at 81),
+// and feed what it finds there to the MFMAs against zeroed weights: NaN where that memory holds NaN or Inf.
+static int act_lstm_kb(int H, int K, int* spb) {
   int kb = 256 / (H / 8);
   if (kb > 16) kb = 16;
   if (kb > K / 16 / 8) kb = K / 16 / 8;
-  return kb < 1 ? 1 : kb;
+  if (kb < 1) kb = 1;
+  const int steps = K / 16;
+  *spb = (steps + kb - 1) / kb;
+  return (steps + *spb - 1) / *spb;
 }
 
 extern "C" int mirl_act_lstm_workspace_bytes(int32_t E, int32_t H, int32_t K, int64_t* bytes) {
   if (!bytes || !mirl_act_lstm_supported(E, H, K)) return fail(MIRL_ERR_ARG, "bad act_lstm_workspace_bytes arguments");
-  const int kb = act_lstm_kb(H, K);
+  int spb = 0;
+  const int kb = act_lstm_kb(H, K, &spb);
   *bytes = (int64_t)sizeof(float) * kb * (H / 8) * E * 32 + (int64_t)sizeof(unsigned) * (H / 8) + 256;
   return MIRL_OK;
 }
@@ -682,8 +689,7 @@ extern "C" int mirl_act_lstm_fwd(int32_t E, int32_t H, int32_t K, const float* x
   ActLstmArgs a;
   a.xh = xh; a.xh_pitch = xh_pitch; a.w = w; a.bias = bias; a.c_in = c_in; a.h_out = h_out; a.c_out = c_out;
   a.E = E; a.H = H; a.K = K;
-  a.KB = act_lstm_kb(H, K);
-  a.SPB = (K / 16 + a.KB - 1) / a.KB;
+  a.KB = act_lstm_kb(H, K, &a.SPB);
   a.arrived = (unsigned*)workspace;                          // zero on first use (the caller allocates zeroed memory)
   a.shares = (float*)((char*)workspace + ((sizeof(unsigned) * (H / 8) + 255) / 256) * 256);
   hipStream_t st = (hipStream_t)stream;

@@ -14,6 +14,8 @@ torch.optim.Adam and torch.nn.LSTMCell) and the GPU tests of csrc/qmath.hip, opt
   LSTM cell with state reset          models/torch/modules/lstm.py:83-116
   actor head                          policies/torch/dqn.py:74-87,140-141, policies/torch/iqn.py, exploration/
                                       epsilon_greedy.py:74-100
+  conv + ReLU, linear layers          models/torch/modules/cnn.py:43-50, dqn.py:50-66 (for csrc/actnet.hip)
+  quantile embedding product          policies/torch/iqn.py:67-106: relu(cos(pi i tau) W^T + b) * features
 
 Every function computes in the dtype of its inputs (call it with float64 tensors).  The module also holds the dyadic
 operand generators: operands for which every sum a kernel can form is a float32 number, so that float32 arithmetic in any
@@ -186,7 +188,142 @@ def eps_greedy(greedy, eps_used32, u, rnd):
     return torch.where(u.float() < eps_used32.float(), rnd.to(greedy.dtype), greedy)
 
 
+# ---- the acting network's layers -----------------------------------------------------------------------------------------------
+def conv_patches_nhwc(x, k, s):
+    """x (F, Hi, Wi, C) -> (F, Ho, Wo, k * k * C): the input pixels under every output pixel, tap-major, channel fastest."""
+    F_, Hi, Wi, _ = x.shape
+    Ho, Wo = (Hi - k) // s + 1, (Wi - k) // s + 1
+    taps = [x[:, ky:ky + s * (Ho - 1) + 1:s, kx:kx + s * (Wo - 1) + 1:s, :] for ky in range(k) for kx in range(k)]
+    return torch.cat(taps, dim=-1)
+
+
+def conv_relu_nhwc(x, w, b, k, s, pre=False):
+    """Conv2d (no padding) + ReLU over channels-last frames: x (F, Hi, Wi, C), w (Co, C, k, k), b (Co,) -> (F, Ho, Wo, Co);
+    y[f, oy, ox, o] = relu(b[o] + sum_{ky, kx, c} x[f, oy s + ky, ox s + kx, c] w[o, c, ky, kx]).  pre: without the ReLU."""
+    w_taps = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+    y = conv_patches_nhwc(x, k, s) @ w_taps.t() + b
+    return y if pre else torch.clamp(y, min=0)
+
+
+def linear(x, w, b=None):
+    y = x @ w.t()
+    return y if b is None else y + b
+
+
+def cos_embed_pre(taus, freq, wq, bq):
+    """taus (R,), freq (D,) -> (phi (R, D) = cos(freq tau), phi wq^T + bq (R, H))."""
+    phi = torch.cos(freq.unsqueeze(0) * taus.unsqueeze(1))
+    return phi, linear(phi, wq, bq)
+
+
+def cos_embed_product(taus, freq, wq, bq, h, N):
+    """x[m] = relu(cos(freq tau_m) wq^T + bq) * h[m // N]."""
+    return torch.clamp(cos_embed_pre(taus, freq, wq, bq)[1], min=0) * h.repeat_interleave(N, dim=0)
+
+
+def head_shares(x, wfc, bfc, wout):
+    """hid = relu(x wfc^T + bfc) (R, HID); share cb of the output layer = hid[:, 64 cb : 64 cb + 64] wout[:, the same]^T.
+    -> (hid, shares (ceil(HID / 64), R, NO))."""
+    hid = torch.clamp(linear(x, wfc, bfc), min=0)
+    HID = hid.shape[1]
+    return hid, torch.stack([hid[:, c:c + 64] @ wout[:, c:c + 64].t() for c in range(0, HID, 64)])
+
+
+def philox_4x32(seed, call, lane):
+    """Philox4x32-10 (Salmon et al., SC'11), key (seed lo, seed hi), counter (lane, call lo, call hi, tag) -> four 32-bit
+    words: the acting heads draw u = (word 0 >> 8) / 2^24 and the random action (word 1 * A) >> 32 per env."""
+    M0, M1, MASK = 0xD2511F53, 0xCD9E8D57, 0xFFFFFFFF
+    c = [lane & MASK, call & MASK, (call >> 32) & MASK, 0x52544D45]
+    k0, k1 = seed & MASK, (seed >> 32) & MASK
+    for _ in range(10):
+        p0, p1 = M0 * c[0], M1 * c[2]
+        c = [((p1 >> 32) ^ c[1] ^ k0) & MASK, p1 & MASK, ((p0 >> 32) ^ c[3] ^ k1) & MASK, p0 & MASK]
+        k0, k1 = (k0 + 0x9E3779B9) & MASK, (k1 + 0xBB67AE85) & MASK
+    return c
+
+
+def philox_head_draws(seed, step, E, A):
+    """-> (u (E,) float32, random action (E,) int64) of one (seed, step)."""
+    w = [philox_4x32(seed, step, e) for e in range(E)]
+    u = torch.tensor([(x[0] >> 8) / 16777216.0 for x in w], dtype=torch.float64).float()
+    return u, torch.tensor([(x[1] * A) >> 32 for x in w], dtype=torch.int64)
+
+
 # ---- dyadic operands ---------------------------------------------------------------------------------------------------------
+def _ints(g, lo, hi, *shape):
+    return torch.randint(int(lo), int(hi) + 1, shape, generator=g).double()
+
+
+def dyadic_conv(seed, layer, frames, Hi, Wi):
+    """Layer 2 (32 -> 64 channels, 4x4, stride 2) or 3 (64 -> 64, 3x3, stride 1) of the acting network.  x in {-1, 0, 1} / 2 (half
+    of them 0), w in {-2 .. 2} / 4: products are multiples of 1/8 bounded by 1/2, K = 512 / 576 of them per output.  The bias is
+    planted per channel: minus the most frequent value of the channel's sums (even channels: that many pre-activations are
+    exactly 0) and one eighth less (odd channels: the same pixels come out at -1/8)."""
+    ci, k, s = (32, 4, 2) if layer == 2 else (64, 3, 1)
+    g = torch.Generator().manual_seed(seed)
+    x = _ints(g, -1, 1, frames, Hi, Wi, ci) * _ints(g, 0, 1, frames, Hi, Wi, ci) / 2
+    w = _ints(g, -2, 2, 64, ci, k, k) / 4
+    sums = conv_relu_nhwc(x, w, torch.zeros(64, dtype=torch.float64), k, s, pre=True).reshape(-1, 64)
+    b = -sums.mode(dim=0).values
+    b[1::2] -= 0.125
+    return {"x": x, "w": w, "b": b, "k": k, "s": s, "margin": exact_sum_margin(k * k * ci, 0.5, 0.125) + float(b.abs().max()) * 8}
+
+
+def dyadic_lstm(seed, E, H, K):
+    """xh in {-1, 0, 1} / 2, w in {-2 .. 2} / 16, bias multiples of 1/32 in [-1, 1]: products are multiples of 1/32 bounded by
+    1/16, K of them per gate: the pre-activations are exact whatever the slices, waves and shares add first.  c_in is real."""
+    g = torch.Generator().manual_seed(seed)
+    xh, w = _ints(g, -1, 1, E, K) / 2, _ints(g, -2, 2, 4 * H, K) / 16
+    b = _ints(g, -32, 32, 4 * H) / 32
+    c_in = torch.randn(E, H, generator=g).double()
+    return {"xh": xh, "w": w, "b": b, "c_in": c_in, "margin": exact_sum_margin(K, 1.0 / 16, 1.0 / 32) + 32}
+
+
+def dyadic_hidden(seed, R, H, HID, NO):
+    """x in {-1, 0, 1} / 2, wfc in {-2 .. 2} / 4, bfc multiples of 1/8 in [-2, 2]: hid is a multiple of 1/8 bounded by H / 2 + 2;
+    wout in {-2 .. 2} / 2: a share adds 64 multiples of 1/16 bounded by H / 2 + 2, all shares HID of them."""
+    g = torch.Generator().manual_seed(seed)
+    x, wfc = _ints(g, -1, 1, R, H) / 2, _ints(g, -2, 2, HID, H) / 4
+    bfc, wout = _ints(g, -16, 16, HID) / 8, _ints(g, -2, 2, NO, HID) / 2
+    return {"x": x, "wfc": wfc, "bfc": bfc, "wout": wout,
+            "margin": max(exact_sum_margin(H, 0.5, 0.125) + 16, exact_sum_margin(HID, H / 2 + 2, 1.0 / 16))}
+
+
+def dyadic_head_parts(seed, E, N, A, P, has_val):
+    """Output shares for the selection: adv, val multiples of 1/8 as in dyadic_actor_head, any N and A.  Where A is no power of
+    two every row's advantages are made to add up to a multiple of A / 8 (one untied action takes up the remainder), so that
+    mean_a A is a multiple of 1/8; the quantile mean is ONE division of an exact sum, correctly rounded in float32 and equal to the
+    rounded float64 quotient (53 >= 2 * 24 + 2 bits).  Every env has its best q-value planted on two actions (A >= 2), the first
+    must win.  out = bout + P shares: bout multiples of 1/8, shares multiples of 1/8.
+    -> dict(adv (E, N, A), val (E, N) or None, first (E,), parts (P, E * N, NO), bout (NO,))."""
+    g = torch.Generator().manual_seed(seed)
+    adv = _ints(g, -32, 24, E, N, A) / 8
+    val = _ints(g, -32, 32, E, N) / 8 if has_val else None
+    first = torch.zeros(E, dtype=torch.int64)
+    fix = has_val and A & (A - 1) != 0
+    if A >= 2:
+        for e in range(E):
+            a, b, c = torch.randperm(A, generator=g)[:3].tolist() if A >= 3 else (0, 1, 0)
+            a, b = min(a, b), max(a, b)
+            adv[e, :, a] = 3.5
+            adv[e, :, b] = 3.5
+            if N >= 2:
+                adv[e, 0, a], adv[e, 1, a] = 4.0, 3.0
+            if fix:
+                adv[e, :, c] = -2.0
+                rem = torch.remainder(adv[e].sum(-1) * 8, A)
+                adv[e, :, c] -= rem / 8
+            first[e] = a
+    NO = A + (1 if has_val else 0)
+    out = adv.reshape(E * N, A) if val is None else torch.cat([adv.reshape(E * N, A), val.reshape(E * N, 1)], 1)
+    bout = _ints(g, -16, 16, NO) / 8
+    parts = _ints(g, -64, 64, P, E * N, NO) / 8
+    parts[P - 1] = out - bout - parts[:P - 1].sum(0)
+    return {"adv": adv, "val": val, "first": first, "parts": parts, "bout": bout,
+            "margin": max(exact_sum_margin(N, 16.0, 1.0 / 8), exact_sum_margin(A, 6.0, 1.0 / 8),
+                          exact_sum_margin(P + 1, float(parts.abs().max()), 1.0 / 8))}
+
+
 def _halves(g, lo, hi, *shape):
     """Multiples of 1/2 in [lo, hi]."""
     return torch.randint(int(2 * lo), int(2 * hi) + 1, shape, generator=g).double() / 2

@@ -1,7 +1,8 @@
 """No GPU: tests/pointwise_restate.py is what it claims to be.  Targets and losses equal oracle/qmath.py run in float64,
 gradients equal float64 autograd of the plain expression, the Adam step equals clip_grad_norm_ + torch.optim.Adam, the cell
-equals torch.nn.LSTMCell with masked state and its autograd, the actor head equals the plain torch expression; and the
-dyadic operands of the bit-exact GPU tests keep every sum exact in float32 and hold the ties and kinks they promise."""
+equals torch.nn.LSTMCell with masked state and its autograd, the actor head equals the plain torch expression, the acting
+network's layers (conv + ReLU over channels-last frames, linear, quantile-embedding product, output shares) equal torch's in
+float64; and the dyadic operands of the bit-exact GPU tests keep every sum exact in float32 and hold the ties and kinks they promise."""
 import numpy as np
 import pytest
 import torch
@@ -199,6 +200,51 @@ def test_actor_head_equals_the_plain_expression(dueling):
     assert torch.equal(act[::2], rnd[::2]) and torch.equal(act[1::2], greedy[1::2])
 
 
+# ---- the acting network's layers -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("layer,frames,Hi,Wi", [(2, 3, 6, 12), (2, 2, 12, 6), (2, 1, 4, 4), (3, 3, 5, 9), (3, 2, 9, 5), (3, 1, 3, 3)])
+def test_conv_relu_nhwc_equals_torch_conv2d(layer, frames, Hi, Wi):
+    g = _g(7)
+    ci, k, s = (32, 4, 2) if layer == 2 else (64, 3, 1)
+    x = torch.randn(frames, ci, Hi, Wi, generator=g, dtype=F64)
+    w, b = torch.randn(64, ci, k, k, generator=g, dtype=F64) * 0.05, torch.randn(64, generator=g, dtype=F64)
+    want = torch.nn.functional.conv2d(x, w, b, stride=s).permute(0, 2, 3, 1)
+    got = R.conv_relu_nhwc(x.permute(0, 2, 3, 1), w, b, k, s, pre=True)
+    _close(got, want)
+    _close(R.conv_relu_nhwc(x.permute(0, 2, 3, 1), w, b, k, s), torch.relu(want))
+    assert bool((want < 0).any()) and got.shape == (frames, (Hi - k) // s + 1, (Wi - k) // s + 1, 64)
+
+
+def test_linear_embedding_product_and_output_shares_equal_torch():
+    g = _g(8)
+    E, N, H, D, HID, NO = 3, 5, 48, 32, 144, 7
+    h, taus = torch.randn(E, H, generator=g, dtype=F64), torch.rand(E * N, generator=g, dtype=F64)
+    freq = torch.arange(1, D + 1, dtype=F64) * np.pi
+    wq, bq = torch.randn(H, D, generator=g, dtype=F64), torch.randn(H, generator=g, dtype=F64)
+    Fn = torch.nn.functional
+    _close(R.linear(h, wq.t().contiguous()[:, :H]), Fn.linear(h, wq.t().contiguous()[:, :H]))
+    _close(R.linear(taus.view(-1, 1) * freq, wq, bq), Fn.linear(taus.view(-1, 1) * freq, wq, bq))
+    phi = torch.cos(taus.unsqueeze(1) * freq.unsqueeze(0))
+    want = torch.relu(Fn.linear(phi, wq, bq)) * h.repeat_interleave(N, dim=0)
+    _close(R.cos_embed_product(taus, freq, wq, bq, h, N), want)
+    assert torch.equal(R.cos_embed_pre(taus, freq, wq, bq)[0], phi)
+    wfc, bfc = torch.randn(HID, H, generator=g, dtype=F64), torch.randn(HID, generator=g, dtype=F64)
+    wout = torch.randn(NO, HID, generator=g, dtype=F64)
+    hid, shares = R.head_shares(want, wfc, bfc, wout)
+    _close(hid, torch.relu(Fn.linear(want, wfc, bfc)))
+    assert shares.shape == (3, E * N, NO)                             # 64 + 64 + 16 columns
+    _close(shares.sum(0), Fn.linear(hid, wout), 1e-12)
+    _close(shares[2], Fn.linear(hid[:, 128:], wout[:, 128:]))
+
+
+def test_philox_words_are_the_replay_test_generator():
+    from tests.test_replay_gpu import _philox_u53
+    for seed, call, lane in [(0, 0, 0), (99, 5, 3), (0xFFFFFFFF12345678, 1 << 40, 77)]:
+        c = R.philox_4x32(seed, call, lane)
+        assert ((c[0] >> 5) * 67108864.0 + (c[1] >> 6)) / 9007199254740992.0 == _philox_u53(seed, call, lane)
+    u, rnd = R.philox_head_draws(77, 5, 9, 6)
+    assert float(u.min()) >= 0 and float(u.max()) < 1 and int(rnd.min()) >= 0 and int(rnd.max()) < 6 and len(set(u.tolist())) == 9
+
+
 # ---- the dyadic operands of the bit-exact GPU tests --------------------------------------------------------------------------
 def _three_orders(terms, want64, seed):
     """terms (rows, n) float64 dyadics: added one after the other in float32, in three shuffled orders, they give `want64`."""
@@ -284,3 +330,59 @@ def test_dyadic_gradients_have_an_exact_sum_of_squares():
     assert margin < 2 ** 24
     sq = torch.cat(gs) ** 2
     _three_orders(sq.reshape(1, -1), sq.sum().reshape(1), 9)
+
+
+@pytest.mark.parametrize("layer,frames,Hi,Wi", [(2, 1, 4, 4), (2, 3, 12, 6), (2, 20, 20, 20), (3, 1, 3, 3), (3, 3, 5, 9), (3, 30, 9, 9)])
+def test_dyadic_conv_operands(layer, frames, Hi, Wi):
+    d = R.dyadic_conv(900 + frames, layer, frames, Hi, Wi)
+    assert d["margin"] < 2 ** 24
+    patches = R.conv_patches_nhwc(d["x"], d["k"], d["s"]).reshape(-1, d["k"] ** 2 * d["x"].shape[-1])
+    w_taps = d["w"].permute(0, 2, 3, 1).reshape(64, -1)
+    pre = R.conv_relu_nhwc(d["x"], d["w"], d["b"], d["k"], d["s"], pre=True).reshape(-1, 64)
+    for co in (0, 1, 63):                                             # products and bias in three orders: the float64 sum
+        terms = torch.cat([patches * w_taps[co], d["b"][co].expand(patches.shape[0], 1)], 1)
+        _three_orders(terms, pre[:, co], 900 + co)
+    assert bool((pre[:, 0::2] == 0).any(0).all()) and bool((pre[:, 1::2] == -0.125).any(0).all())
+    assert pre.shape[0] < 64 or int((pre == 0).sum()) >= pre.numel() // 200
+
+
+@pytest.mark.parametrize("E,H,K", [(1, 8, 1296), (20, 64, 1424), (7, 64, 112)])
+def test_dyadic_lstm_operands(E, H, K):
+    d = R.dyadic_lstm(910 + E, E, H, K)
+    assert d["margin"] < 2 ** 24 and torch.equal(d["c_in"].float().double(), d["c_in"])
+    pre = R.linear(d["xh"], d["w"], d["b"])
+    for j in (0, 4 * H - 1):
+        _three_orders(torch.cat([d["xh"] * d["w"][j], d["b"][j].expand(E, 1)], 1), pre[:, j], 910 + j)
+    assert 0.5 < float(pre.std()) < 4.0                               # the gates are not saturated
+
+
+@pytest.mark.parametrize("Rr,H,HID,NO", [(33, 128, 80, 7), (70, 1024, 64, 31), (40, 64, 1024, 7)])
+def test_dyadic_hidden_operands(Rr, H, HID, NO):
+    d = R.dyadic_hidden(920 + Rr, Rr, H, HID, NO)
+    assert d["margin"] < 2 ** 24
+    hid, shares = R.head_shares(d["x"], d["wfc"], d["bfc"], d["wout"])
+    _three_orders(torch.cat([d["x"] * d["wfc"][0], d["bfc"][0].expand(Rr, 1)], 1), R.linear(d["x"], d["wfc"], d["bfc"])[:, 0], 920)
+    _three_orders(hid * d["wout"][NO - 1], shares.sum(0)[:, NO - 1], 921)
+    assert torch.equal(shares.float().double(), shares) and float(hid.abs().max()) <= H / 2 + 2
+
+
+@pytest.mark.parametrize("E,N,A,has_val", [(1, 1, 1, 0), (5, 7, 8, 1), (3, 70, 12, 0), (6, 130, 18, 1), (4, 64, 31, 1), (9, 32, 6, 1), (3, 5, 2, 1)])
+def test_dyadic_head_parts_operands(E, N, A, has_val):
+    d = R.dyadic_head_parts(930 + E, E, N, A, 3, bool(has_val))
+    assert d["margin"] < 2 ** 24
+    adv, val = d["adv"], d["val"]
+    out = d["parts"].sum(0) + d["bout"]
+    assert torch.equal(out[:, :A].reshape(E, N, A), adv) and (val is None or torch.equal(out[:, A].reshape(E, N), val))
+    _three_orders(torch.cat([d["parts"].permute(1, 2, 0).reshape(-1, 3), d["bout"].repeat(E * N).unsqueeze(1)], 1), out.reshape(-1), 930)
+    mean = adv.sum(-1) / A
+    unit = 8 * A if A & (A - 1) == 0 else 8                               # mean_a A: a multiple of 1 / (8 A) at a power of two, else of 1/8
+    assert val is None or bool((mean * unit == (mean * unit).round()).all())
+    x = adv if val is None else val.unsqueeze(-1) + adv - mean.unsqueeze(-1)
+    q = R.actor_qvalues(adv, val)
+    _three_orders(x.permute(0, 2, 1).reshape(E * A, N), x.sum(1).reshape(-1), 931)
+    # the one division: float32(sum) / float32(N) correctly rounded is the rounded float64 quotient
+    s32 = x.sum(1).reshape(-1).numpy().astype(np.float32)
+    assert np.array_equal(s32 / np.float32(N), q.reshape(-1).float().numpy())
+    if A >= 2:
+        assert bool(((q == q.max(-1, keepdim=True).values).sum(-1) == 2).all()) and torch.equal(R.first_max(q), d["first"])
+        assert torch.equal(R.first_max(q.float()), d["first"])
