@@ -185,8 +185,7 @@ int mirl_replay_prime_stack(mirl_replay* h, const uint8_t* newest_planes, int64_
 
 /* mirl_replay_ingest issues ONE fused kernel per call (frame / state / q-value rows, scalars,
  * plan, tree fix) unless the shard de-duplicates frame stacks or initialises priorities at
- * acting time; 0 selects the separate kernels of rounds 1-2 for every shard (A/B tests; the
- * environment variable MIRL_INGEST_FUSED=0 does the same).                                  */
+ * acting time; 0 selects the separate kernels of rounds 1-2 for every shard (A/B tests).   */
 int mirl_ingest_fused_set(int32_t on);
 
 /* needed_feed_count (replay_history.py:62-75).  *out = -1 for None.           */
@@ -469,8 +468,8 @@ int mirl_conv1_u8_wpk_floats(int64_t* out);
  * MIRL_CONV1_BF16 environment default.  For in-process A/B runs (tests/test_network_ab_gpu.py).              */
 int mirl_conv1_bf16_set(int32_t mode);
 /* Same switch for the layer's WEIGHT gradient (mirl_conv1_u8_wrw / _wrw_ex / _wrw_masked): 1 = bf16 MFMA with the exact
- * three-way split of the gradient operand (pixels are exact in bf16; the default, MIRL_CONV1_WRW_BF16), 0 = f32 MFMA,
- * negative = back to the environment's choice.  In-process A/B tests.                                                  */
+ * three-way split of the gradient operand (pixels are exact in bf16; the default), 0 = f32 MFMA,
+ * negative = back to the default.  In-process A/B tests.                                                               */
 int mirl_conv1_wrw_bf16_set(int32_t mode);
 int mirl_conv1_u8_fwd(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* weight,
                       int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w, const float* bias,
@@ -575,7 +574,7 @@ int mirl_gemm3(int32_t layout, int64_t M, int64_t N, int64_t K, const float* A, 
  * 2^group_shift consecutive rows.  Removes the separate multiply pass over the (rows, N) embedding. */
 /* Plain NT products with too few 256 x 256 tiles to fill the chip take a 256 x 128 tile (k_gemm3_mid; the acting batch's
  * hidden layer at 256 envs: 8 192 x 1 024 x 512 in 55 us against 71 with the big tile and 73 on the library).  Process-wide
- * switch for in-process A/B runs: -1 = the MIRL_GEMM3_MID environment default (on), 0 = always the big tile, 1 = on.        */
+ * switch for in-process A/B runs: -1 = the default (on), 0 = always the big tile, 1 = on.                                   */
 int mirl_gemm3_mid_set(int32_t mode);
 int mirl_gemm3_nt_mul(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B,
                       int64_t ldb, float* C, int64_t ldc, const float* bias, int32_t relu,

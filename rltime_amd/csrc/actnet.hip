@@ -732,9 +732,8 @@ extern "C" int mirl_act_embed(int32_t E, int32_t N, int32_t H, int32_t D, const 
   const int R = E * N;
   // enough workgroups to fill the chip twice, then more rows per workgroup (the weights stay in its registers)
   const int tiles = (R + 15) / 16, ycount = (H + 127) / 128;
-  static const int groups_env = getenv("MIRL_ACT_EMBED_GROUPS") ? atoi(getenv("MIRL_ACT_EMBED_GROUPS")) : 0;
-  int groups = groups_env > 0 ? groups_env : 1;
-  if (groups_env <= 0) while (groups < 8 && (tiles / (2 * groups)) * ycount >= 512) groups *= 2;
+  int groups = 1;
+  while (groups < 8 && (tiles / (2 * groups)) * ycount >= 512) groups *= 2;
   a.groups = groups;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps("k_act_embed", 4.0 * ((double)R * H + (double)E * H + (double)H * D), st, 2.0 * (double)R * H * D);

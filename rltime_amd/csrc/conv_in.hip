@@ -709,9 +709,9 @@ static int c1_pitch(int HW) {
 
 }  // namespace mirl
 
-static int g_conv1_wrw_bf16 = -1;  // -1: MIRL_CONV1_WRW_BF16 (default on); 0 / 1: set by mirl_conv1_wrw_bf16_set (in-process A/B tests)
+static int g_conv1_wrw_bf16 = 1;   // mirl_conv1_wrw_bf16_set (in-process A/B tests): 0 = off, anything else (-1 = default) = on
 extern "C" int mirl_conv1_wrw_bf16_set(int32_t mode) {
-  g_conv1_wrw_bf16 = mode < 0 ? -1 : (mode ? 1 : 0);
+  g_conv1_wrw_bf16 = mode ? 1 : 0;
   return MIRL_OK;
 }
 
@@ -720,9 +720,8 @@ namespace mirl {
 template <bool MASK>
 static int c1_wrw_b3(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* g, const float* y, float* scratch, int slab,
                      unsigned* grid_out, hipStream_t st, bool* ran) {
-  static const int env = getenv("MIRL_CONV1_WRW_BF16") ? atoi(getenv("MIRL_CONV1_WRW_BF16")) : 1;
   *ran = false;
-  if (!(g_conv1_wrw_bf16 >= 0 ? g_conv1_wrw_bf16 : env)) return MIRL_OK;
+  if (!g_conv1_wrw_bf16) return MIRL_OK;
   const int OH = (H - C1_K) / C1_S + 1, OW = (W - C1_K) / C1_S + 1, HW = H * W, Pd = c1b_pitch(HW, OW);
   size_t lds = (size_t)C1_PLANES * Pd * 2;
   if (lds > 80 * 1024) return MIRL_OK;                             // two workgroups per CU or the f32-pipe kernel
@@ -852,8 +851,7 @@ extern "C" int mirl_conv1_u8_fwd_ex(int64_t N, int32_t H, int32_t W, const uint8
 extern "C" int mirl_conv1_u8_fwd(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* weight, int64_t ws_o,
                                  int64_t ws_c, int64_t ws_h, int64_t ws_w, const float* bias, float scale, float* wpk,
                                  float* y, void* stream) {
-  static const int flags = getenv("MIRL_CONV1_FLAGS") ? atoi(getenv("MIRL_CONV1_FLAGS")) : 0;
-  return mirl_conv1_u8_fwd_ex(N, H, W, x, weight, ws_o, ws_c, ws_h, ws_w, bias, scale, wpk, y, flags, stream);
+  return mirl_conv1_u8_fwd_ex(N, H, W, x, weight, ws_o, ws_c, ws_h, ws_w, bias, scale, wpk, y, 0, stream);
 }
 
 // floats of `wpk` scratch mirl_conv1_u8_fwd[_ex] needs (the bf16-pipe kernel packs three 16 KB weight parts: more than the
@@ -969,6 +967,6 @@ extern "C" int mirl_conv1_u8_wrw_masked(int64_t N, int32_t H, int32_t W, const u
 extern "C" int mirl_conv1_u8_wrw(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* g, float scale,
                                  float* scratch, float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w,
                                  void* stream) {
-  static const int flags = getenv("MIRL_CONV1_WRW_FLAGS") ? atoi(getenv("MIRL_CONV1_WRW_FLAGS")) : 0;   // hoisted conversions: 2.60 vs 2.66 ms per 42 496 frames (profiles/r03)
-  return mirl_conv1_u8_wrw_ex(N, H, W, x, g, scale, scratch, dw, ws_o, ws_c, ws_h, ws_w, flags, stream);
+  // flags 0, hoisted conversions: 2.60 vs 2.66 ms per 42 496 frames (profiles/r03)
+  return mirl_conv1_u8_wrw_ex(N, H, W, x, g, scale, scratch, dw, ws_o, ws_c, ws_h, ws_w, 0, stream);
 }

@@ -125,7 +125,5 @@ extern "C" int mirl_frames_to_f32_nhwc_ex(int64_t N, int32_t C, int32_t HW, cons
 }
 
 extern "C" int mirl_frames_to_f32_nhwc(int64_t N, int32_t C, int32_t HW, const uint8_t* src, float scale, float* dst, void* stream) {
-  static const int per_wg = getenv("MIRL_CONVERT_PER_WG") ? atoi(getenv("MIRL_CONVERT_PER_WG")) : 0;
-  static const int flags = getenv("MIRL_CONVERT_FLAGS") ? atoi(getenv("MIRL_CONVERT_FLAGS")) : 1;   // cached loads, nt stores
-  return mirl_frames_to_f32_nhwc_ex(N, C, HW, src, scale, dst, per_wg, flags, stream);
+  return mirl_frames_to_f32_nhwc_ex(N, C, HW, src, scale, dst, /*per_wg: heuristic*/ 0, /*flags: cached loads, nt stores*/ 1, stream);
 }

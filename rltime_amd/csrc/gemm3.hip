@@ -64,7 +64,6 @@ struct G3Args {
   //   C[row][col] = e > 0 ? d * x : 0;   gsum[row >> 5][col] = sum over the group's 32 rows of d * e;
   //   part[2 it + wm][col] = this wave's 128-row column sum of C   (the embedding layer's bias gradient, summed by the caller)
   float* gsum; int64_t ldgsum;
-  int prio;              // experiment switch (MIRL_GEMM3_PRIO): 1 = s_setprio 1 around every MFMA block, 2 = waves 4-7 raised once
 };
 
 
@@ -187,7 +186,6 @@ k_gemm3(G3Args g) {
   const int b_off = (wn * 64 + (lane & 31)) * G3_PITCH + (lane >> 5) * 16;
   const bool stage_first = (wu >> 2) & 1;      // waves w and w + 4 share a SIMD and take opposite orders
 
-  if (g.prio == 2 && wu >= 4) __builtin_amdgcn_s_setprio(1);
   // first tile of this workgroup
   int e = l, it = 0, jt = 0;
   if (g.splits > 1) {
@@ -232,9 +230,9 @@ k_gemm3(G3Args g) {
         if (k + 1 < nk) { la.store(nxt, va); lb.store(nxt + 3 * G3_PLANE, vb); }
         if (k + 2 < nk) { la.load(va); lb.load(vb); }
       }
-      if (g.prio == 1) __builtin_amdgcn_s_setprio(1);
+      __builtin_amdgcn_s_setprio(1);
       g3_compute<TI>(cur, acc, a_off, b_off);
-      if (g.prio == 1) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
       if (!stage_first) {
         if (k + 1 < nk) { la.store(nxt, va); lb.store(nxt + 3 * G3_PLANE, vb); }
         if (k + 2 < nk) { la.load(va); lb.load(vb); }
@@ -636,7 +634,7 @@ k_g3_head_reduce(const float* __restrict__ part, int ncb, int64_t M, int O, cons
   }
 }
 
-static int g_g3_mid_mode = -1;       // mirl_gemm3_mid_set: -1 = MIRL_GEMM3_MID (default on), 0 / 1 = forced for in-process A/B runs
+static int g_g3_mid_mode = -1;       // mirl_gemm3_mid_set: -1 = on (the default), 0 / 1 = forced for in-process A/B runs
 
 static int g3_splits(int64_t M, int64_t N, int64_t K) {
   const int64_t tiles = ((M + 255) / 256) * ((N + 255) / 256);
@@ -688,14 +686,10 @@ static int g3_launch(int32_t layout, int64_t M, int64_t N, int64_t K, const floa
   g.relu = relu ? 1 : 0;
   g.mul = mul; g.ldmul = ldmul; g.mul_shift = mul_shift; g.pre = pre; g.ldpre = ldpre;
   g.w2 = w2; g.part = part; g.gsum = gsum; g.ldgsum = ldgsum;
-  static const int prio_env = getenv("MIRL_GEMM3_PRIO") ? atoi(getenv("MIRL_GEMM3_PRIO")) : 1;
-  g.prio = prio_env;
-  static const int vec_env = getenv("MIRL_GEMM3_VEC") ? atoi(getenv("MIRL_GEMM3_VEC")) : 1;
-  g.vec_ok = vec_env && (N % 4 == 0) && (ldc % 4 == 0) && !((uintptr_t)C % 16) && (!w2 || !((uintptr_t)w2 % 16)) && (!bias || !((uintptr_t)bias % 16)) &&
+  g.vec_ok = (N % 4 == 0) && (ldc % 4 == 0) && !((uintptr_t)C % 16) && (!w2 || !((uintptr_t)w2 % 16)) && (!bias || !((uintptr_t)bias % 16)) &&
              (!mul || ((ldmul % 4 == 0) && !((uintptr_t)mul % 16))) && (!pre || ((ldpre % 4 == 0) && !((uintptr_t)pre % 16)));
   g.mt = (int)((M + 255) / 256); g.nt = (int)((N + 255) / 256);
   g.splits = 1; g.steps_per_split = (int)(K / 16);
-  static const int narrow_env = getenv("MIRL_GEMM3_NARROW") ? atoi(getenv("MIRL_GEMM3_NARROW")) : 1;
   unsigned grid = (unsigned)(8 * ((g.mt + 7) / 8) * g.nt);                 // one tile per workgroup
   if (K <= 128) {          // short K: the tile is mostly epilogue — let the next tile's loads fly during the stores
     int dev = 0, cus = 256;
@@ -714,10 +708,8 @@ static int g3_launch(int32_t layout, int64_t M, int64_t N, int64_t K, const floa
     grid = (unsigned)(g.mt * g.nt * g.splits);
   }
   const int vec = g.vec_ok ? 1 : 0;
-  // too few 256 x 256 tiles for the chip: the 256 x 128 tile (plain NT with bias / ReLU; MIRL_GEMM3_MID=0 keeps the big tile)
-  static const int mid_default = getenv("MIRL_GEMM3_MID") ? atoi(getenv("MIRL_GEMM3_MID")) : 1;
-  const int mid_env = g_g3_mid_mode >= 0 ? g_g3_mid_mode : mid_default;
-  if (mid_env && layout == 0 && !mul && !w2 && !gsum && vec && (N % 4) == 0 && (int64_t)g.mt * g.nt < 192 && N > 128 &&
+  // too few 256 x 256 tiles for the chip: the 256 x 128 tile (plain NT with bias / ReLU; mirl_gemm3_mid_set(0) keeps the big tile)
+  if (g_g3_mid_mode != 0 && layout == 0 && !mul && !w2 && !gsum && vec && (N % 4) == 0 && (int64_t)g.mt * g.nt < 192 && N > 128 &&
       ((int64_t)g.mt * ((N + G3M_BROWS - 1) / G3M_BROWS) >= 192 || (int64_t)g.mt * g.nt < 24)) {
     // (between: neither tiling fills the chip — the callers' area gate, models/torch/gemm3.py _MIN_AREA, keeps those
     //  products on the library; tiny products take the smaller tile for its shorter tail)
@@ -733,7 +725,7 @@ static int g3_launch(int32_t layout, int64_t M, int64_t N, int64_t K, const floa
   static bool attr[4][2] = {{false, false}, {false, false}, {false, false}, {false, false}};
   const void* fns[4][2] = {{(const void*)k_gemm3<true, true, 0, false>, (const void*)k_gemm3<true, true, 0, true>},
                            {(const void*)k_gemm3<true, false, 0, false>, (const void*)k_gemm3<true, false, 0, true>},
-                           {(const void*)k_gemm3<false, false, 0, false>, (const void*)k_gemm3<false, false, 0, true>},
+                           {nullptr /* split K takes 16-byte aligned rows only (checked above): vec holds */, (const void*)k_gemm3<false, false, 0, true>},
                            {(const void*)k_gemm3<true, true, 1, false>, (const void*)k_gemm3<true, true, 1, true>}};
   const int which = (mul && !gsum) ? 3 : layout;
   const void* fn = fns[which][vec];
@@ -748,12 +740,11 @@ static int g3_launch(int32_t layout, int64_t M, int64_t N, int64_t K, const floa
     static bool hd_attr = false;
     fn = (const void*)k_gemm3<true, true, 2, true>;
     if (!hd_attr) { MIRL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS)); hd_attr = true; }
-  } else if (layout == 2 && N <= 64 && narrow_env) {
+  } else if (layout == 2 && N <= 64) {
     // weight gradient of a narrow layer: eight waves stacked along M, 12 MFMAs per K-step (k_gemm3 NARROW)
-    static bool nr_attr[2] = {false, false};
-    const void* nr[2] = {(const void*)k_gemm3<false, false, 0, false, true>, (const void*)k_gemm3<false, false, 0, true, true>};
-    fn = nr[vec];
-    if (!nr_attr[vec]) { MIRL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS)); nr_attr[vec] = true; }
+    static bool nr_attr = false;
+    fn = (const void*)k_gemm3<false, false, 0, true, true>;
+    if (!nr_attr) { MIRL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS)); nr_attr = true; }
   } else
   if (!attr[which][vec]) { MIRL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS)); attr[which][vec] = true; }
   {
@@ -783,7 +774,7 @@ extern "C" int mirl_gemm3(int32_t layout, int64_t M, int64_t N, int64_t K, const
 }
 
 extern "C" int mirl_gemm3_mid_set(int32_t mode) {
-  if (mode < -1 || mode > 1) return mirl::fail(MIRL_ERR_ARG, "gemm3_mid_set: mode is -1 (environment default), 0 or 1");
+  if (mode < -1 || mode > 1) return mirl::fail(MIRL_ERR_ARG, "gemm3_mid_set: mode is -1 (default), 0 or 1");
   mirl::g_g3_mid_mode = mode;
   return MIRL_OK;
 }

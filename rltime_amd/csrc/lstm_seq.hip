@@ -685,15 +685,15 @@ static int seq_init() {
   return MIRL_OK;
 }
 
+// small batches: four times as many, four times narrower waves (k_lstm_seq_fwd_narrow) while they all
+// fit the chip at once (every wave a step waits for must be resident)
+static bool seq_narrow(int nrb, int H) { return nrb * (H / 4) <= g_seq_cus; }
+
 template <int H>
 static int seq_launch(const SeqFwdArgs& a, void* workspace, hipStream_t st) {
   constexpr int NCG = H / 16, KQ = H / 16;
   const int tiles = a.B / 16, nrb = (a.B + 63) / 64;
-  // small batches: four times as many, four times narrower waves (k_lstm_seq_fwd_narrow) while they all
-  // fit the chip at once (every wave a step waits for must be resident)
-  static const int narrow_env = getenv("MIRL_LSTM_SEQ_NARROW") ? atoi(getenv("MIRL_LSTM_SEQ_NARROW")) : -1;
-  const bool narrow = narrow_env >= 0 ? (narrow_env != 0 && nrb * (H / 4) <= g_seq_cus) : (nrb * (H / 4) <= g_seq_cus);
-  if (narrow) {
+  if (seq_narrow(nrb, H)) {
     const size_t cnt_b = (size_t)tiles * 32 * sizeof(unsigned);
     const int64_t x_half_n = (int64_t)tiles * KQ * 256;
     unsigned* counters_n = (unsigned*)workspace;
@@ -830,10 +830,8 @@ extern "C" int mirl_lstm_seq_fwd_grid(int32_t B, int32_t H, int32_t* workgroups,
   int rc = seq_init();
   if (rc) return rc;
   const int NCG = H / 16, nrb = (B + 63) / 64;
-  static const int narrow_env = getenv("MIRL_LSTM_SEQ_NARROW") ? atoi(getenv("MIRL_LSTM_SEQ_NARROW")) : -1;
-  const bool narrow = (narrow_env != 0) && (nrb * (H / 4) <= g_seq_cus);
   int64_t lds;
-  if (narrow) {
+  if (seq_narrow(nrb, H)) {
     *workgroups = nrb * (H / 4);
     lds = (int64_t)(16 * (H + 4) + 4 * 64) * (int64_t)sizeof(float);
   } else {

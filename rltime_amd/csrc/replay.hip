@@ -540,9 +540,7 @@ __device__ __forceinline__ int64_t row_src_off(const Dev& d, int overlapped, int
 
 // out[r][b][:] = ring[env[b]][src(r, b)][:] for one leaf of the state pytree.
 // One workgroup per (r, b) row: the source is a contiguous ring slot, the
-// destination a contiguous row of the time-major batch, 16 B per lane, four
-// independent loads in flight per lane before the first store.
-template <int NT>
+// destination a contiguous row of the time-major batch, 16 B per lane.
 __global__ void __launch_bounds__(256)
 k_gather_rows(Dev d, const uint8_t* __restrict__ ring, uint8_t* __restrict__ out,
               const int32_t* __restrict__ env, const int64_t* __restrict__ start,
@@ -558,44 +556,25 @@ k_gather_rows(Dev d, const uint8_t* __restrict__ ring, uint8_t* __restrict__ out
     const int n = row_bytes >> 4;
     const u32x4* s4 = (const u32x4*)s;
     u32x4* t4 = (u32x4*)t;
-    int c = threadIdx.x;
-    for (; c + 768 < n; c += 1024) {
-      u32x4 v0, v1, v2, v3;
-      if (NT) {
-        v0 = __builtin_nontemporal_load(s4 + c); v1 = __builtin_nontemporal_load(s4 + c + 256);
-        v2 = __builtin_nontemporal_load(s4 + c + 512); v3 = __builtin_nontemporal_load(s4 + c + 768);
-        __builtin_nontemporal_store(v0, t4 + c); __builtin_nontemporal_store(v1, t4 + c + 256);
-        __builtin_nontemporal_store(v2, t4 + c + 512); __builtin_nontemporal_store(v3, t4 + c + 768);
-      } else {
-        v0 = s4[c]; v1 = s4[c + 256]; v2 = s4[c + 512]; v3 = s4[c + 768];
-        t4[c] = v0; t4[c + 256] = v1; t4[c + 512] = v2; t4[c + 768] = v3;
-      }
-    }
-    for (; c < n; c += 256) {
-      if (NT) __builtin_nontemporal_store(__builtin_nontemporal_load(s4 + c), t4 + c);
-      else t4[c] = s4[c];
-    }
+    // rows of 8 KB and more go to k_gather_rows_v1: at most two chunks per lane here
+    for (int c = threadIdx.x; c < n; c += 256) __builtin_nontemporal_store(__builtin_nontemporal_load(s4 + c), t4 + c);
   } else {
     for (int c = threadIdx.x; c < row_bytes; c += 256) t[c] = s[c];
   }
 }
 
-// Default launch shape for 16-byte-aligned rows (MIRL_GATHER_VARIANT=1): 512
-// lanes per row and every load of the row issued before its first store.
+// Launch shape for 16-byte-aligned rows of at least 8 KB: 512 lanes per row and
+// every load of the row issued before its first store.
 // Measured on MI355X at B=512, L+n=122, 1M-transition replay (profiles/):
 // 0.638 ms (5.53 TB/s) vs 0.654 ms for the 256-lane kernel above; a persistent
 // 2048..8192-workgroup variant and a source-contiguous block order were slower
 // (0.66-0.72 ms) at this replay size and were dropped.
-template <int NTL>
 __global__ void __launch_bounds__(512)
 k_gather_rows_v1(Dev d, const uint8_t* __restrict__ ring, uint8_t* __restrict__ out,
                  const int32_t* __restrict__ env, const int64_t* __restrict__ start,
-                 int B, int overlapped, int32_t row_bytes, int64_t ring_stride, int order) {
-  int64_t rb = blockIdx.x;
-  const int R = gridDim.x / B;
-  int r, b;
-  if (order) { b = (int)(rb / R); r = (int)(rb % R); rb = (int64_t)r * B + b; }   // source-contiguous order
-  else { r = (int)(rb / B); b = (int)(rb % B); }
+                 int B, int overlapped, int32_t row_bytes, int64_t ring_stride) {
+  const int64_t rb = blockIdx.x;
+  const int r = (int)(rb / B), b = (int)(rb % B);
   int32_t e = env[b];
   if (e < 0 || e >= d.E) e = 0;
   const int64_t src_off = row_src_off(d, overlapped, r, e, start[b]);
@@ -604,18 +583,15 @@ k_gather_rows_v1(Dev d, const uint8_t* __restrict__ ring, uint8_t* __restrict__ 
   const int n = row_bytes >> 4;
   int c = threadIdx.x;
   for (; c + 1536 < n; c += 2048) {
-    u32x4 v0, v1, v2, v3;
-    if (NTL) {
-      v0 = __builtin_nontemporal_load(s4 + c); v1 = __builtin_nontemporal_load(s4 + c + 512);
-      v2 = __builtin_nontemporal_load(s4 + c + 1024); v3 = __builtin_nontemporal_load(s4 + c + 1536);
-    } else { v0 = s4[c]; v1 = s4[c + 512]; v2 = s4[c + 1024]; v3 = s4[c + 1536]; }
+    u32x4 v0 = __builtin_nontemporal_load(s4 + c), v1 = __builtin_nontemporal_load(s4 + c + 512);
+    u32x4 v2 = __builtin_nontemporal_load(s4 + c + 1024), v3 = __builtin_nontemporal_load(s4 + c + 1536);
     __builtin_nontemporal_store(v0, t4 + c); __builtin_nontemporal_store(v1, t4 + c + 512);
     __builtin_nontemporal_store(v2, t4 + c + 1024); __builtin_nontemporal_store(v3, t4 + c + 1536);
   }
   u32x4 w0, w1, w2; bool h0 = c < n, h1 = c + 512 < n, h2 = c + 1024 < n;
-  if (h0) w0 = NTL ? __builtin_nontemporal_load(s4 + c) : s4[c];
-  if (h1) w1 = NTL ? __builtin_nontemporal_load(s4 + c + 512) : s4[c + 512];
-  if (h2) w2 = NTL ? __builtin_nontemporal_load(s4 + c + 1024) : s4[c + 1024];
+  if (h0) w0 = __builtin_nontemporal_load(s4 + c);
+  if (h1) w1 = __builtin_nontemporal_load(s4 + c + 512);
+  if (h2) w2 = __builtin_nontemporal_load(s4 + c + 1024);
   if (h0) __builtin_nontemporal_store(w0, t4 + c);
   if (h1) __builtin_nontemporal_store(w1, t4 + c + 512);
   if (h2) __builtin_nontemporal_store(w2, t4 + c + 1024);
@@ -664,6 +640,7 @@ k_gather_rows_dedup(Dev d, uint8_t* __restrict__ out, const int32_t* __restrict_
 // whose source transitions are not one short run (layout seams, truncated n-step
 // targets at the ring end) take the direct path of k_gather_rows_dedup.
 #define MIRL_DD_MAX_PLANES 22
+#define MIRL_DD_LDS_BYTES 65536        // staging budget: the dynamic LDS a launch may ask for without a function attribute
 __global__ void __launch_bounds__(512)
 k_gather_rows_dedup_lds(Dev d, uint8_t* __restrict__ out, const int32_t* __restrict__ env,
                         const int64_t* __restrict__ start, int B, int R, int overlapped, int RC, int lds_planes) {
@@ -969,10 +946,6 @@ struct mirl_replay {
   double* gpow_dev = nullptr;
   int32_t* bad_host = nullptr;
   int64_t* td_idx = nullptr; float* td_loss = nullptr; int td_cap = 0;   // acting-time priority scratch
-  int gather_nt = 0;
-  int gather_variant = 1, gather_order = 0;
-  int recalc_wave = 1;
-  int dedup_lds = 1;
   int prof = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
   // rollout plan (mirl_replay_ingest_plan / _planned): ONE device buffer at a fixed address — captured graphs hold it
@@ -1088,12 +1061,6 @@ extern "C" int mirl_replay_create(const mirl_replay_config* cfg, mirl_replay** o
   // are shifted to the ring end by avoid_episode_crossing.
   h->overlapped = (bk.N < bk.L && !cfg->avoid_episode_crossing) ? 1 : 0;
   h->rows = h->overlapped ? bk.L + bk.N : 2 * bk.L;
-  const char* nt = getenv("MIRL_GATHER_NT");
-  h->gather_nt = nt ? atoi(nt) : 1;
-  if (const char* v = getenv("MIRL_GATHER_VARIANT")) h->gather_variant = atoi(v);
-  if (const char* v = getenv("MIRL_GATHER_ORDER")) h->gather_order = atoi(v);
-  if (const char* v = getenv("MIRL_RECALC_WAVE")) h->recalc_wave = atoi(v);
-  if (const char* v = getenv("MIRL_DEDUP_LDS")) h->dedup_lds = atoi(v);
   MIRL_HIP(hipDeviceSynchronize());
   *out = h;
   return MIRL_OK;
@@ -1152,7 +1119,7 @@ static IngestSrc make_ingest_src(const Dev& d, const mirl_ingest* in) {
                    f_stride, f_row, f_slot};
 }
 
-static int g_ingest_fused = -1;     // -1: take MIRL_INGEST_FUSED (default on) at the first ingest
+static int g_ingest_fused = 1;      // test hook: mirl_ingest_fused_set
 extern "C" int mirl_ingest_fused_set(int32_t on) { g_ingest_fused = on ? 1 : 0; return MIRL_OK; }
 
 extern "C" int mirl_replay_ingest(mirl_replay* h, const mirl_ingest* in, void* stream) {
@@ -1189,7 +1156,6 @@ extern "C" int mirl_replay_ingest(mirl_replay* h, const mirl_ingest* in, void* s
   rc = h->staging.upload(total, st); if (rc) return rc;
   const int32_t* s_env = (const int32_t*)(db + o_env);
   const int64_t* s_off = (const int64_t*)(db + o_off);
-  if (g_ingest_fused < 0) g_ingest_fused = (getenv("MIRL_INGEST_FUSED") && atoi(getenv("MIRL_INGEST_FUSED")) == 0) ? 0 : 1;
   if ((g_ingest_fused && !d.planes && !(h->book.cfg.acting_priority_init && d.per)) || (d.planes && in->newest_plane_only)) {
     const IngestSrc src = make_ingest_src(d, in);
     const int32_t f_row = src.row_bytes;
@@ -1267,7 +1233,6 @@ extern "C" int mirl_replay_ingest(mirl_replay* h, const mirl_ingest* in, void* s
 // changes; mirl_replay_ingest_planned enqueues the device side of ONE of those steps with no host argument that
 // varies from rollout to rollout — the call a HIP graph of the whole rollout captures (acting/fast_step.py).
 static bool planned_ingest_ok(mirl_replay* h) {
-  if (g_ingest_fused < 0) g_ingest_fused = (getenv("MIRL_INGEST_FUSED") && atoi(getenv("MIRL_INGEST_FUSED")) == 0) ? 0 : 1;
   return g_ingest_fused && !h->d.planes && !(h->book.cfg.acting_priority_init && h->d.per);
 }
 
@@ -1528,35 +1493,32 @@ extern "C" int mirl_replay_sample_global(mirl_replay* h, int32_t mbatch_local, i
   return MIRL_OK;
 }
 
+// Runs `launch` between two stream events when `timed`; mirl_replay_profile sums the pairs.
+template <class F>
+static int timed_launch(mirl_replay* h, bool timed, hipStream_t st, F launch) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (timed) { MIRL_HIP(hipEventCreate(&e0)); MIRL_HIP(hipEventCreate(&e1)); MIRL_HIP(hipEventRecord(e0, st)); }
+  launch();
+  MIRL_LAUNCH_CHECK();
+  if (timed) { MIRL_HIP(hipEventRecord(e1, st)); h->prof_events.push_back(std::make_pair(e0, e1)); }
+  return MIRL_OK;
+}
+
 static int gather_leaf(mirl_replay* h, const void* ring, void* out, const int32_t* env, const int64_t* start,
                        int B, int32_t row_bytes, int64_t ring_stride, hipStream_t st) {
   if (!row_bytes || !out) return MIRL_OK;
   int vec = (row_bytes % 16 == 0) && (ring_stride % 16 == 0) && (((uintptr_t)out) % 16 == 0);
   int64_t blocks = (int64_t)h->rows * B;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  const bool timed = h->prof && ring == (const void*)h->d.frames;
-  if (timed) { MIRL_HIP(hipEventCreate(&e0)); MIRL_HIP(hipEventCreate(&e1)); MIRL_HIP(hipEventRecord(e0, st)); }
-  {
-  ProfScope ps(ring == (const void*)h->d.frames ? "k_gather_rows(frames)" : (ring == (const void*)h->d.state ? "k_gather_rows(recurrent state)" : "k_gather_rows(extra)"),
-               2.0 * (double)blocks * row_bytes, st);
-  if (vec && h->gather_variant == 1 && row_bytes >= 512 * 16) {    // small rows (recurrent state) keep the 256-lane shape
-    if (h->gather_nt == 2)                                          // cached loads, non-temporal stores
-      hipLaunchKernelGGL(k_gather_rows_v1<0>, dim3((unsigned)blocks), dim3(512), 0, st, h->d, (const uint8_t*)ring, (uint8_t*)out,
-                         env, start, B, h->overlapped, row_bytes, ring_stride, h->gather_order);
+  return timed_launch(h, h->prof && ring == (const void*)h->d.frames, st, [&] {
+    ProfScope ps(ring == (const void*)h->d.frames ? "k_gather_rows(frames)" : (ring == (const void*)h->d.state ? "k_gather_rows(recurrent state)" : "k_gather_rows(extra)"),
+                 2.0 * (double)blocks * row_bytes, st);
+    if (vec && row_bytes >= 512 * 16)                                // small rows (recurrent state) keep the 256-lane shape
+      hipLaunchKernelGGL(k_gather_rows_v1, dim3((unsigned)blocks), dim3(512), 0, st, h->d, (const uint8_t*)ring, (uint8_t*)out,
+                         env, start, B, h->overlapped, row_bytes, ring_stride);
     else
-      hipLaunchKernelGGL(k_gather_rows_v1<1>, dim3((unsigned)blocks), dim3(512), 0, st, h->d, (const uint8_t*)ring, (uint8_t*)out,
-                         env, start, B, h->overlapped, row_bytes, ring_stride, h->gather_order);
-  }
-  else if (h->gather_nt)
-    hipLaunchKernelGGL(k_gather_rows<1>, dim3((unsigned)blocks), dim3(256), 0, st, h->d, (const uint8_t*)ring, (uint8_t*)out,
-                       env, start, B, h->overlapped, row_bytes, ring_stride, vec);
-  else
-    hipLaunchKernelGGL(k_gather_rows<0>, dim3((unsigned)blocks), dim3(256), 0, st, h->d, (const uint8_t*)ring, (uint8_t*)out,
-                       env, start, B, h->overlapped, row_bytes, ring_stride, vec);
-  }
-  MIRL_LAUNCH_CHECK();
-  if (timed) { MIRL_HIP(hipEventRecord(e1, st)); h->prof_events.push_back(std::make_pair(e0, e1)); }
-  return MIRL_OK;
+      hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)blocks), dim3(256), 0, st, h->d, (const uint8_t*)ring, (uint8_t*)out,
+                         env, start, B, h->overlapped, row_bytes, ring_stride, vec);
+  });
 }
 
 extern "C" int mirl_replay_profile(mirl_replay* h, int32_t enable, int64_t* launches, double* total_ms) {
@@ -1715,30 +1677,21 @@ extern "C" int mirl_replay_gather(mirl_replay* h, int32_t B, const int32_t* env,
   if (d.planes) {
     if (((uintptr_t)out->frames) % 16) return fail(MIRL_ERR_ARG, "stack_planes: the frames output must be 16-byte aligned");
     const int64_t blocks = (int64_t)h->rows * B;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->prof) { MIRL_HIP(hipEventCreate(&e0)); MIRL_HIP(hipEventCreate(&e1)); MIRL_HIP(hipEventRecord(e0, st)); }
-    {
+    rc = timed_launch(h, h->prof, st, [&] {
       // algorithmic bytes: every output stack written once + every distinct plane of a
       // window read once (rows + P - 1 planes per sequence and state block)
       ProfScope ps("k_gather_rows_dedup(frames)", (double)blocks * d.F + (double)B * (h->rows + d.planes - 1) * d.plane_bytes, st);
-      // LDS-staged variant: as many planes as fit in 64 KB; RC rows per workgroup
-      static const int lds_kb = getenv("MIRL_DEDUP_LDS_KB") ? atoi(getenv("MIRL_DEDUP_LDS_KB")) : 64;
-      int lds_planes = (int)((size_t)lds_kb * 1024 / d.plane_bytes); if (lds_planes > MIRL_DD_MAX_PLANES) lds_planes = MIRL_DD_MAX_PLANES;
+      // LDS-staged variant: as many planes as fit in the budget; RC rows per workgroup
+      int lds_planes = MIRL_DD_LDS_BYTES / d.plane_bytes; if (lds_planes > MIRL_DD_MAX_PLANES) lds_planes = MIRL_DD_MAX_PLANES;
       const int RC = lds_planes - (d.planes - 1);
-      static bool lds_attr = false;
-      if (!lds_attr && (size_t)lds_planes * d.plane_bytes > 65536) {
-        MIRL_HIP(hipFuncSetAttribute((const void*)k_gather_rows_dedup_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        lds_attr = true;
-      }
-      if (h->dedup_lds && RC >= 2) {
+      if (RC >= 2) {
         const int chunks = (h->rows + RC - 1) / RC;
         hipLaunchKernelGGL(k_gather_rows_dedup_lds, dim3((unsigned)(chunks * B)), dim3(512), (size_t)lds_planes * d.plane_bytes, st, d,
                            out->frames, env, start, B, h->rows, h->overlapped, RC, lds_planes);
       } else
-      hipLaunchKernelGGL(k_gather_rows_dedup, dim3((unsigned)blocks), dim3(512), 0, st, d, out->frames, env, start, B, h->overlapped);
-    }
-    MIRL_LAUNCH_CHECK();
-    if (h->prof) { MIRL_HIP(hipEventRecord(e1, st)); h->prof_events.push_back(std::make_pair(e0, e1)); }
+        hipLaunchKernelGGL(k_gather_rows_dedup, dim3((unsigned)blocks), dim3(512), 0, st, d, out->frames, env, start, B, h->overlapped);
+    });
+    if (rc) return rc;
   } else {
     rc = gather_leaf(h, d.frames, out->frames, env, start, B, d.F, d.Fp, st); if (rc) return rc;
   }
@@ -1758,8 +1711,6 @@ extern "C" int mirl_replay_gather(mirl_replay* h, int32_t B, const int32_t* env,
   return MIRL_OK;
 }
 
-static int update_losses_impl(mirl_replay* h, int64_t count, const int64_t* indices, const float* losses, hipStream_t st);
-
 extern "C" int mirl_replay_update_losses(mirl_replay* h, int64_t count, const int64_t* indices, const float* losses, void* stream) {
   if (!h) return fail(MIRL_ERR_ARG, "null handle");
   if (!h->d.per || count <= 0) return MIRL_OK;           // history.py:332-335 no-op for non-prioritized buffers
@@ -1778,7 +1729,7 @@ static int update_losses_impl(mirl_replay* h, int64_t count, const int64_t* indi
   { ProfScope ps("k_loss_write", (double)count * 32.0, st);
     hipLaunchKernelGGL(k_loss_write, dim3(g), dim3(256), 0, st, d, count, indices, losses, epoch); }
   MIRL_LAUNCH_CHECK();
-  if (d.T >= 8 && d.T <= 128 && h->recalc_wave) {
+  if (d.T >= 8 && d.T <= 128) {
     ProfScope ps("k_recalc_flagged_wave", (double)d.n_slots + (double)count * 4.0 * 2, st);
     hipLaunchKernelGGL(k_recalc_flagged_wave, dim3((unsigned)((d.n_slots + 3) / 4)), dim3(256), 0, st, d);
   } else {
@@ -1917,8 +1868,7 @@ extern "C" int mirl_copy_bytes_ex(void* dst, const void* src, int64_t bytes, int
 }
 
 extern "C" int mirl_copy_bytes(void* dst, const void* src, int64_t bytes, void* stream) {
-  static int nt = getenv("MIRL_COPY_NT") ? atoi(getenv("MIRL_COPY_NT")) : 0;
-  return mirl_copy_bytes_ex(dst, src, bytes, nt, stream);
+  return mirl_copy_bytes_ex(dst, src, bytes, 0, stream);
 }
 
 // ---- host-only hooks ---------------------------------------------------------

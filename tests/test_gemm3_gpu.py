@@ -54,6 +54,8 @@ SHAPES = [("nt", 256, 256, 16), ("nt", 1000, 300, 64), ("nt", 513, 1024, 512), (
           # N <= 64: the NARROW wave tiling (eight waves along M, csrc/gemm3.hip) — the quantile layer's weight gradient
           ("tn", 512, 64, 40960), ("tn", 300, 60, 4112), ("tn", 700, 64, 2064), ("tn", 256, 8, 1040)]
 NARROW_SHAPES = SHAPES[-4:]
+# the two sides of the N <= 64 choice between the split-K tilings, at the smallest K the layout takes
+SHAPES = SHAPES + [("tn", 256, 64, 128), ("tn", 256, 68, 128)]
 
 
 @pytest.mark.parametrize("lay,M,N,K", SHAPES)
@@ -67,6 +69,22 @@ def test_integer_operands_are_bit_exact(lay, M, N, K):
     got = gemm3.gemm(LAYOUTS[lay], a, b)
     assert got.shape == (M, N)
     assert torch.equal(got.double(), want)
+
+
+@pytest.mark.parametrize("lay,M,N,K,pitch,col0", [("nt", 300, 260, 48, 264, 1), ("nn", 300, 260, 48, 261, 0), ("nn", 300, 61, 48, 61, 0)])
+def test_integer_operands_are_bit_exact_without_16_byte_stores(lay, M, N, K, pitch, col0):
+    """An output the kernel cannot store 16 bytes at a time — rows that start 4 bytes off a 16-byte boundary, a row pitch
+    or a width that is no multiple of four floats — takes the element-wise epilogue: same bit-exact product, and nothing
+    written outside the output view."""
+    from rltime_amd.models.torch import gemm3
+    gen = torch.Generator(device="cuda").manual_seed(M * 7 + N * 3 + K)
+    a, b = _operands(lay, M, N, K, gen, integer=True)
+    wide = torch.full((M, pitch), float("nan"), device="cuda")
+    out = wide[:, col0:col0 + N]
+    assert out.data_ptr() % 16 or pitch % 4 or N % 4
+    gemm3.gemm(LAYOUTS[lay], a, b, out=out)
+    assert torch.equal(out.double(), _product(lay, a.double(), b.double()))
+    assert bool(torch.isnan(wide[:, :col0]).all()) and bool(torch.isnan(wide[:, col0 + N:]).all())
 
 
 @pytest.mark.parametrize("lay,M,N,K", SHAPES[:12] + NARROW_SHAPES)

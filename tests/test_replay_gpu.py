@@ -247,6 +247,18 @@ def test_frame_dedup_uniform_atari_frames_vs_oracle():
               dev_kw=dict(frame_stack_dedup=True))
 
 
+@pytest.mark.parametrize("frame_shape,dedup", [((1, 80, 103), False), ((1, 73, 112), False), ((4, 100, 164), True)])
+def test_gather_kernel_for_each_row_size_vs_oracle(frame_shape, dedup):
+    """The frame gather picks its kernel from the row alone (csrc/replay.hip gather_leaf, mirl_replay_gather): 8240-byte
+    rows take the 512-lane kernel with 515 sixteen-byte chunks (three lanes carry a second one), 8176-byte rows the
+    256-lane kernel with two chunks per lane, and four 16400-byte planes are too large to stage a run of rows in LDS, so
+    the stack is rebuilt straight from the ring.  Every gathered batch bit-identical to the oracle's, ring wrap included."""
+    _run_pair(54, 3, [("feed", 5), ("draw", 1, None), ("feed", 12), ("draw", 2, None), ("draw", 3, None)],
+              dict(size=36, train_frequency=0, nstep_target=2, nstep_train=2, prefix_steps=0),
+              0.99, False, dict(frame_shape=frame_shape, n_actions=4, done_prob=0.1, stacked=dedup), 2,
+              dev_kw=dict(frame_stack_dedup=True) if dedup else None)
+
+
 def test_frame_dedup_resets_within_an_envs_first_steps():
     """Episode ends inside an env's first three transitions: their stacks reach back
     to planes no transition stored (virtual predecessors in ring slots -1, -2, -3);

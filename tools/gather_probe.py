@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-probe of the replay gather / ingest kernels at the BASELINE shapes
 (B=512, T=80, burn-in 40, n=2, 84x84x4 u8 + 2x512 f32 LSTM state).  Prints
-algorithmic GB/s per variant; used while tuning, bench.py is the judged number."""
+algorithmic GB/s; used while tuning, bench.py is the judged number."""
 import json
 import os
 import sys
@@ -13,8 +13,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(nt, size, E, B, T, P, n, iters):
-    os.environ["MIRL_GATHER_NT"] = str(nt)
+def run(size, E, B, T, P, n, iters):
     from rltime_amd.history import PrioritizedReplayHistoryBuffer
     H = 512
     buf = PrioritizedReplayHistoryBuffer(
@@ -43,7 +42,7 @@ def run(nt, size, E, B, T, P, n, iters):
     torch.cuda.synchronize()
     ing_ms = e0.elapsed_time(e1) / steps
     ing_bytes = E * (4 * 84 * 84 + 2 * H * 4 + 16) * 2
-    out = {"nt": nt, "ingest_us_per_vector_step": ing_ms * 1e3,
+    out = {"ingest_us_per_vector_step": ing_ms * 1e3,
            "ingest_GBps_rw": ing_bytes / ing_ms / 1e6, "fill_wall_s": time.time() - t0}
     # whole get_train_data
     for _ in range(3):
@@ -104,24 +103,7 @@ def run(nt, size, E, B, T, P, n, iters):
     return out
 
 
-def sweep():
-    size = int(os.environ.get("PROBE_SIZE", 262144))
-    combos = [dict(V=0, O=0), dict(V=1, O=0), dict(V=1, O=1)]
-    for c in combos:
-        os.environ["MIRL_GATHER_VARIANT"] = str(c["V"])
-        os.environ["MIRL_GATHER_ORDER"] = str(c["O"])
-        r = run(1, size, 256, 512, 80, 40, 2, 10)
-        print(json.dumps({"combo": c, "get_train_data_ms": r["get_train_data_ms"],
-                          "frames_kernel_ms": r["frames_kernel_ms"],
-                          "frames_kernel_GBps": r["frames_kernel_GBps"]}), flush=True)
-
-
 if __name__ == "__main__":
-    if os.environ.get("PROBE_SWEEP"):
-        sweep()
-        sys.exit(0)
     size = int(os.environ.get("PROBE_SIZE", 262144))
     iters = int(os.environ.get("PROBE_ITERS", 10))
-    nts = [int(os.environ["PROBE_NT"])] if "PROBE_NT" in os.environ else [0, 1]
-    for nt in nts:
-        print(json.dumps(run(nt, size, 256, 512, 80, 40, 2, iters)), flush=True)
+    print(json.dumps(run(size, 256, 512, 80, 40, 2, iters)), flush=True)
