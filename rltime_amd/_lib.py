@@ -264,6 +264,16 @@ def check(rc, what=""):
     return rc
 
 
+def ptr(t):
+    """Tensor -> its device address as a c_void_p; None -> a null pointer."""
+    return C.c_void_p(t.data_ptr() if t is not None else None)
+
+
+def stream():
+    """torch's current HIP stream as the `stream` argument of every launch."""
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
 def device_count():
     return lib.mirl_device_count()
 

@@ -223,7 +223,6 @@ class Actor(ActingInterface):
         (actor.py:108-122), everything after the network in ONE launch
         (csrc/acting.hip k_actor_head) when the policy exposes its raw head outputs.
         `eps`: 0-dim float64 device tensor holding the base epsilon (None = greedy)."""
-        import ctypes as C
         pol = self._policy
         expl = self._exploration
         fused = getattr(self, "fused_head", True) and hasattr(pol, "actor_head_raw") and pol.is_cuda() \
@@ -234,7 +233,7 @@ class Actor(ActingInterface):
             if expl is not None:
                 actions, _ = expl.remap_with_eps_tensor(actions, eps, self._env_ids, self._action_space)
             return actions.to(torch.int32), pred["qvalues"].contiguous()
-        from rltime_amd._lib import lib, check
+        from rltime_amd._lib import lib, check, ptr as p, stream
         adv, val, n = pol.actor_head_raw(state, 1)
         adv = adv.contiguous()
         Z = getattr(pol, "num_atoms", None)                  # C51: A * Z outputs per row, Z per value row
@@ -251,19 +250,16 @@ class Actor(ActingInterface):
             rnd = torch.randint(0, self._action_space.n, (E,), device=dev)
             expo = expl._device_exponents(self._env_ids, dev)
             eps_min = float(expl.eps_min)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)   # noqa: E731
         if val is not None:
             val = val.contiguous()
         if Z:
             check(lib.mirl_actor_head_c51(E, A, Z, p(adv), A * Z, p(val), Z, p(pol.support),
-                                          p(eps) if expl is not None else C.c_void_p(None), p(expo), eps_min, p(u), p(rnd),
-                                          0, C.c_void_p(None), p(actions), p(qvalues), C.c_void_p(None),
-                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mirl_actor_head_c51")
+                                          p(eps if expl is not None else None), p(expo), eps_min, p(u), p(rnd),
+                                          0, None, p(actions), p(qvalues), None, stream()), "mirl_actor_head_c51")
             return actions, qvalues
         check(lib.mirl_actor_head(E, n, A, p(adv), p(val), val.shape[1] if val is not None else 0,
-                                  p(eps) if expl is not None else C.c_void_p(None), p(expo), eps_min, p(u), p(rnd),
-                                  p(actions), p(qvalues), C.c_void_p(None),
-                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mirl_actor_head")
+                                  p(eps if expl is not None else None), p(expo), eps_min, p(u), p(rnd),
+                                  p(actions), p(qvalues), None, stream()), "mirl_actor_head")
         return actions, qvalues
 
     def _fast_steps(self, iters):

@@ -6,15 +6,9 @@ The device actor never brings per-step data to the host, so the running
 accumulators live on the GPU (one fused launch per vector step, csrc/acting.hip)
 and finished episodes come back through an asynchronous, event-guarded copy: the
 acting loop never waits; statistics arrive one or two get_samples calls late."""
-import ctypes as C
-
 import torch
 
-from rltime_amd._lib import lib, check
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)
+from rltime_amd._lib import lib, check, ptr, stream
 
 
 class EpisodeTracker:
@@ -38,9 +32,9 @@ class EpisodeTracker:
             self.flush()
         r = self.row % self.ROWS
         check(lib.mirl_episode_track(
-            self.E, self.A, _p(rewards), _p(dones_u8), _p(actions_i32), _p(self.ep_reward), _p(self.ep_len),
-            _p(self.out_reward[r]), _p(self.out_len[r]), _p(self.action_counts),
-            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mirl_episode_track")
+            self.E, self.A, ptr(rewards), ptr(dones_u8), ptr(actions_i32), ptr(self.ep_reward), ptr(self.ep_len),
+            ptr(self.out_reward[r]), ptr(self.out_len[r]), ptr(self.action_counts), stream()),
+            "mirl_episode_track")
         self.row += 1
 
     def begin_step(self):

@@ -18,7 +18,7 @@ weight concatenations, rand / randint, fills).  Here one step is
                                                writes the LSTM product's input rows), [features | h] x [W_ih | W_hh]^T
                                                with the cell in the same launch, quantile embedding x features, hidden
                                                layers -> output shares, head with in-kernel Philox draws.  (Shapes those kernels do not cover keep the round-3 graph
-                                               of library calls, ~15 launches: MIRL_ACT_FUSED=0 forces it.)
+                                               of library calls, ~15 launches.)
 
 Everything that only depends on the weights (b_ih + b_hh, [W_ih | W_hh], the joint
 [last FC | dueling value-hidden] weights) is rebuilt once per get_samples call
@@ -39,18 +39,10 @@ import ctypes as C
 import numpy as np
 import torch
 
-from rltime_amd._lib import lib, check
+from rltime_amd._lib import lib, check, ptr, stream
 from rltime_amd.general.utils import deep_apply, quiet_gc
 from rltime_amd.models.torch.fused import conv_bias_relu, conv_u8_supported, cos_embed
 from rltime_amd.models.torch import gemm3
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class IngestedSamples:
@@ -190,18 +182,15 @@ class FastActingStep:
         self.out_b = torch.zeros(self.na + self.nq, **f32)
         self.adv_w = torch.zeros((self.na, h1), **f32)           # advantage stream alone (need_q=False)
         self.freq = (pol.embedding_range * np.pi).contiguous() if self.iqn else None
-        # the network's own kernels (csrc/actnet.hip), piece by piece where the shape is covered
-        # MIRL_ACT_FUSED: 0 = library calls only, 1 (default) = own kernels where they measured faster (conv layers and the
-        # quantile product at any batch; the LSTM step and the head's hidden layers at the acting batch of one rank of a
-        # multi-GPU job: <= 64 envs, <= 2048 quantile rows; profiles/r05_actnet_probe.jsonl), 2 = everything at any size
-        mode = os.environ.get("MIRL_ACT_FUSED", "1")
-        fused = mode != "0"
-        small = mode == "2" or E <= 64
+        # the network's own kernels (csrc/actnet.hip), piece by piece: each one wherever the library's *_supported query
+        # takes the shape and the size gate below holds — the conv layers and the quantile product at any batch, the LSTM
+        # step where mirl_act_lstm_supported says so, the head's hidden layers up to 2048 quantile rows (where they
+        # measured faster: profiles/r05_actnet_probe.jsonl).  Everything else stays on library calls.
         convs = list(self.cnn.layers)
         self.f_conv = False
         # (without a recurrent layer the features go to the head in the reference's (C, H, W) order: the shared conv path +
         # one reordering copy, models/torch/fused.conv_bias_relu — the same kernels under no_grad)
-        if fused and len(convs) == 3 and self.lstm is not None:          # any batch: 16-pixel tiles below ~100 frames, LDS-resident weights above
+        if len(convs) == 3 and self.lstm is not None:          # any batch: 16-pixel tiles below ~100 frames, LDS-resident weights above
             c2, c3 = convs[1], convs[2]
             h1o, w1o = self.y1.shape[2], self.y1.shape[3]
             k2, s2 = c2.kernel_size[0], c2.stride[0]
@@ -216,13 +205,13 @@ class FastActingStep:
                 self.w2p = torch.empty((64, k2 * k2 * c2.in_channels), **f32)
                 self.w3p = torch.empty((64, k3 * k3 * c3.in_channels), **f32)
                 self.conv_dims = (h1o, w1o, h2o, w2o, h3o, w3o)
-        self.f_lstm = fused and self.lstm is not None and bool(lib.mirl_act_lstm_supported(E, H, F + H))
+        self.f_lstm = self.lstm is not None and bool(lib.mirl_act_lstm_supported(E, H, F + H))
         D = int(self.freq.shape[0]) if self.iqn else 0
         # (the output layer in the hidden layer's epilogue selects on scalar Q values: not for C51's distributions)
-        self.f_head = fused and not self.c51 and (mode == "2" or E * self.N <= 2048) and self.fc.in_features == W and self.dueling \
+        self.f_head = not self.c51 and E * self.N <= 2048 and self.fc.in_features == W and self.dueling \
             and bool(lib.mirl_act_head_supported(E, self.N, W, D, h1 + hv, self.na + self.nq))
         # the quantile product as one launch at any batch (cos features + embedding product + ReLU + feature multiply)
-        self.f_embed = fused and self.iqn and W % 16 == 0 and D % 16 == 0 and 0 < D <= 64 and E * self.N <= (1 << 24)
+        self.f_embed = self.iqn and W % 16 == 0 and D % 16 == 0 and 0 < D <= 64 and E * self.N <= (1 << 24)
         self.xq = torch.empty((E * self.N, W), **f32) if self.f_embed else None      # quantile product rows
         if self.f_head:
             parts, pitch = C.c_int32(), C.c_int32()
@@ -238,15 +227,15 @@ class FastActingStep:
         self.eps_min = float(expl.eps_min) if expl is not None else 0.0
         self.last_obs = obs0
         # a frame-stack env produces its observations by the shift contract itself: de-duplicated
-        # storage can take the newest plane without re-verifying it (MIRL_DEDUP_VERIFY=1: whole stacks)
-        self.trusted_stack = bool(getattr(actor._vec_env, "frame_stack", False)) and os.environ.get("MIRL_DEDUP_VERIFY", "0") != "1"
+        # storage can take the newest plane without re-verifying it
+        self.trusted_stack = bool(getattr(actor._vec_env, "frame_stack", False))
         self.tracker = None
         self.graph = None
         # env steps that write static buffers with a fixed launch (capturable); the per-step fast path uses them too, so
         # that the rollout graph and the per-step path see the same env stream
         env = actor._vec_env
         self.env_into = bool(getattr(env, "supports_step_into", lambda: False)())
-        self.env_pre = self.env_into and hasattr(env, "step_into_args") and os.environ.get("MIRL_ACT_ENV_PRE", "1") != "0"
+        self.env_pre = self.env_into and hasattr(env, "step_into_args")
         if self.env_into:
             self.obs_buf = torch.empty_like(obs0)
             self.env_rewards = torch.zeros(E, **f32)
@@ -298,13 +287,13 @@ class FastActingStep:
     # -- pieces ------------------------------------------------------------------------------
     def _pre_args(self, tr, row, clip):
         rec = self.H > 0
-        return (self.H, self.A, _p(self.actions), _p(self.h) if rec else None, _p(self.c) if rec else None,
+        return (self.H, self.A, ptr(self.actions), ptr(self.h) if rec else None, ptr(self.c) if rec else None,
                 C.c_void_p(self.xh.data_ptr() + 4 * self.F) if rec else None, self.F + self.H,
-                _p(self.c_in) if rec else None, _p(self.state_pack) if rec else None, _p(self.initials),
-                _p(self.rewards), _p(self.dones), 1 if clip else 0,
-                _p(tr.ep_reward) if tr is not None else None, _p(tr.ep_len) if tr is not None else None,
-                _p(tr.out_reward[row]) if tr is not None else None, _p(tr.out_len[row]) if tr is not None else None,
-                _p(tr.action_counts) if tr is not None else None, _p(self.rng_step), 0xFFFFFFFFFFFFFFFF, _stream())
+                ptr(self.c_in) if rec else None, ptr(self.state_pack) if rec else None, ptr(self.initials),
+                ptr(self.rewards), ptr(self.dones), 1 if clip else 0,
+                ptr(tr.ep_reward) if tr is not None else None, ptr(tr.ep_len) if tr is not None else None,
+                ptr(tr.out_reward[row]) if tr is not None else None, ptr(tr.out_len[row]) if tr is not None else None,
+                ptr(tr.action_counts) if tr is not None else None, ptr(self.rng_step), 0xFFFFFFFFFFFFFFFF, stream())
 
     def _pre(self, rewards, dones_u8, track=True, clip=False, row=None):
         """row: the episode tracker's ring row (None: reserve the next one).  The step counter the in-kernel draws are
@@ -314,7 +303,7 @@ class FastActingStep:
             row = tr.begin_step()
         self.step_no += 1
         a = self._pre_args(tr, row, clip)
-        check(lib.mirl_actor_pre(self.E, a[0], a[1], _p(rewards), _p(dones_u8), *a[2:]), "mirl_actor_pre")
+        check(lib.mirl_actor_pre(self.E, a[0], a[1], ptr(rewards), ptr(dones_u8), *a[2:]), "mirl_actor_pre")
 
     def env_step_pre(self, clip=False, row=None):
         """env.step and the pre-step as ONE launch (csrc/acting.hip k_synth_env_step<true>): the workgroup that draws an
@@ -333,8 +322,8 @@ class FastActingStep:
         """packed=True: self.wpk still holds the current weights (packed by the call's re-selection)."""
         c1 = self.cnn.layers[0]
         so, sc, sh, sw = c1.weight.stride()
-        check(lib.mirl_conv1_u8_fwd_ex(obs.shape[0], obs.shape[2], obs.shape[3], _p(obs), _p(c1.weight), so, sc, sh, sw, _p(c1.bias),
-                                       float(self.cnn.scale), _p(self.wpk), _p(self.y1), 8 if packed else 0, _stream()),
+        check(lib.mirl_conv1_u8_fwd_ex(obs.shape[0], obs.shape[2], obs.shape[3], ptr(obs), ptr(c1.weight), so, sc, sh, sw, ptr(c1.bias),
+                                       float(self.cnn.scale), ptr(self.wpk), ptr(self.y1), 8 if packed else 0, stream()),
               "mirl_conv1_u8_fwd")
 
     def _body(self):
@@ -343,9 +332,9 @@ class FastActingStep:
         if self.f_conv:
             c2, c3 = self.cnn.layers[1], self.cnn.layers[2]
             h1o, w1o, h2o, w2o, h3o, w3o = self.conv_dims
-            check(lib.mirl_act_conv_fwd(2, E, h1o, w1o, _p(self.y1), _p(self.w2p), _p(c2.bias), _p(self.y2), h2o * w2o * 64, _stream()),
+            check(lib.mirl_act_conv_fwd(2, E, h1o, w1o, ptr(self.y1), ptr(self.w2p), ptr(c2.bias), ptr(self.y2), h2o * w2o * 64, stream()),
                   "mirl_act_conv_fwd")
-            check(lib.mirl_act_conv_fwd(3, E, h2o, w2o, _p(self.y2), _p(self.w3p), _p(c3.bias), _p(self.xh), F + H, _stream()),
+            check(lib.mirl_act_conv_fwd(3, E, h2o, w2o, ptr(self.y2), ptr(self.w3p), ptr(c3.bias), ptr(self.xh), F + H, stream()),
                   "mirl_act_conv_fwd")
         else:
             x = self.y1
@@ -354,14 +343,14 @@ class FastActingStep:
             ch, hh, ww = x.shape[1:]
             torch.as_strided(self.xh, (E, ch, hh, ww), (F + H, hh * ww, ww, 1)).copy_(x)   # NHWC -> the reference's (C, H, W) flatten
         if self.f_lstm:
-            check(lib.mirl_act_lstm_fwd(E, H, F + H, _p(self.xh), F + H, _p(self.wcat), _p(self.bias_sum), _p(self.c_in), _p(self.h),
-                                        _p(self.c), _p(self.lstm_ws), _stream()), "mirl_act_lstm_fwd")
+            check(lib.mirl_act_lstm_fwd(E, H, F + H, ptr(self.xh), F + H, ptr(self.wcat), ptr(self.bias_sum), ptr(self.c_in), ptr(self.h),
+                                        ptr(self.c), ptr(self.lstm_ws), stream()), "mirl_act_lstm_fwd")
         elif self.lstm is not None:
             torch.addmm(self.bias_sum, self.xh, self.wcat.t(), out=self.gates)
-            check(lib.mirl_lstm_cell_fwd(E, H, _p(self.gates), _p(self.c_in), None, None, None, _p(self.h), _p(self.c), _stream()),
+            check(lib.mirl_lstm_cell_fwd(E, H, ptr(self.gates), ptr(self.c_in), None, None, None, ptr(self.h), ptr(self.c), stream()),
                   "mirl_lstm_cell_fwd")
         greedy = self.expo is None
-        eps_p, expo_p = (None, None) if greedy else (_p(self.eps), _p(self.expo))
+        eps_p, expo_p = (None, None) if greedy else (ptr(self.eps), ptr(self.expo))
         feat = self.h if self.lstm is not None else self.xh       # (E, W) rows
         H = self.W                                                # from here on: the head's input width
         if self.f_embed:
@@ -370,19 +359,19 @@ class FastActingStep:
             if not self.in_kernel_taus:
                 taus = pol._draw_taus(E * N).contiguous()        # a test's tau_source replaces the draw
                 self._taus_keep = taus
-            check(lib.mirl_act_embed(E, N, H, int(self.freq.shape[0]), _p(feat), _p(self.freq), _p(taus), self.rng_seed, _p(self.rng_step),
-                                     _p(pol.quantile_layer.weight), _p(pol.quantile_layer.bias), _p(self.xq), None, _stream()), "mirl_act_embed")
+            check(lib.mirl_act_embed(E, N, H, int(self.freq.shape[0]), ptr(feat), ptr(self.freq), ptr(taus), self.rng_seed, ptr(self.rng_step),
+                                     ptr(pol.quantile_layer.weight), ptr(pol.quantile_layer.bias), ptr(self.xq), None, stream()), "mirl_act_embed")
             feat = self.xq
         elif self.iqn:
             if self.in_kernel_taus:
                 phi = torch.empty((E * N, self.freq.shape[0]), dtype=torch.float32, device=self.dev)
-                check(lib.mirl_cos_embed_rng(E * N, self.freq.shape[0], self.rng_seed, _p(self.rng_step), _p(self.freq), _p(phi),
-                                             None, _stream()), "mirl_cos_embed_rng")
+                check(lib.mirl_cos_embed_rng(E * N, self.freq.shape[0], self.rng_seed, ptr(self.rng_step), ptr(self.freq), ptr(phi),
+                                             None, stream()), "mirl_cos_embed_rng")
             else:                                            # a test's tau_source replaces the draw
                 phi = cos_embed(pol._draw_taus(E * N), self.freq)
             emb = torch._addmm_activation(pol.quantile_layer.bias, phi, pol.quantile_layer.weight.t(), use_gelu=False)
             if H % 4 == 0 and 256 % (H // 4) == 0:
-                check(lib.mirl_iqn_mul_fwd(E, N, H, _p(feat), _p(emb), _p(emb), _stream()), "mirl_iqn_mul_fwd")   # in place
+                check(lib.mirl_iqn_mul_fwd(E, N, H, ptr(feat), ptr(emb), ptr(emb), stream()), "mirl_iqn_mul_fwd")   # in place
             else:
                 emb = (emb.view(E, N, H) * feat.view(E, 1, H)).view(E * N, H)
             feat = emb
@@ -393,11 +382,11 @@ class FastActingStep:
             wout = self.out_w if self.need_q else self.adv_w
             parts, pitch = C.c_int32(), C.c_int32()
             check(lib.mirl_act_head_parts(hid, no, C.byref(parts), C.byref(pitch)))
-            check(lib.mirl_act_head_hidden(E * N, H, hid, no, _p(feat), _p(self.fc_w), _p(self.fc_b), _p(wout), _p(self.part), _stream()),
+            check(lib.mirl_act_head_hidden(E * N, H, hid, no, ptr(feat), ptr(self.fc_w), ptr(self.fc_b), ptr(wout), ptr(self.part), stream()),
                   "mirl_act_head_hidden")
             check(lib.mirl_act_head_select(
-                E, N, self.A, parts.value, pitch.value, _p(self.part), _p(self.out_b), 1 if self.need_q else 0,
-                eps_p, expo_p, self.eps_min, self.rng_seed, _p(self.rng_step), _p(self.actions), _p(self.qvalues), _stream()),
+                E, N, self.A, parts.value, pitch.value, ptr(self.part), ptr(self.out_b), 1 if self.need_q else 0,
+                eps_p, expo_p, self.eps_min, self.rng_seed, ptr(self.rng_step), ptr(self.actions), ptr(self.qvalues), stream()),
                 "mirl_act_head_select")
             return
         if use_val:
@@ -413,13 +402,13 @@ class FastActingStep:
             pitch, val = self.na, None
         if self.c51:
             check(lib.mirl_actor_head_c51(
-                E, self.A, self.Z, _p(outs), pitch, val, pitch, _p(pol.support), None if greedy else _p(self.eps),
-                None if greedy else _p(self.expo), self.eps_min, None, None, self.rng_seed, None if greedy else _p(self.rng_step),
-                _p(self.actions), _p(self.qvalues), None, _stream()), "mirl_actor_head_c51")
+                E, self.A, self.Z, ptr(outs), pitch, val, pitch, ptr(pol.support), None if greedy else ptr(self.eps),
+                None if greedy else ptr(self.expo), self.eps_min, None, None, self.rng_seed, None if greedy else ptr(self.rng_step),
+                ptr(self.actions), ptr(self.qvalues), None, stream()), "mirl_actor_head_c51")
             return
         check(lib.mirl_actor_head_rng(
-            E, N, self.A, _p(outs), pitch, val, pitch, None if greedy else _p(self.eps), None if greedy else _p(self.expo),
-            self.eps_min, self.rng_seed, None if greedy else _p(self.rng_step), _p(self.actions), _p(self.qvalues), None, _stream()),
+            E, N, self.A, ptr(outs), pitch, val, pitch, None if greedy else ptr(self.eps), None if greedy else ptr(self.expo),
+            self.eps_min, self.rng_seed, None if greedy else ptr(self.rng_step), ptr(self.actions), ptr(self.qvalues), None, stream()),
             "mirl_actor_head_rng")
 
     def _capture(self):

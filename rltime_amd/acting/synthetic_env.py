@@ -10,16 +10,11 @@ pre-generated pool, reward and done come from a Philox4x32-10 block per (seed, t
 env).  `step_into` writes caller-owned static buffers and can therefore be captured
 into a HIP graph of a whole acting rollout (acting/fast_step.py); `step_device` is the
 same kernel into fresh tensors."""
-import ctypes as C
-
 import numpy as np
 import torch
 
+from rltime_amd._lib import lib, check, ptr, stream
 from rltime_amd.spaces import Box, Discrete
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
 
 
 class SyntheticAtariVecEnv:
@@ -66,18 +61,17 @@ class SyntheticAtariVecEnv:
 
     def step_into(self, obs_out, rewards_out, dones_out):
         """obs_out uint8 [E, ...frame], rewards_out float32 [E], dones_out uint8 [E] <- step t = clock + 1."""
-        from rltime_amd._lib import lib, check
-        check(lib.mirl_synth_env_step(self.num_envs, self._row_bytes, _p(self._pool), self._pool.shape[0], _p(self._clock),
-                                      self._slot, self.seed, self._p_neg, self._p_nonpos, self.done_prob, _p(obs_out),
-                                      _p(rewards_out), _p(dones_out), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+        check(lib.mirl_synth_env_step(self.num_envs, self._row_bytes, ptr(self._pool), self._pool.shape[0], ptr(self._clock),
+                                      self._slot, self.seed, self._p_neg, self._p_nonpos, self.done_prob, ptr(obs_out),
+                                      ptr(rewards_out), ptr(dones_out), stream()),
               "mirl_synth_env_step")
         self._slot ^= 1
 
     def step_into_args(self, obs_out, rewards_out, dones_out):
         """The leading arguments of mirl_synth_env_step / mirl_synth_env_step_pre for the NEXT step (a caller that fuses
         the env step with its own work launches the kernel itself and then calls advance_host())."""
-        return (self.num_envs, self._row_bytes, _p(self._pool), self._pool.shape[0], _p(self._clock), self._slot, self.seed,
-                self._p_neg, self._p_nonpos, self.done_prob, _p(obs_out), _p(rewards_out), _p(dones_out))
+        return (self.num_envs, self._row_bytes, ptr(self._pool), self._pool.shape[0], ptr(self._clock), self._slot, self.seed,
+                self._p_neg, self._p_nonpos, self.done_prob, ptr(obs_out), ptr(rewards_out), ptr(dones_out))
 
     def advance_host(self):
         self._slot ^= 1
@@ -123,9 +117,8 @@ class SyntheticAtariVecEnv:
         plane = newest[0].numel()
         if self._stack.is_cuda and plane % 16 == 0:
             # roll by one plane, zero-fill on reset, append the new plane: one launch (csrc/acting.hip)
-            from rltime_amd._lib import lib, check
-            check(lib.mirl_stack_shift(self.num_envs, self._stack.shape[1], plane, _p(self._stack), _p(nxt), _p(newest),
-                                       _p(dones.view(torch.uint8)), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+            check(lib.mirl_stack_shift(self.num_envs, self._stack.shape[1], plane, ptr(self._stack), ptr(nxt), ptr(newest),
+                                       ptr(dones.view(torch.uint8)), stream()),
                   "mirl_stack_shift")
         else:
             keep = (~dones).to(torch.uint8).view(-1, 1, 1, 1)

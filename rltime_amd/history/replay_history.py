@@ -28,15 +28,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .._lib import lib, check
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)
+from .._lib import lib, check, ptr, stream
 
 
 def _host_example(state):
@@ -318,11 +310,11 @@ class ReplayHistoryBuffer(History):
             ids = np.ascontiguousarray(env_ids, dtype=np.int32)
         arg = _lib.Ingest(
             count=K, env_ids_host=_lib.np_ptr(ids) if ids is not None else None,
-            frames=_ptr(frames) if plane_ptr is None else C.c_void_p(plane_ptr), extra=_ptr(extra), state=_ptr(state),
-            initials=_ptr(initials), actions=_ptr(actions), policy=_ptr(policy),
-            rewards=_ptr(rewards), dones=_ptr(dones), newest_plane_only=1 if newest_plane_only else 0,
+            frames=ptr(frames) if plane_ptr is None else C.c_void_p(plane_ptr), extra=ptr(extra), state=ptr(state),
+            initials=ptr(initials), actions=ptr(actions), policy=ptr(policy),
+            rewards=ptr(rewards), dones=ptr(dones), newest_plane_only=1 if newest_plane_only else 0,
             frames_stride=plane_stride)
-        check(lib.mirl_replay_ingest(self._h, C.byref(arg), _stream()), "mirl_replay_ingest")
+        check(lib.mirl_replay_ingest(self._h, C.byref(arg), stream()), "mirl_replay_ingest")
         # the kernels read the payload asynchronously: tie its lifetime to the stream
         # (transient=True: the caller owns long-lived buffers it only rewrites in stream order)
         if not transient:
@@ -342,7 +334,7 @@ class ReplayHistoryBuffer(History):
         ingest_planned(k, ...) — from a captured graph, if the caller wants."""
         ids = np.ascontiguousarray(env_ids, dtype=np.int32) if env_ids is not None else None
         check(lib.mirl_replay_ingest_plan(self._h, int(steps), int(count), _lib.np_ptr(ids) if ids is not None else None,
-                                          _stream()), "mirl_replay_ingest_plan")
+                                          stream()), "mirl_replay_ingest_plan")
 
     def ingest_planned(self, step, frames, actions, rewards, dones, extra=None, state=None, initials=None, policy=None):
         """Device side of step `step` of the current plan: same payload contract as update_batch; the buffers must stay
@@ -353,10 +345,10 @@ class ReplayHistoryBuffer(History):
                 assert t.is_cuda and t.is_contiguous()
         assert frames.dtype == torch.uint8 and actions.dtype == torch.int32
         assert rewards.dtype == torch.float32 and dones.dtype == torch.uint8
-        arg = _lib.Ingest(count=K, env_ids_host=None, frames=_ptr(frames), extra=_ptr(extra), state=_ptr(state),
-                          initials=_ptr(initials), actions=_ptr(actions), policy=_ptr(policy), rewards=_ptr(rewards),
-                          dones=_ptr(dones), newest_plane_only=0, frames_stride=0)
-        check(lib.mirl_replay_ingest_planned(self._h, int(step), C.byref(arg), _stream()), "mirl_replay_ingest_planned")
+        arg = _lib.Ingest(count=K, env_ids_host=None, frames=ptr(frames), extra=ptr(extra), state=ptr(state),
+                          initials=ptr(initials), actions=ptr(actions), policy=ptr(policy), rewards=ptr(rewards),
+                          dones=ptr(dones), newest_plane_only=0, frames_stride=0)
+        check(lib.mirl_replay_ingest_planned(self._h, int(step), C.byref(arg), stream()), "mirl_replay_ingest_planned")
 
     def prime_stack(self, obs):
         """De-duplicated storage + newest-plane ingest: hand over the observation block the env's
@@ -364,7 +356,7 @@ class ReplayHistoryBuffer(History):
         assert self._dedup and self._h is not None and obs.is_contiguous()
         per_plane = obs[0, 0].numel()
         check(lib.mirl_replay_prime_stack(self._h, C.c_void_p(obs.data_ptr() + (obs.shape[1] - 1) * per_plane),
-                                          obs.shape[1] * per_plane, _stream()), "mirl_replay_prime_stack")
+                                          obs.shape[1] * per_plane, stream()), "mirl_replay_prime_stack")
 
     def configure(self, example_state, num_envs, env_base=0, policy_f32=0):
         """Create the shard up-front from one example ``next_state`` pytree
@@ -417,7 +409,7 @@ class ReplayHistoryBuffer(History):
         rc = check(lib.mirl_replay_sample(
             self._h, B, -1.0 if train_progress is None else float(train_progress),
             _lib.np_ptr(rng) if rng is not None else None, self._seed,
-            _ptr(slot), _ptr(env), _ptr(start), _ptr(loss_start), _ptr(weight), _ptr(stats), _stream()),
+            ptr(slot), ptr(env), ptr(start), ptr(loss_start), ptr(weight), ptr(stats), stream()),
             "mirl_replay_sample")
         if rc == _lib.MIRL_NEED_MORE:
             return None
@@ -459,12 +451,12 @@ class ReplayHistoryBuffer(History):
         weights = new("weights", (L, B), torch.float32) if per else None
         loss_idx = new("loss_idx", (L, B, 2), torch.int64) if per else None
         out = _lib.Batch(
-            frames=_ptr(frames), extra=_ptr(extra), state=_ptr(state),
-            initials=_ptr(initials), returns=_ptr(returns), nsteps=_ptr(nsteps),
-            masks=_ptr(masks), actions=_ptr(actions), policy=_ptr(policy),
-            weights=_ptr(weights), loss_indices=_ptr(loss_idx))
+            frames=ptr(frames), extra=ptr(extra), state=ptr(state),
+            initials=ptr(initials), returns=ptr(returns), nsteps=ptr(nsteps),
+            masks=ptr(masks), actions=ptr(actions), policy=ptr(policy),
+            weights=ptr(weights), loss_indices=ptr(loss_idx))
         check(lib.mirl_replay_gather(
-            self._h, B, _ptr(env), _ptr(start), _ptr(loss_start), _ptr(weight), C.byref(out), _stream()),
+            self._h, B, ptr(env), ptr(start), ptr(loss_start), ptr(weight), C.byref(out), stream()),
             "mirl_replay_gather")
 
         if self._overlapped:
@@ -641,7 +633,7 @@ class PrioritizedReplayHistoryBuffer(ReplayHistoryBuffer):
             return None
         dev = self.device
         root = torch.empty(2, dtype=torch.float64, device=dev)
-        check(lib.mirl_replay_tree_root(self._h, _ptr(root), _stream()), "mirl_replay_tree_root")
+        check(lib.mirl_replay_tree_root(self._h, ptr(root), stream()), "mirl_replay_tree_root")
         shard = dp.exchange_rows(root).contiguous()                 # (R, 2): sum of priorities, active sequences
         table = shard.cpu()                                         # the one host read of this path
         share = float(table[rank, 0]) / float(table[:, 0].sum())
@@ -656,8 +648,8 @@ class PrioritizedReplayHistoryBuffer(ReplayHistoryBuffer):
         stats = torch.zeros(4, dtype=torch.float64, device=dev)
         self._seed += 1
         rc = check(lib.mirl_replay_sample_global(
-            self._h, B, B * R, rows, rank, R, _ptr(shard), float(train_progress or 0.0), self._seed,
-            _ptr(slot), _ptr(env), _ptr(start), _ptr(loss_start), _ptr(raw), _ptr(stratum), _ptr(stats), _stream()),
+            self._h, B, B * R, rows, rank, R, ptr(shard), float(train_progress or 0.0), self._seed,
+            ptr(slot), ptr(env), ptr(start), ptr(loss_start), ptr(raw), ptr(stratum), ptr(stats), stream()),
             "mirl_replay_sample_global")
         if rc == _lib.MIRL_NEED_MORE:                               # cannot happen after the agreed readiness check
             raise _lib.MirlError("mirl_replay_sample_global disagreed with mirl_replay_sample_ready")
@@ -710,7 +702,7 @@ class PrioritizedReplayHistoryBuffer(ReplayHistoryBuffer):
         losses = losses.detach().to(self.device, torch.float32).reshape(-1).contiguous()
         assert indices.shape[0] == losses.shape[0]
         check(lib.mirl_replay_update_losses(
-            self._h, losses.shape[0], _ptr(indices), _ptr(losses), _stream()),
+            self._h, losses.shape[0], ptr(indices), ptr(losses), stream()),
             "mirl_replay_update_losses")
         s = torch.cuda.current_stream()
         indices.record_stream(s)

@@ -14,13 +14,14 @@ expressions; parity tests in tests/test_fused_gpu.py compare against those):
   conv_u8_bias_relu  the INPUT layer, relu(conv2d(x_u8 * scale, W) + b) (cnn.py:44-49),
                      straight from the replay's uint8 frames on the f32 MFMA pipe
                      (csrc/conv_in.hip): no converted copy of the frames, no separate
-                     bias / ReLU pass; backward = mask + bias-gradient pass and MIOpen's
-                     weight gradient on a conversion made there
+                     bias / ReLU pass; backward = the weight gradient from the same uint8
+                     frames, ReLU mask and bias gradient in that kernel
   cos_embed          IQN cosine features (iqn.py:78-81) in one kernel
   quantile_product   x[m] * relu(phi @ Wq^T + bq)[m, n] (iqn.py:82-102) with a
                      backward that never materialises g*x / g*emb / the mask
 """
 import ctypes as C
+import importlib
 import os
 
 import torch
@@ -29,25 +30,29 @@ import torch.nn.functional as F
 
 from . import gemm3
 
-_TAIL_WGRAD = os.environ.get("MIRL_TAIL_WGRAD", "1") != "0"
-_QP_EPILOGUE = os.environ.get("MIRL_QP_EPILOGUE", "1") != "0"
+_QP_EPILOGUE = True      # False: the embedding GEMM on the library, then the stand-alone feature-product kernel
 _CONV3 = os.environ.get("MIRL_CONV3", "1") != "0"
-# multiply-adds below which a conv layer's forward stays on MIOpen; MIRL_CONV3_MIN_WORK=0 forces every supported shape
+# multiply-adds below which a conv layer's forward stays on MIOpen; 0 takes every supported shape
 # (512 frames: 35 us against 70 / 54 for MIOpen + the bias / ReLU pass, 256 frames: 33 against 54 / 41 — tools/conv3_probe.py)
-_CONV3_MIN_WORK = int(os.environ.get("MIRL_CONV3_MIN_WORK", "400000000"))
+_CONV3_MIN_WORK = 400000000
 
 
 def _lib():
-    from rltime_amd import _lib as L
-    return L
+    return importlib.import_module("rltime_amd._lib")
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)
+_floats = {}
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def _scratch_floats(query):
+    """What the library's `query` entry point reports as a scratch buffer's size in floats: a compile-time constant of
+    the library, asked once."""
+    if query not in _floats:
+        L = _lib()
+        n = C.c_int64()
+        L.check(getattr(L.lib, query)(C.byref(n)), query)
+        _floats[query] = n.value
+    return _floats[query]
 
 
 def _pow2_quads(c):
@@ -62,21 +67,23 @@ def _fusable(*tensors):
 def bias_relu_rows_(y, bias, channels):
     """y viewed as (rows, channels) row-major <- relu(y + bias), in place."""
     L = _lib()
-    L.check(L.lib.mirl_bias_relu_rows(y.numel() // channels, channels, _p(y), _p(bias), _stream()), "mirl_bias_relu_rows")
+    L.check(L.lib.mirl_bias_relu_rows(y.numel() // channels, channels, L.ptr(y), L.ptr(bias), L.stream()), "mirl_bias_relu_rows")
     return y
 
 
 def relu_bwd_bias_rows(dy, y, channels):
     """-> (g = dy * (y > 0), db = column sums of g) for row-major (rows, channels) views."""
     L = _lib()
+    if dy.data_ptr() % 16:
+        dy = dy.clone()          # the kernel reads 16 bytes per lane: an upstream gradient off that grid is copied onto it
     rows = y.numel() // channels
     blocks = C.c_int32()
     L.check(L.lib.mirl_colsum_blocks(rows, channels, C.byref(blocks)))
     g = torch.empty_like(y)
     db = torch.empty(channels, dtype=torch.float32, device=y.device)
     partial = torch.empty((blocks.value, channels), dtype=torch.float32, device=y.device)
-    L.check(L.lib.mirl_relu_bwd_bias_rows(rows, channels, _p(dy), _p(y), _p(g), _p(db), _p(partial), blocks.value,
-                                          _stream()), "mirl_relu_bwd_bias_rows")
+    L.check(L.lib.mirl_relu_bwd_bias_rows(rows, channels, L.ptr(dy), L.ptr(y), L.ptr(g), L.ptr(db), L.ptr(partial), blocks.value,
+                                          L.stream()), "mirl_relu_bwd_bias_rows")
     return g, db
 
 
@@ -135,20 +142,17 @@ def conv3_bias_relu(x, weight, bias, stride, relu=True):
     y = torch.empty((n, f, (h - kh) // s + 1, (w - kw) // s + 1), dtype=torch.float32, device=x.device,
                     memory_format=torch.channels_last)
     b = bias.contiguous() if bias is not None else None
-    L.check(L.lib.mirl_conv3_fwd(n, h, w, c, f, kh, kw, s, _p(x), _p(wk), _p(b) if b is not None else None,
-                                 1 if relu else 0, _p(y), _stream()), "mirl_conv3_fwd")
+    L.check(L.lib.mirl_conv3_fwd(n, h, w, c, f, kh, kw, s, L.ptr(x), L.ptr(wk), L.ptr(b),
+                                 1 if relu else 0, L.ptr(y), L.stream()), "mirl_conv3_fwd")
     return y
 
 
 # no-grad conv layers 2-3 below the implicit GEMM's work threshold (the acting batch of the non-recurrent policies, whose
 # actor runs the generic graph): csrc/actnet.hip's kernels, one launch with bias + ReLU instead of MIOpen's fill + implicit
-# GEMM + the bias pass (32 frames: ~10 us against 25 / 19).  0: the library.
-_ACT_CONV = os.environ.get("MIRL_ACT_CONV", "1") != "0"
-
-
+# GEMM + the bias pass (32 frames: ~10 us against 25 / 19).
 def act_conv_layer(x, weight, bias, stride):
     """2 / 3 when csrc/actnet.hip's conv kernel of that layer takes this NHWC forward as stored, else 0."""
-    if not (_ACT_CONV and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and weight.dtype == torch.float32 and bias is not None
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and weight.dtype == torch.float32 and bias is not None
             and x.is_contiguous(memory_format=torch.channels_last) and weight.is_contiguous(memory_format=torch.channels_last)
             and stride[0] == stride[1] and weight.shape[2] == weight.shape[3] and bias.is_contiguous()
             and x.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0 and x.shape[0] > 0):
@@ -168,7 +172,7 @@ def act_conv_bias_relu(layer, x, weight, bias, stride):
     ho, wo = (h - k) // s + 1, (w - k) // s + 1
     y = torch.empty((n, f, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     # an NHWC weight's memory IS (Co, kh, kw, Ci): the kernel's tap-major operand without a copy
-    L.check(L.lib.mirl_act_conv_fwd(layer, n, h, w, _p(x), _p(weight), _p(bias), _p(y), ho * wo * f, _stream()), "mirl_act_conv_fwd")
+    L.check(L.lib.mirl_act_conv_fwd(layer, n, h, w, L.ptr(x), L.ptr(weight), L.ptr(bias), L.ptr(y), ho * wo * f, L.stream()), "mirl_act_conv_fwd")
     return y
 
 
@@ -218,11 +222,11 @@ class _ConvBiasReLU(torch.autograd.Function):
             (db if ctx.needs_input_grad[2] else None), None, None
 
 
-_CONV2_BWD = os.environ.get("MIRL_CONV2_BWD", "1") != "0"   # 0: MIOpen data gradient for the second conv layer
-# weight gradient of conv layers 2-3 on the bf16 pipe (csrc/conv_wrw.hip); 0: MIOpen.  Frame counts whose multiply-adds stay
-# below MIRL_CONV_WRW_MIN_WORK keep the library either way (launch-bound shapes)
-_CONV_WRW = os.environ.get("MIRL_CONV_WRW", "1") != "0"
-_CONV_WRW_MIN_WORK = int(os.environ.get("MIRL_CONV_WRW_MIN_WORK", str(1 << 31)))
+_CONV2_BWD = True   # False: MIOpen data gradient for the second conv layer
+# weight gradient of conv layers 2-3 on the bf16 pipe (csrc/conv_wrw.hip); False: MIOpen.  Frame counts whose multiply-adds
+# stay below _CONV_WRW_MIN_WORK keep the library either way (launch-bound shapes)
+_CONV_WRW = True
+_CONV_WRW_MIN_WORK = 1 << 31
 _wrw_scratch = {}
 
 
@@ -253,9 +257,11 @@ def conv_wgrad_b3(g, x, weight, stride):
         L.check(L.lib.mirl_conv_wrw_b3_scratch_bytes(c, f, kh, kw, C.byref(nbytes)), "mirl_conv_wrw_b3_scratch_bytes")
         scratch = _wrw_scratch[key] = torch.empty(nbytes.value, dtype=torch.uint8, device=x.device)
     dw = torch.empty((f, kh, kw, c), dtype=torch.float32, device=x.device)
-    L.check(L.lib.mirl_conv_wrw_b3(n, h, w, c, f, kh, kw, int(stride[0]), _p(x), _p(g), _p(scratch), scratch.numel(), _p(dw),
-                                   _stream()), "mirl_conv_wrw_b3")
+    L.check(L.lib.mirl_conv_wrw_b3(n, h, w, c, f, kh, kw, int(stride[0]), L.ptr(x), L.ptr(g), L.ptr(scratch), scratch.numel(), L.ptr(dw),
+                                   L.stream()), "mirl_conv_wrw_b3")
     return dw.permute(0, 3, 1, 2)                     # logical (F, C, KH, KW) with channels_last strides
+
+
 def conv2_bwd_data_supported(x, weight, stride, g):
     if not (g.is_contiguous(memory_format=torch.channels_last) and g.data_ptr() % 16 == 0
             and tuple(stride) == (2, 2) and weight.shape[2] == weight.shape[3]):
@@ -264,8 +270,7 @@ def conv2_bwd_data_supported(x, weight, stride, g):
                                                          x.shape[3], g.shape[2], g.shape[3]))
 
 
-_CONV3_BWD = os.environ.get("MIRL_CONV3_BWD", "1") != "0"   # 0: MIOpen data gradient for the third conv layer
-_c3_wpk_floats = None
+_CONV3_BWD = True   # False: MIOpen data gradient for the third conv layer
 
 
 def conv3_bwd_data_supported(x, weight, stride, g):
@@ -278,38 +283,27 @@ def conv3_bwd_data_supported(x, weight, stride, g):
 
 def conv3_bwd_data(g, weight, x_like):
     """d loss / d input of conv2d(x, weight, stride 1) for the (64 -> 64, k 3) layer; g is NHWC."""
-    global _c3_wpk_floats
     L = _lib()
-    if _c3_wpk_floats is None:
-        n = C.c_int64()
-        L.check(L.lib.mirl_conv3_bwd_data_wpk_floats(C.byref(n)), "mirl_conv3_bwd_data_wpk_floats")
-        _c3_wpk_floats = n.value
     dx = torch.empty_like(x_like, memory_format=torch.channels_last)
-    wpk = torch.empty(_c3_wpk_floats, dtype=torch.float32, device=g.device)
+    wpk = torch.empty(_scratch_floats("mirl_conv3_bwd_data_wpk_floats"), dtype=torch.float32, device=g.device)
     so, sc, sh, sw = weight.stride()
-    L.check(L.lib.mirl_conv3_bwd_data(g.shape[0], g.shape[2], g.shape[3], _p(g), _p(weight), so, sc, sh, sw, _p(wpk), wpk.numel(),
-                                      _p(dx), _stream()), "mirl_conv3_bwd_data")
+    L.check(L.lib.mirl_conv3_bwd_data(g.shape[0], g.shape[2], g.shape[3], L.ptr(g), L.ptr(weight), so, sc, sh, sw, L.ptr(wpk), wpk.numel(),
+                                      L.ptr(dx), L.stream()), "mirl_conv3_bwd_data")
     return dx
 
 
-# which matrix pipe the layer-2 data gradient runs on: "bf16" = exact three-way split, f32 results (default), "f32" = f32 MFMA
-_CONV2_BWD_PIPE = 0 if os.environ.get("MIRL_CONV2_BWD_PIPE", "bf16") == "f32" else 1
-_c2_wpk_floats = None
+# which matrix pipe the layer-2 data gradient runs on: 1 = bf16, exact three-way split, f32 results; 0 = f32 MFMA
+_CONV2_BWD_PIPE = 1
 
 
-def conv2_bwd_data(g, weight, x_like, pipe=None):
+def conv2_bwd_data(g, weight, x_like):
     """d loss / d input of conv2d(x, weight, stride 2) for the (32 -> 64, k 4) layer; g is NHWC."""
-    global _c2_wpk_floats
     L = _lib()
-    if _c2_wpk_floats is None:
-        n = C.c_int64()
-        L.check(L.lib.mirl_conv2_bwd_data_wpk_floats(C.byref(n)), "mirl_conv2_bwd_data_wpk_floats")
-        _c2_wpk_floats = n.value
     dx = torch.empty_like(x_like, memory_format=torch.channels_last)
-    wpk = torch.empty(_c2_wpk_floats, dtype=torch.float32, device=g.device)
+    wpk = torch.empty(_scratch_floats("mirl_conv2_bwd_data_wpk_floats"), dtype=torch.float32, device=g.device)
     so, sc, sh, sw = weight.stride()
-    L.check(L.lib.mirl_conv2_bwd_data_ex(g.shape[0], g.shape[2], g.shape[3], _p(g), _p(weight), so, sc, sh, sw, _p(wpk), wpk.numel(),
-                                         _p(dx), _CONV2_BWD_PIPE if pipe is None else pipe, _stream()), "mirl_conv2_bwd_data_ex")
+    L.check(L.lib.mirl_conv2_bwd_data_ex(g.shape[0], g.shape[2], g.shape[3], L.ptr(g), L.ptr(weight), so, sc, sh, sw, L.ptr(wpk), wpk.numel(),
+                                         L.ptr(dx), _CONV2_BWD_PIPE, L.stream()), "mirl_conv2_bwd_data_ex")
     return dx
 
 
@@ -327,15 +321,8 @@ def frames_to_f32_nhwc(x, scale):
     L = _lib()
     n, c, h, w = x.shape
     out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    L.check(L.lib.mirl_frames_to_f32_nhwc(n, c, h * w, _p(x), float(scale), _p(out), _stream()), "mirl_frames_to_f32_nhwc")
+    L.check(L.lib.mirl_frames_to_f32_nhwc(n, c, h * w, L.ptr(x), float(scale), L.ptr(out), L.stream()), "mirl_frames_to_f32_nhwc")
     return out
-
-
-def _wpk_floats():
-    need = C.c_int64()
-    L = _lib()
-    L.check(L.lib.mirl_conv1_u8_wpk_floats(C.byref(need)))
-    return need.value
 
 
 def conv_u8_supported(x, conv):
@@ -350,10 +337,6 @@ def conv_u8_supported(x, conv):
                                                    conv.kernel_size[0], conv.stride[0]))
 
 
-_U8_WRW = os.environ.get("MIRL_CONV1_WRW", "1") != "0"     # 0: MIOpen weight gradient on a converted copy
-_U8_WRW_MASK = os.environ.get("MIRL_CONV1_WRW_MASK", "1") != "0"   # 0: separate ReLU-mask + bias-gradient pass in front of it
-
-
 class _ConvU8BiasReLU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, scale, stride):
@@ -363,12 +346,12 @@ class _ConvU8BiasReLU(torch.autograd.Function):
         oh, ow = (h - k) // stride + 1, (w - k) // stride + 1
         y = torch.empty((n, f, oh, ow), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
         if n:
-            wpk = torch.empty(_wpk_floats(), dtype=torch.float32, device=x.device)
+            wpk = torch.empty(_scratch_floats("mirl_conv1_u8_wpk_floats"), dtype=torch.float32, device=x.device)
             so, sc, sh, sw = weight.stride()
             b = bias if bias.data_ptr() % 16 == 0 else bias.clone()
-            L.check(L.lib.mirl_conv1_u8_fwd(n, h, w, _p(x), _p(weight), so, sc, sh, sw, _p(b), float(scale), _p(wpk), _p(y),
-                                            _stream()), "mirl_conv1_u8_fwd")
-        ctx.scale, ctx.stride = scale, stride
+            L.check(L.lib.mirl_conv1_u8_fwd(n, h, w, L.ptr(x), L.ptr(weight), so, sc, sh, sw, L.ptr(b), float(scale), L.ptr(wpk), L.ptr(y),
+                                            L.stream()), "mirl_conv1_u8_fwd")
+        ctx.scale = scale
         ctx.save_for_backward(x, weight, y)
         return y
 
@@ -376,41 +359,27 @@ class _ConvU8BiasReLU(torch.autograd.Function):
     def backward(ctx, grad):
         x, weight, y = ctx.saved_tensors
         grad = grad.contiguous(memory_format=torch.channels_last)
-        if ctx.needs_input_grad[1] and _U8_WRW and _U8_WRW_MASK and x.shape[0] and grad.data_ptr() % 16 == 0:
+        if not (ctx.needs_input_grad[1] and x.shape[0]):
+            _, db = relu_bwd_bias_rows(grad, y, y.shape[1])
+            dw = torch.zeros_like(weight) if ctx.needs_input_grad[1] else None
+            return None, dw, (db if ctx.needs_input_grad[2] else None), None, None
+        # weight gradient from the uint8 frames (csrc/conv_in.hip): no float pixels anywhere
+        L = _lib()
+        n, _, h, w = x.shape
+        scratch = torch.empty(_scratch_floats("mirl_conv1_u8_wrw_scratch_floats"), dtype=torch.float32, device=x.device)
+        dw = torch.empty_like(weight)
+        so, sc, sh, sw = dw.stride()
+        if grad.data_ptr() % 16 == 0:
             # ReLU mask and bias gradient inside the weight-gradient kernel (this layer's input takes no gradient, so the
             # masked gradient itself is not needed anywhere else): one pass over dy, y and the uint8 frames
-            L = _lib()
-            n, _, h, w = x.shape
-            need = C.c_int64()
-            L.check(L.lib.mirl_conv1_u8_wrw_scratch_floats(C.byref(need)))
-            scratch = torch.empty(need.value, dtype=torch.float32, device=x.device)
-            dw = torch.empty_like(weight)
             db = torch.empty(weight.shape[0], dtype=torch.float32, device=x.device)
-            so, sc, sh, sw = dw.stride()
-            L.check(L.lib.mirl_conv1_u8_wrw_masked(n, h, w, _p(x), _p(grad), _p(y), float(ctx.scale), _p(scratch), _p(dw), so, sc, sh, sw,
-                                                   _p(db), _stream()), "mirl_conv1_u8_wrw_masked")
-            return None, dw, (db if ctx.needs_input_grad[2] else None), None, None
-        g, db = relu_bwd_bias_rows(grad, y, y.shape[1])
-        dw = None
-        if ctx.needs_input_grad[1] and _U8_WRW and x.shape[0]:
-            # weight gradient from the uint8 frames as well (csrc/conv_in.hip): no float pixels anywhere
-            L = _lib()
-            n, _, h, w = x.shape
-            need = C.c_int64()
-            L.check(L.lib.mirl_conv1_u8_wrw_scratch_floats(C.byref(need)))
-            scratch = torch.empty(need.value, dtype=torch.float32, device=x.device)
-            dw = torch.empty_like(weight)
-            so, sc, sh, sw = dw.stride()
-            L.check(L.lib.mirl_conv1_u8_wrw(n, h, w, _p(x), _p(g), float(ctx.scale), _p(scratch), _p(dw), so, sc, sh, sw,
-                                            _stream()), "mirl_conv1_u8_wrw")
-        elif ctx.needs_input_grad[1] and not x.shape[0]:
-            dw = torch.zeros_like(weight)
-        elif ctx.needs_input_grad[1]:
-            # library weight gradient: the only consumer of float pixels, converted here for
-            # the rows that take part in the backward only
-            xf = frames_to_f32_nhwc(x, ctx.scale)
-            _, dw, _ = torch.ops.aten.convolution_backward(
-                g, xf, weight, None, [ctx.stride, ctx.stride], [0, 0], [1, 1], False, [0, 0], 1, [False, True, False])
+            L.check(L.lib.mirl_conv1_u8_wrw_masked(n, h, w, L.ptr(x), L.ptr(grad), L.ptr(y), float(ctx.scale), L.ptr(scratch), L.ptr(dw), so, sc, sh, sw,
+                                                   L.ptr(db), L.stream()), "mirl_conv1_u8_wrw_masked")
+        else:
+            # an upstream gradient off the 16-byte grid: the mask + bias-gradient pass leaves an aligned masked gradient
+            g, db = relu_bwd_bias_rows(grad, y, y.shape[1])
+            L.check(L.lib.mirl_conv1_u8_wrw(n, h, w, L.ptr(x), L.ptr(g), float(ctx.scale), L.ptr(scratch), L.ptr(dw), so, sc, sh, sw,
+                                            L.stream()), "mirl_conv1_u8_wrw")
         return None, dw, (db if ctx.needs_input_grad[2] else None), None, None
 
 
@@ -425,7 +394,7 @@ def cos_embed(taus, freq):
     if D % 4 == 0 and _fusable(taus, freq) and taus.is_contiguous():
         L = _lib()
         out = torch.empty((taus.shape[0], D), dtype=torch.float32, device=taus.device)
-        L.check(L.lib.mirl_cos_embed(taus.shape[0], D, _p(taus), _p(freq), _p(out), _stream()), "mirl_cos_embed")
+        L.check(L.lib.mirl_cos_embed(taus.shape[0], D, L.ptr(taus), L.ptr(freq), L.ptr(out), L.stream()), "mirl_cos_embed")
         return out
     return torch.cos(freq * taus.unsqueeze(1))
 
@@ -481,7 +450,7 @@ class _QuantileProduct(torch.autograd.Function):
         else:
             emb = torch._addmm_activation(bias, phi, weight.t(), use_gelu=False)
             out = torch.empty_like(emb) if need else emb     # no-grad: multiply in place
-            L.check(L.lib.mirl_iqn_mul_fwd(M, n, Cf, _p(x), _p(emb), _p(out), _stream()), "mirl_iqn_mul_fwd")
+            L.check(L.lib.mirl_iqn_mul_fwd(M, n, Cf, L.ptr(x), L.ptr(emb), L.ptr(out), L.stream()), "mirl_iqn_mul_fwd")
         ctx.n = n
         ctx.save_for_backward(x, phi, weight, emb)
         ctx.link = _qp_announce(out, x, emb, n) if need else None
@@ -508,8 +477,8 @@ class _QuantileProduct(torch.autograd.Function):
                 dx = torch.empty_like(x)
                 db = torch.empty(Cf, dtype=torch.float32, device=x.device)
                 partial = torch.empty((blocks, Cf), dtype=torch.float32, device=x.device)
-                L.check(L.lib.mirl_iqn_mul_bwd(M, ctx.n, Cf, _p(grad), _p(emb), _p(x), _p(d_pre), _p(dx), _p(db), _p(partial),
-                                               blocks, _stream()), "mirl_iqn_mul_bwd")
+                L.check(L.lib.mirl_iqn_mul_bwd(M, ctx.n, Cf, L.ptr(grad), L.ptr(emb), L.ptr(x), L.ptr(d_pre), L.ptr(dx), L.ptr(db), L.ptr(partial),
+                                               blocks, L.stream()), "mirl_iqn_mul_bwd")
             else:
                 # feature widths the stand-alone kernel does not take (3136 = the conv stack's output without an FC layer in
                 # front of the product): only reached when no consumer ran this backward in its data-gradient GEMM
@@ -589,17 +558,17 @@ class _DuelingTail(torch.autograd.Function):
             db = torch.empty(width, dtype=torch.float32, device=both.device)
             partial = torch.empty((blocks.value, width), dtype=torch.float32, device=both.device)
             kw = max(ga.shape[1], gv.shape[1])
-            if kw <= 8 and _TAIL_WGRAD:
+            if kw <= 8:
                 # the output layers' weight gradients from the same pass over `both` (no (A | Q) x rows x H GEMMs)
                 dwj = torch.empty((kw, width), dtype=torch.float32, device=both.device)
                 partial_w = torch.empty((blocks.value, kw, width), dtype=torch.float32, device=both.device)
-                L.check(L.lib.mirl_dueling_tail_bwd_w(M, h1, width - h1, ga.shape[1], gv.shape[1], _p(ga), _p(gv), _p(wo), _p(wq),
-                                                      _p(both), _p(g), _p(db), _p(partial), blocks.value, _p(dwj), _p(partial_w),
-                                                      _stream()), "mirl_dueling_tail_bwd_w")
+                L.check(L.lib.mirl_dueling_tail_bwd_w(M, h1, width - h1, ga.shape[1], gv.shape[1], L.ptr(ga), L.ptr(gv), L.ptr(wo), L.ptr(wq),
+                                                      L.ptr(both), L.ptr(g), L.ptr(db), L.ptr(partial), blocks.value, L.ptr(dwj), L.ptr(partial_w),
+                                                      L.stream()), "mirl_dueling_tail_bwd_w")
                 dwo_dwq = (dwj[:ga.shape[1], :h1], dwj[:gv.shape[1], h1:])
             else:
-                L.check(L.lib.mirl_dueling_tail_bwd(M, h1, width - h1, ga.shape[1], gv.shape[1], _p(ga), _p(gv), _p(wo), _p(wq),
-                                                    _p(both), _p(g), _p(db), _p(partial), blocks.value, _stream()),
+                L.check(L.lib.mirl_dueling_tail_bwd(M, h1, width - h1, ga.shape[1], gv.shape[1], L.ptr(ga), L.ptr(gv), L.ptr(wo), L.ptr(wq),
+                                                    L.ptr(both), L.ptr(g), L.ptr(db), L.ptr(partial), blocks.value, L.stream()),
                         "mirl_dueling_tail_bwd")
         else:
             d_both = torch.empty_like(both)
@@ -625,7 +594,7 @@ class _DuelingTail(torch.autograd.Function):
                 link.done = gemm3.grad_input_qp(g, wj, link.emb, link.x)
                 link.placeholder = dx = torch.zeros(1, dtype=x.dtype, device=x.device).expand(x.shape)
             elif ctx.needs_input_grad[0]:
-                dx = gemm3.gemm(gemm3.NN, g, wj, weight_b=True)
+                dx = gemm3.gemm(gemm3.NN, g, wj)
             dwj = gemm3.gemm(gemm3.TN, g, x)
             dw1, dwv = dwj[:h1], dwj[h1:]
         else:

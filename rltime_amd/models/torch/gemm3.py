@@ -5,37 +5,28 @@ modules/lstm.py:60-81) and their autograd gradients; results are f32 GEMM result
 (tests/test_gemm3_gpu.py).  `enabled()` is the switch the callers consult: MIRL_GEMM3=0
 keeps the library path."""
 import ctypes as C
+import importlib
 import os
 
 import torch
 
 NT, NN, TN = 0, 1, 2
-# M*N*K below this stays on the library (launch-bound anyway).  MIRL_GEMM3_MIN_WORK=0 sends every product the
-# kernel takes through it (tests/test_e2e_gpu.py pins the reference trajectories that way).
-_MIN_WORK = int(os.environ.get("MIRL_GEMM3_MIN_WORK", str(1 << 31)))
+# M*N*K below this stays on the library (launch-bound anyway).  0 sends every product the kernel takes through it.
+_MIN_WORK = 1 << 31
 # NT / NN run one 256 x 256 output tile per workgroup over the whole K: with fewer than ~96 tiles most of the chip idles for
 # 0.104 us x K while the library's smaller tiles finish the product at ~120 TFLOP/s — 1024 x 1024 x 3136 (the 32-env acting
 # batch of the Rainbow-IQN head): 325 us here, 57 us there; break-even at M x N ~ 6e6 (profiles/r05_gemm3_small_m.jsonl).
-# Not applied when the work threshold is 0 (MIRL_GEMM3_MIN_WORK=0: everything the kernel takes goes through it).
-_MIN_AREA = int(os.environ.get("MIRL_GEMM3_MIN_AREA", "6000000"))
+# Not applied when the work threshold is 0 (everything the kernel takes goes through it).
+_MIN_AREA = 6000000
 _ws = {}
 
 
 def _lib():
-    from rltime_amd import _lib as L
-    return L
+    return importlib.import_module("rltime_amd._lib")
 
 
 def enabled():
     return os.environ.get("MIRL_GEMM3", "1") != "0"
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _rowmajor(t):
@@ -97,10 +88,8 @@ def joint_rows(tensors):
     return out
 
 
-def gemm(layout, a, b, bias=None, relu=False, out=None, weight_b=False):
-    """NT: a (M,K) @ b (N,K)^T [+ bias, ReLU];  NN: a (M,K) @ b (K,N);  TN: a (K,M)^T @ b (K,N).
-    weight_b: b is a weight (kept for the call sites; a pre-split cache of weight operands was measured slower and removed:
-    profiles/r04_gemm3_probe_presplit.jsonl)."""
+def gemm(layout, a, b, bias=None, relu=False, out=None):
+    """NT: a (M,K) @ b (N,K)^T [+ bias, ReLU];  NN: a (M,K) @ b (K,N);  TN: a (K,M)^T @ b (K,N)."""
     L = _lib()
     if layout == NT:
         M, K, N = a.shape[0], a.shape[1], b.shape[0]
@@ -116,9 +105,8 @@ def gemm(layout, a, b, bias=None, relu=False, out=None, weight_b=False):
         L.check(L.lib.mirl_gemm3_workspace_bytes(layout, M, N, K, C.byref(need)), "mirl_gemm3_workspace_bytes")
         wsb = need.value
         ws = _workspace(a.device, wsb)
-    L.check(L.lib.mirl_gemm3(layout, M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(out), out.stride(0),
-                             _p(bias) if bias is not None else None, 1 if relu else 0,
-                             _p(ws) if ws is not None else None, wsb, _stream()), "mirl_gemm3")
+    L.check(L.lib.mirl_gemm3(layout, M, N, K, L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), L.ptr(out), out.stride(0),
+                             L.ptr(bias), 1 if relu else 0, L.ptr(ws), wsb, L.stream()), "mirl_gemm3")
     return out
 
 
@@ -128,7 +116,7 @@ def gemm(layout, a, b, bias=None, relu=False, out=None, weight_b=False):
 def linear_fwd(x, w, bias=None, relu=False):
     """x (M,K) @ w (N,K)^T [+ bias] [ReLU]  (nn.Linear forward)."""
     if enabled() and supported(NT, x, w) and (bias is None or (bias.is_contiguous() and bias.dtype == torch.float32)):
-        return gemm(NT, x, w, bias, relu, weight_b=True)
+        return gemm(NT, x, w, bias, relu)
     if relu:
         return torch._addmm_activation(bias, x, w.t(), use_gelu=False) if bias is not None else torch.relu(x.mm(w.t()))
     return torch.addmm(bias, x, w.t()) if bias is not None else x.mm(w.t())
@@ -137,7 +125,7 @@ def linear_fwd(x, w, bias=None, relu=False):
 def grad_input(g, w):
     """g (M,N) @ w (N,K) -> (M,K): gradient w.r.t. a linear layer's input."""
     if enabled() and supported(NN, g, w):
-        return gemm(NN, g, w, weight_b=True)
+        return gemm(NN, g, w)
     return g.mm(w)
 
 
@@ -148,7 +136,7 @@ def grad_weight(g, x):
     return g.t().mm(x)
 
 
-_QP_BWD = os.environ.get("MIRL_GEMM3_QP_BWD", "1") != "0"   # 0: data gradient stored, then the separate feature-product backward pass
+_QP_BWD = True   # False: data gradient stored, then the separate feature-product backward pass
 
 
 def grad_input_qp_supported(g, w, emb, x, n):
@@ -170,8 +158,8 @@ def grad_input_qp(g, w, emb, x):
     dx = torch.empty((M // 32, K), dtype=torch.float32, device=g.device)
     part = torch.empty((rows.value, K), dtype=torch.float32, device=g.device)
     # NN form: the contraction runs over g's columns, the result is K wide
-    L.check(L.lib.mirl_gemm3_nn_qp(M, K, N, _p(g), g.stride(0), _p(w), w.stride(0), _p(emb), emb.stride(0), _p(x), x.stride(0),
-                                   _p(d_pre), d_pre.stride(0), _p(dx), dx.stride(0), _p(part), _stream()), "mirl_gemm3_nn_qp")
+    L.check(L.lib.mirl_gemm3_nn_qp(M, K, N, L.ptr(g), g.stride(0), L.ptr(w), w.stride(0), L.ptr(emb), emb.stride(0), L.ptr(x), x.stride(0),
+                                   L.ptr(d_pre), d_pre.stride(0), L.ptr(dx), dx.stride(0), L.ptr(part), L.stream()), "mirl_gemm3_nn_qp")
     return d_pre, dx, part.sum(0)
 
 
@@ -211,14 +199,14 @@ def quantile_product(x, phi, weight, bias, n, keep_embedding):
     R, K, N = phi.shape[0], phi.shape[1], weight.shape[0]
     out = torch.empty((R, N), dtype=torch.float32, device=phi.device)
     emb = torch.empty((R, N), dtype=torch.float32, device=phi.device) if keep_embedding else None
-    L.check(L.lib.mirl_gemm3_nt_mul(R, N, K, _p(phi), phi.stride(0), _p(weight), weight.stride(0), _p(out), out.stride(0),
-                                    _p(bias), 1, _p(x), x.stride(0), n.bit_length() - 1,
-                                    _p(emb) if emb is not None else None, N, _stream()), "mirl_gemm3_nt_mul")
+    L.check(L.lib.mirl_gemm3_nt_mul(R, N, K, L.ptr(phi), phi.stride(0), L.ptr(weight), weight.stride(0), L.ptr(out), out.stride(0),
+                                    L.ptr(bias), 1, L.ptr(x), x.stride(0), n.bit_length() - 1,
+                                    L.ptr(emb), N, L.stream()), "mirl_gemm3_nt_mul")
     return out, emb
 
 
 # ---- a wide layer + the narrow layer behind it in one pass (csrc/gemm3.hip mirl_gemm3_nt_head) ---------------------
-_HEAD = os.environ.get("MIRL_GEMM3_HEAD", "1") != "0"
+_HEAD = True   # False: the narrow layer as its own product behind the stored hidden activation
 
 
 def head_supported(x, w, bias, w2):
@@ -238,9 +226,9 @@ def linear_relu_head(x, w, bias, w2, bias2, keep_hidden):
     need = C.c_int64()
     L.check(L.lib.mirl_gemm3_head_workspace_bytes(M, N, C.byref(need)), "mirl_gemm3_head_workspace_bytes")
     ws = _workspace(x.device, need.value)
-    L.check(L.lib.mirl_gemm3_nt_head(M, N, K, _p(x), x.stride(0), _p(w), w.stride(0), _p(hidden) if hidden is not None else None, N,
-                                     _p(bias), 1, _p(pad), O, _p(bias2) if bias2 is not None else None, _p(out), O,
-                                     _p(ws), need.value, _stream()), "mirl_gemm3_nt_head")
+    L.check(L.lib.mirl_gemm3_nt_head(M, N, K, L.ptr(x), x.stride(0), L.ptr(w), w.stride(0), L.ptr(hidden), N,
+                                     L.ptr(bias), 1, L.ptr(pad), O, L.ptr(bias2), L.ptr(out), O,
+                                     L.ptr(ws), need.value, L.stream()), "mirl_gemm3_nt_head")
     return hidden, out
 
 

@@ -15,14 +15,12 @@ gradients of W_ih and W_hh are one GEMM each over all timesteps after the
 backward sweep.
 """
 import ctypes as C
+import os
 
 import torch
 
-from rltime_amd._lib import lib, check
+from rltime_amd._lib import lib, check, ptr, stream
 from . import gemm3
-
-
-import os
 
 # (A one-launch step kernel — recurrent GEMM on f32 MFMA with the cell in its epilogue — was built in round 2 and measured no
 # faster than GEMM + cell at B = H = 512 (18.8 vs 12.6 + 5.7 us): the gain is in keeping W_hh resident across steps, which the
@@ -37,11 +35,7 @@ _PERSISTENT = os.environ.get("MIRL_LSTM_PERSISTENT", "1") != "0"
 # 64 MB per step saturate the fabric — no better than the cell kernel + rocBLAS GEMM per step
 # (20.6 us inside the learner step; profiles/r03_lstm_probe_with_persistent_backward.jsonl).  It is
 # therefore the default for small per-GPU batches only (strong scaling: B = 64 per rank at 8 GPUs).
-_BWD_PERSISTENT_MAX_B = int(os.environ.get("MIRL_LSTM_BWD_PERSISTENT_MAX_B", "128"))
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)
+_BWD_PERSISTENT_MAX_B = 128
 
 
 def check_status(what="a persistent LSTM sweep"):
@@ -82,7 +76,7 @@ def _forward_sweep(gates, w, h0, c0, keep, need_grad):
     H = G // 4
     dev = gates.device
     out = torch.empty((T, B, H), dtype=torch.float32, device=dev)
-    st = _stream()
+    st = stream()
     if persistent_supported(T, B, H) and w.data_ptr() % 16 == 0:
         nbytes = C.c_int64()
         check(lib.mirl_lstm_seq_workspace_bytes(B, H, C.byref(nbytes)))
@@ -97,8 +91,8 @@ def _forward_sweep(gates, w, h0, c0, keep, need_grad):
             h_last = torch.empty((B, H), dtype=torch.float32, device=dev)
             c_last = torch.empty((B, H), dtype=torch.float32, device=dev)
         check(lib.mirl_lstm_seq_fwd(
-            T, B, H, _p(gates), _p(w), _p(h0), _p(c0), _p(keep), _p(out), _p(c_all), _p(hm), _p(cm),
-            _p(h_last), _p(c_last), 1 if need_grad else 0, _p(ws), st), "mirl_lstm_seq_fwd")
+            T, B, H, ptr(gates), ptr(w), ptr(h0), ptr(c0), ptr(keep), ptr(out), ptr(c_all), ptr(hm), ptr(cm),
+            ptr(h_last), ptr(c_last), 1 if need_grad else 0, ptr(ws), st), "mirl_lstm_seq_fwd")
         ws.record_stream(torch.cuda.current_stream())
         if need_grad:
             h_last, c_last = hm[T], cm[T]
@@ -112,14 +106,10 @@ def _forward_sweep(gates, w, h0, c0, keep, need_grad):
     for t in range(T):
         gates[t].addmm_(hm[t], wt)
         check(lib.mirl_lstm_cell_fwd(
-            B, H, _p(gates[t]), _p(cm[t]), _p(keep[t + 1]) if t + 1 < T else None,
-            _p(out[t]), _p(c_all[t]) if need_grad else None, _p(hm[t + 1]), _p(cm[t + 1]), st),
+            B, H, ptr(gates[t]), ptr(cm[t]), ptr(keep[t + 1] if t + 1 < T else None),
+            ptr(out[t]), ptr(c_all[t] if need_grad else None), ptr(hm[t + 1]), ptr(cm[t + 1]), st),
             "mirl_lstm_cell_fwd")
     return out, hm, cm, c_all, hm[T], cm[T]
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _backward_sweep(gates, c_all, cm, d_out, keep, w):
@@ -128,13 +118,13 @@ def _backward_sweep(gates, c_all, cm, d_out, keep, w):
     cell kernel + one recurrent GEMM per step."""
     T, B, G = gates.shape
     H = G // 4
-    st = _stream()
+    st = stream()
     if _PERSISTENT and T >= 2 and B <= _BWD_PERSISTENT_MAX_B and lib.mirl_lstm_seq_bwd_supported(T, B, H) \
             and w.data_ptr() % 16 == 0:
         nbytes = C.c_int64()
         check(lib.mirl_lstm_seq_bwd_workspace_bytes(B, H, C.byref(nbytes)))
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=gates.device)
-        check(lib.mirl_lstm_seq_bwd(T, B, H, _p(gates), _p(w), _p(c_all), _p(cm), _p(d_out), _p(keep), _p(ws), st),
+        check(lib.mirl_lstm_seq_bwd(T, B, H, ptr(gates), ptr(w), ptr(c_all), ptr(cm), ptr(d_out), ptr(keep), ptr(ws), st),
               "mirl_lstm_seq_bwd")
         ws.record_stream(torch.cuda.current_stream())
         return
@@ -142,8 +132,8 @@ def _backward_sweep(gates, c_all, cm, d_out, keep, w):
     dc_rec = torch.empty((B, H), dtype=torch.float32, device=gates.device)
     for t in range(T - 1, -1, -1):
         check(lib.mirl_lstm_cell_bwd(
-            B, H, _p(gates[t]), _p(c_all[t]), _p(cm[t]), _p(d_out[t]), _p(dh_rec), _p(dc_rec),
-            _p(keep[t + 1]) if t + 1 < T else None, 1 if t == T - 1 else 0, st),
+            B, H, ptr(gates[t]), ptr(c_all[t]), ptr(cm[t]), ptr(d_out[t]), ptr(dh_rec), ptr(dc_rec),
+            ptr(keep[t + 1] if t + 1 < T else None), 1 if t == T - 1 else 0, st),
             "mirl_lstm_cell_bwd")
         if t > 0:
             torch.mm(gates[t], w, out=dh_rec)

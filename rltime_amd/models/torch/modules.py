@@ -8,8 +8,6 @@ MI355X-first differences:
   * the LSTM sequence forward hoists the input projection of all timesteps into
     one GEMM and keeps only the recurrent GEMM in the time loop.
 """
-import os
-
 import numpy as np
 import torch
 import torch.nn as nn
@@ -47,8 +45,8 @@ class CNN(BaseModule):
         super().__init__()
         self.scale = scale
         self.channels_last = channels_last
-        # input layer straight from uint8 frames (csrc/conv_in.hip) when its shape is covered
-        self.direct_u8 = (os.environ.get("MIRL_CONV1_DIRECT", "1") != "0") if direct_u8 is None else bool(direct_u8)
+        # input layer straight from uint8 frames (csrc/conv_in.hip) when its shape is covered; None means True
+        self.direct_u8 = direct_u8 is None or bool(direct_u8)
         self.layers = nn.ModuleList()
         ch = inp_shape[0]
         h, w = inp_shape[1:]
@@ -154,7 +152,7 @@ class LSTM(BaseModule):
         self.last_state = None
         self.fused = True          # use the fused HIP sequence op on the GPU
         # NHWC conv output consumed in memory order with permuted W_ih columns instead of a transposing copy (_flat_input)
-        self.nhwc_input = os.environ.get("MIRL_LSTM_NHWC_INPUT", "1") != "0"
+        self.nhwc_input = True
         self._w_ih_nhwc = None     # (key, permuted W_ih) of the last no-grad pass
         init_weight(self.lstm_cell.weight_hh)
         init_weight(self.lstm_cell.weight_ih)

@@ -5,13 +5,13 @@ IS a torch.optim.Adam (same state: step / exp_avg / exp_avg_sq per parameter, sa
 lr handling); `step_clipped(clip)` runs norm -> clip -> update as k_adam_sqsum + k_adam_update instead of PyTorch's ~25-60
 small launches, and falls back to those (the caller's own clip + `step()`) for anything the kernels do not take."""
 import ctypes as C
+import importlib
 
 import torch
 
 
 def _lib():
-    from rltime_amd import _lib as L
-    return L
+    return importlib.import_module("rltime_amd._lib")
 
 
 def _dense_like(a, b):
@@ -78,12 +78,12 @@ class ClipAdam(torch.optim.Adam):
         ws = self._ws[1]
         out = torch.empty(2, dtype=torch.float32, device=dev)
         lr = group["lr"]
-        lr_dev = C.c_void_p(lr.data_ptr()) if torch.is_tensor(lr) and lr.is_cuda else None
+        lr_dev = L.ptr(lr) if torch.is_tensor(lr) and lr.is_cuda else None
         b1, b2 = group["betas"]
         L.check(L.lib.mirl_adam_clip_step(n, arr(params), arr(grads), arr(ms), arr(vs), arr(steps), numel,
                                           float(lr) if lr_dev is None else 0.0, lr_dev, float(b1), float(b2), float(group["eps"]),
-                                          float(clip) if clip is not None else 0.0, C.c_void_p(ws.data_ptr()), ws.numel(),
-                                          C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                          float(clip) if clip is not None else 0.0, L.ptr(ws), ws.numel(),
+                                          L.ptr(out), L.stream()),
                 "mirl_adam_clip_step")
         # the kernels wrote through raw pointers: move the version counters like the in-place tensor ops they replace
         # (the caches of derived weights — joint / permuted / packed copies, models/torch/gemm3.py — are keyed by them)

@@ -104,8 +104,6 @@ class DataParallel:
         self.host_group = host_group
         self._backend = dist.get_backend(group)
         self.timing = None      # a list: (start, end) HIP event pairs around the EXPOSED part of every gradient all-reduce (bench.py)
-        # bucketed all-reduce overlapped with the backward pass (MIRL_DP_OVERLAP=0: one blocking collective)
-        self.overlap = os.environ.get("MIRL_DP_OVERLAP", "1") != "0"
         self.buckets_overlapped = 0
         self._buckets, self._bucket_of, self._hooks = [], {}, []
 
@@ -161,7 +159,7 @@ class DataParallel:
         single blocking all-reduce of rounds 1-3."""
         params = [p for p in module.parameters() if p.requires_grad]
         groups = self._bucket_groups(module, params) if buckets == "auto" else None
-        if not groups or buckets in (None, 1) or not self.overlap:
+        if not groups or buckets in (None, 1):
             groups = [params]
         n = sum(p.numel() for p in params)
         flat = torch.zeros(n, dtype=params[0].dtype, device=params[0].device)

@@ -9,19 +9,9 @@ Reference arithmetic restated by the kernels:
   training/torch/iqn.py:77-120     IQN pairwise quantile-Huber loss
   training/torch/dist_dqn.py:30-97,99-142   C51 target projection and loss (csrc/c51.hip)
 """
-import ctypes as C
-
 import torch
 
-from .._lib import lib, check
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)
+from .._lib import lib, check, ptr, stream
 
 
 def _f32(t):
@@ -48,8 +38,8 @@ def q_target_dqn(q_target, q_select, returns, nsteps, masks, gamma, vf_eps=None)
     M, A = q_target.shape
     out = torch.empty(M, dtype=torch.float32, device=q_target.device)
     check(lib.mirl_q_target_dqn(
-        M, A, _p(q_target), _p(q_select), _p(_f32(returns)), _p(_f32(nsteps)),
-        _p(_f32(masks)), float(gamma), float(vf_eps or 0.0), _p(out), _stream()),
+        M, A, ptr(q_target), ptr(q_select), ptr(_f32(returns)), ptr(_f32(nsteps)),
+        ptr(_f32(masks)), float(gamma), float(vf_eps or 0.0), ptr(out), stream()),
         "mirl_q_target_dqn")
     return out
 
@@ -60,9 +50,9 @@ def q_target_iqn(z_target, z_select, returns, nsteps, masks, gamma, vf_eps=None)
     Ns = z_select.shape[1]
     out = torch.empty((M, Nt), dtype=torch.float32, device=z_target.device)
     check(lib.mirl_q_target_iqn(
-        M, Nt, Ns, A, _p(z_target), _p(z_select), _p(_f32(returns)),
-        _p(_f32(nsteps)), _p(_f32(masks)), float(gamma), float(vf_eps or 0.0),
-        _p(out), _stream()), "mirl_q_target_iqn")
+        M, Nt, Ns, A, ptr(z_target), ptr(z_select), ptr(_f32(returns)),
+        ptr(_f32(nsteps)), ptr(_f32(masks)), float(gamma), float(vf_eps or 0.0),
+        ptr(out), stream()), "mirl_q_target_iqn")
     return out
 
 
@@ -85,9 +75,9 @@ def q_target_c51(logits_target, logits_select, support, returns, nsteps, masks, 
     out = torch.empty((M, Z), dtype=torch.float32, device=logits_target.device)
     delta_z = float(vmax - vmin) / (Z - 1)          # dist_dqn.py:81, a Python float like the reference's
     check(lib.mirl_q_target_c51(
-        M, A, Z, _p(logits_target), _p(logits_select), _p(support), _p(_f32(returns)), _p(_f32(nsteps)),
-        _p(_f32(masks)), float(gamma), float(vmin), float(vmax), delta_z, _PROJECTIONS[projection], _p(out),
-        _stream()), "mirl_q_target_c51")
+        M, A, Z, ptr(logits_target), ptr(logits_select), ptr(support), ptr(_f32(returns)), ptr(_f32(nsteps)),
+        ptr(_f32(masks)), float(gamma), float(vmin), float(vmax), delta_z, _PROJECTIONS[projection], ptr(out),
+        stream()), "mirl_q_target_c51")
     return out
 
 
@@ -101,8 +91,8 @@ class _C51Loss(torch.autograd.Function):
         dx = torch.empty_like(xc)
         w = _f32(weights) if weights is not None else None
         check(lib.mirl_loss_c51(
-            M, A, Z, _p(xc), _p(actions.to(torch.int64).contiguous()), _p(_f32(targets)), _p(w),
-            _C51_MODES[mode], float(kappa), float(scale), _p(rows), _p(dx), _p(rep), _stream()), "mirl_loss_c51")
+            M, A, Z, ptr(xc), ptr(actions.to(torch.int64).contiguous()), ptr(_f32(targets)), ptr(w),
+            _C51_MODES[mode], float(kappa), float(scale), ptr(rows), ptr(dx), ptr(rep), stream()), "mirl_loss_c51")
         ctx.save_for_backward(dx)
         ctx.mark_non_differentiable(rep)
         return rows.sum() * scale, rep
@@ -123,9 +113,9 @@ class _DQNLoss(torch.autograd.Function):
         dq = torch.empty_like(qc)
         w = _f32(weights) if weights is not None else None
         check(lib.mirl_loss_dqn(
-            M, A, _p(qc), _p(actions.to(torch.int64).contiguous()), _p(_f32(targets)),
-            _p(w), float(kappa), 1 if mode == "mse" else 0, float(scale),
-            _p(rows), _p(dq), _p(td), _stream()), "mirl_loss_dqn")
+            M, A, ptr(qc), ptr(actions.to(torch.int64).contiguous()), ptr(_f32(targets)),
+            ptr(w), float(kappa), 1 if mode == "mse" else 0, float(scale),
+            ptr(rows), ptr(dq), ptr(td), stream()), "mirl_loss_dqn")
         ctx.save_for_backward(dq)
         ctx.mark_non_differentiable(td)
         return rows.sum() * scale, td
@@ -147,9 +137,9 @@ class _IQNLoss(torch.autograd.Function):
         dz = torch.empty_like(zc)
         w = _f32(weights) if weights is not None else None
         check(lib.mirl_loss_iqn(
-            M, N, Nt, A, _p(zc), _p(_f32(taus).reshape(M, N)),
-            _p(actions.to(torch.int64).contiguous()), _p(_f32(targets)), _p(w),
-            float(kappa), float(scale), _p(rows), _p(dz), _p(rep), _stream()),
+            M, N, Nt, A, ptr(zc), ptr(_f32(taus).reshape(M, N)),
+            ptr(actions.to(torch.int64).contiguous()), ptr(_f32(targets)), ptr(w),
+            float(kappa), float(scale), ptr(rows), ptr(dz), ptr(rep), stream()),
             "mirl_loss_iqn")
         ctx.save_for_backward(dz)
         ctx.mark_non_differentiable(rep)

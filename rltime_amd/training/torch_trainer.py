@@ -33,9 +33,9 @@ class TorchTrainer(MultiStepTrainer):
         # graph_learner_step (not in the reference): targets -> forward / backward -> clip -> Adam of one learner step as ONE
         # captured HIP graph (see _learner_step_graphed).  For the launch-bound T = 1 configs, where the ~150 launches of a
         # step cost more host time than GPU time; needs static batch buffers and a capturable optimizer, so it is decided
-        # here, before train_init.  MIRL_GRAPH_STEP=0 switches it off.
+        # here, before train_init.
         # ("no-capture": the same set-up — static batches, capturable Adam — with every step issued eagerly: the A/B of the tests)
-        self.graph_learner_step = bool(graph_learner_step) and os.environ.get("MIRL_GRAPH_STEP", "1") != "0"
+        self.graph_learner_step = bool(graph_learner_step)
         self._graph_capture = graph_learner_step != "no-capture"
         self._gstep = None
         super()._train(**kwargs)
@@ -139,8 +139,6 @@ class TorchTrainer(MultiStepTrainer):
             if self.clip_grad:
                 self.value_log.log("grad_norm_clipped", norms[1], group="train")
             return
-        if hasattr(opt, "why_not_fused") and os.environ.get("MIRL_CLIP_ADAM_WHY") == "1":
-            print("ClipAdam not used:", "dynamic clip" if self.clip_grad_dynamic_alpha is not None else opt.why_not_fused(), flush=True)
         params = [p for p in self.policy.parameters() if p.grad is not None]
         grads = [p.grad for p in params]
         norm = torch.linalg.vector_norm(torch.stack(torch._foreach_norm(grads, 2)), 2)
@@ -157,20 +155,12 @@ class TorchTrainer(MultiStepTrainer):
     def _check_sweeps(self):
         """A persistent LSTM sweep that gave up (csrc/lstm_seq.hip: bounded spin, non-finite state) sets a pinned host
         word.  Reading it only means something at a point the host is SYNCHRONISED with the sweeps it covers — the host
-        enqueues about a step ahead of the GPU.  Default: wait for the event recorded after the PREVIOUS step's backward
-        (the GPU still holds a whole step of queued work, so it never idles), then read: a failed step k raises before
-        step k+1's optimizer is enqueued and before anything of it is logged or checkpointed (policy_trainer.py checks
-        again behind its own synchronisation).  At the point of that raise step k's OWN update has already been applied
-        (the fused clip + Adam is enqueued right after this look, and a graphed step contains it): the weights and Adam
-        moments in memory are then invalid and the run must be restarted from its last checkpoint — which is intact,
-        because log rows and both kinds of checkpoint sit behind a synchronised check_status() (policy_trainer.py).
-        MIRL_STRICT_SWEEP_CHECK=1 waits for THIS step's backward instead — no invalid gradient can reach the optimizer
-        at all, at the price of a drained launch queue per step."""
+        enqueues about a step ahead of the GPU.  So: wait for the event recorded after the PREVIOUS step's backward (the
+        GPU still holds a whole step of queued work, so it never idles), then read.  A failed step k raises before step
+        k+1's optimizer is enqueued and before anything of it is logged or checkpointed; step k's own update has already
+        been applied by then, so the run restarts from its last checkpoint — intact, because log rows and checkpoints
+        sit behind a synchronised check_status() (policy_trainer.py)."""
         from rltime_amd.models.torch import lstm_seq
-        if os.environ.get("MIRL_STRICT_SWEEP_CHECK", "0") == "1":
-            torch.cuda.current_stream().synchronize()
-            lstm_seq.check_status()
-            return
         prev = getattr(self, "_backward_done", None)
         if prev is not None:
             prev.synchronize()

@@ -767,7 +767,7 @@ E2E_IQN = dict(
 
 
 # The same algorithm on a model whose layer shapes are the ones the round-3 HIP kernels take, so that the GPU test
-# can force EVERY hand-written product into this reference-pinned run (MIRL_GEMM3_MIN_WORK=0, MIRL_CONV3_MIN_WORK=0):
+# can force EVERY hand-written product into this reference-pinned run (gemm3._MIN_WORK = 0, fused._CONV3_MIN_WORK = 0):
 # (4,36,36) uint8 frames -> conv 32@8x8/4 (csrc/conv_in.hip, bf16 pipe) -> 64@4x4/2 -> 64@3x3/1 (csrc/conv3.hip,
 # conv_mid.hip data gradient) -> LSTM 512 (csrc/lstm_seq.hip persistent sweeps: H in {128,256,512}, B % 16 == 0)
 # -> quantile layer 64 -> 512 (gemm3 NT with the feature product in its epilogue) -> FC 128 | value-hidden 128

@@ -239,3 +239,75 @@ def test_masked_weight_gradient_equals_mask_pass_plus_weight_gradient(n, h, w, w
             assert float((db.double() - want_db).abs().max()) <= 1e-5 * max(float(want_db.abs().max()), 1.0)
         dw2, db2 = masked(dy, scale)
         assert torch.equal(dw, dw2) and torch.equal(db, db2)
+
+
+class _MisalignedGrad(torch.autograd.Function):
+    """Identity whose backward hands the incoming gradient on as a channels_last view that starts 4 bytes into a fresh
+    buffer: what an upstream op may legitimately produce, and what the masked weight-gradient kernel does not take."""
+
+    @staticmethod
+    def forward(ctx, y):
+        return y.view_as(y)
+
+    @staticmethod
+    def backward(ctx, grad):
+        n, c, h, w = grad.shape
+        buf = torch.empty(grad.numel() + 1, dtype=grad.dtype, device=grad.device)
+        view = buf.as_strided((n, c, h, w), (h * w * c, 1, w * c, c), 1)
+        view.copy_(grad)
+        assert view.data_ptr() % 16 == 4 and view.is_contiguous(memory_format=torch.channels_last)
+        return view
+
+
+@pytest.mark.parametrize("h,w", [(8, 8), (12, 16)])
+@pytest.mark.parametrize("integer", [True, False], ids=["integer", "real"])
+def test_input_layer_backward_with_a_misaligned_upstream_gradient(h, w, integer):
+    """_ConvU8BiasReLU.backward when the upstream gradient is not 16-byte aligned: the mask + bias-gradient pass
+    (k_relu_bwd_bias_rows) makes an aligned masked copy and mirl_conv1_u8_wrw follows, instead of the one masked kernel.
+    Small-integer frames, weights, bias and gradient make every partial sum exact in f32 in any order: dW and db are then
+    BIT-identical to the aligned backward's; real-valued operands are held to the 1e-4 bound."""
+    from rltime_amd import _lib
+    from rltime_amd.models.torch.fused import conv_u8_bias_relu, conv_u8_supported
+    g_ = torch.Generator(device="cuda").manual_seed(h * 100 + w + int(integer))
+    x = torch.randint(0, 8 if integer else 256, (2, 4, h, w), dtype=torch.uint8, device="cuda", generator=g_)
+    conv = nn.Conv2d(4, 32, 8, 4).cuda().to(memory_format=torch.channels_last)
+    oh, ow = (h - 8) // 4 + 1, (w - 8) // 4 + 1
+    with torch.no_grad():
+        if integer:
+            conv.weight.copy_(torch.randint(-2, 3, (32, 4, 8, 8), device="cuda", generator=g_).float())
+            conv.bias.copy_(torch.randint(-20, 21, (32,), device="cuda", generator=g_).float())
+            up = torch.randint(-3, 4, (2, 32, oh, ow), device="cuda", generator=g_).float()
+        else:
+            conv.bias.uniform_(-0.3, 0.3)
+            up = torch.randn(2, 32, oh, ow, device="cuda", generator=g_)
+    up = up.contiguous(memory_format=torch.channels_last)
+    scale = 1.0 if integer else 1.0 / 255.0
+    assert conv_u8_supported(x, conv)
+    res = []
+    for misaligned in (False, True):
+        conv.zero_grad(set_to_none=True)
+        y = conv_u8_bias_relu(x, conv, scale)
+        if misaligned:
+            y = _MisalignedGrad.apply(y)
+        loss = (y * up).sum()
+        torch.cuda.synchronize()
+        _lib.check(_lib.lib.mirl_profile_reset())
+        _lib.check(_lib.lib.mirl_profile_set(2))
+        try:
+            loss.backward()
+            torch.cuda.synchronize()
+            ran = {r["name"]: r["calls"] for r in _lib.profile_table()}
+        finally:
+            _lib.check(_lib.lib.mirl_profile_set(0))
+        # the masked kernel needs no separate mask pass; the fallback is exactly that pass in front of the unmasked kernel
+        assert bool(ran.get("k_relu_bwd_bias_rows")) == misaligned, ran
+        res.append((conv.weight.grad.clone(), conv.bias.grad.clone()))
+    (dw, db), (dw_m, db_m) = res
+    assert float(dw.abs().max()) > 0 and float(db.abs().max()) > 0
+    if integer:
+        assert torch.equal(dw_m, dw) and torch.equal(db_m, db)
+    else:
+        for got, want, what in ((dw_m, dw, "dW"), (db_m, db, "db")):
+            err = float((got - want).abs().max()) / float(want.abs().max())
+            print("%s: misaligned vs aligned %.3e of scale" % (what, err))
+            assert err <= 1e-4, (what, err)

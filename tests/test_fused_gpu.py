@@ -160,7 +160,8 @@ def test_dueling_tail_matches_separate_layers(rows, f, h1, hv, a, q):
 # two column-sum launches), "plain" = k_tail_bwd (9 .. 16), "torch" = neither (more outputs, or a joint width that is not 4 * 2^k)
 @pytest.mark.parametrize("rows,f,h1,hv,a,q,path", [
     (300, 64, 32, 32, 9, 1, "plain"), (300, 64, 32, 32, 16, 1, "plain"), (300, 64, 32, 32, 18, 1, "torch"),
-    (300, 64, 96, 32, 6, 1, "w"), (300, 64, 32, 96, 6, 1, "w"), (300, 64, 32, 16, 5, 3, "torch")])
+    (300, 64, 96, 32, 6, 1, "w"), (300, 64, 32, 96, 6, 1, "w"), (300, 64, 32, 16, 5, 3, "torch"),
+    (64, 64, 64, 64, 9, 1, "plain")])          # joint width 128: the arm that the outputs-per-branch test alone selects
 def test_dueling_tail_takes_each_backward_branch_and_is_right_on_it(rows, f, h1, hv, a, q, path):
     """The dispatch of _DuelingTail.backward: the profile table shows which kernel ran (both tail kernels report as
     k_tail_bwd; k_tail_bwd_w is followed by two k_colsum_partials launches, the plain kernel by one), and all eleven tensors

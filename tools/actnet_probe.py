@@ -57,7 +57,7 @@ if lib.mirl_act_lstm_supported(E, H, F + H):
     ws = torch.zeros((need.value + 3) // 4, dtype=torch.int32, device=dev)
     calls["lstm"] = lambda: check(lib.mirl_act_lstm_fwd(E, H, F + H, p(xh), F + H, p(wcat), p(bias), p(c_in), p(h), p(c), p(ws), st()))
 only = os.environ.get("PROBE_ONLY")
-res = {"E": E, "need_q": need_q, "dbg": os.environ.get("MIRL_ACT_DBG", "0")}
+res = {"E": E, "need_q": need_q}
 iters = 300
 for name, fn in calls.items():
     if only and name not in only.split(","):

@@ -31,7 +31,9 @@ def main():
         check(lib.mirl_conv1_u8_wrw_masked(n, 84, 84, p(x1), p(dy1), p(y1), 1 / 255., p(scratch), p(dw1), so, sc, sh, sw, p(db1), st))
     bw = lambda g, x, w, s, m: torch.ops.aten.convolution_backward(g, x, w, None, [s, s], [0, 0], [1, 1], False, [0, 0], 1, m)   # noqa: E731
     for _ in range(reps):
-        fused.conv2_bwd_data(g2, w2, x2, 1); fused.conv2_bwd_data(g2, w2, x2, 0)
+        for pipe in (0, 1):                       # f32 MFMA for comparison, then the split-bf16 default
+            fused._CONV2_BWD_PIPE = pipe
+            fused.conv2_bwd_data(g2, w2, x2)
         fused.conv3_bwd_data(g3, w3, x3); bw(g3, x3, w3, 1, [True, False, False])
         fused.conv_wgrad_b3(g2, x2, w2, (2, 2)); bw(g2, x2, w2, 2, [False, True, False])
         fused.conv_wgrad_b3(g3, x3, w3, (1, 1)); bw(g3, x3, w3, 1, [False, True, False])
