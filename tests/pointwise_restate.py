@@ -12,6 +12,7 @@ torch.optim.Adam and torch.nn.LSTMCell) and the GPU tests of csrc/qmath.hip, opt
   clip_grad_norm_ + Adam              torch_trainer.py:177-199, coef = min(clip / (norm + 1e-6), 1), bias corrections from
                                       each tensor's own step
   LSTM cell with state reset          models/torch/modules/lstm.py:83-116
+  LSTM time loop over T steps         the same lines: forward sweep and its backward (for csrc/lstm_seq.hip)
   actor head                          policies/torch/dqn.py:74-87,140-141, policies/torch/iqn.py, exploration/
                                       epsilon_greedy.py:74-100
   conv + ReLU, linear layers          models/torch/modules/cnn.py:43-50, dqn.py:50-66 (for csrc/actnet.hip)
@@ -168,6 +169,83 @@ def lstm_cell_bwd(gates, c_t, c_in, d_out=None, dh_rec=None, dc_rec=None, keep_n
     tc = torch.tanh(c_t)
     dc = (zero if first else dc_rec * k) + dh * o * (1 - tc * tc)
     return torch.cat([dc * g * i * (1 - i), dc * c_in * f * (1 - f), dc * i * (1 - g * g), dh * tc * o * (1 - o)], 1), dc * f
+
+
+# ---- LSTM time loop ----------------------------------------------------------------------------------------------------------
+def lstm_sweep_fwd(gx, w_hh, h0, c0, keep):
+    """The reference's time loop (modules/lstm.py:83-116) on given input projections: gx (T, B, 4H) = x W_ih^T + b, w_hh (4H, H),
+    h0 / c0 (B, H) the state before step 0, keep (T, B) = 1 - initials.  Step t multiplies the state by keep[t], then runs the cell.
+    -> (out (T, B, H), c_all (T, B, H), activated gates (T, B, 4H), hm, cm (T + 1, B, H)): hm[t] / cm[t] are the masked state
+    step t is given (hm[0] = h0 keep[0], hm[t + 1] = out[t] keep[t + 1]); row T is the final state, unmasked."""
+    T, B, _ = gx.shape
+    H = h0.shape[1]
+    hm, cm = gx.new_zeros(T + 1, B, H), gx.new_zeros(T + 1, B, H)
+    out, c_all, gates = gx.new_zeros(T, B, H), gx.new_zeros(T, B, H), torch.zeros_like(gx)
+    hm[0], cm[0] = h0 * keep[0].unsqueeze(1), c0 * keep[0].unsqueeze(1)
+    for t in range(T):
+        kn = keep[t + 1] if t + 1 < T else None
+        gates[t], out[t], c_all[t], hm[t + 1], cm[t + 1] = lstm_cell_fwd(gx[t] + hm[t] @ w_hh.t(), cm[t], kn)
+    return out, c_all, gates, hm, cm
+
+
+def lstm_sweep_bwd(gates, c_all, cm, d_out, keep, w_hh):
+    """gates: ACTIVATED (T, B, 4H); c_all (T, B, H); cm (T + 1, B, H) as lstm_sweep_fwd returns them; d_out (T, B, H) the gradient
+    of out, or None.  -> d loss / d pre-activation (T, B, 4H): the cell's backward from the last step to the first, with
+    dh_rec(t) = dgates(t + 1) @ w_hh and dc_rec(t) = d c_in(t + 1), both through keep[t + 1]."""
+    T = gates.shape[0]
+    dg = torch.zeros_like(gates)
+    dh_rec = dc_rec = None
+    for t in range(T - 1, -1, -1):
+        first = t == T - 1
+        dg[t], dc_rec = lstm_cell_bwd(gates[t], c_all[t], cm[t], None if d_out is None else d_out[t], dh_rec, dc_rec,
+                                      None if first else keep[t + 1], first)
+        dh_rec = dg[t] @ w_hh
+    return dg
+
+
+def selector_whh(seed, H):
+    """A (4H, H) recurrent matrix with ONE non-zero per row, +- 2^-e with e in 0..3: row gate * H + j reads column
+    k = (stride j + offset(gate)) mod H.  stride is odd, coprime to H and neither 1 nor -1 mod H (neighbouring hidden units do not
+    read neighbouring k); the offsets gate * (H / 4 + 1) differ, so the four gates of a hidden unit read four different k, and every
+    k is read by exactly one row of each gate.  The recurrent sum of a gate column is then ONE exact product (a pre-activation
+    carries a single rounding) and a backward dh_rec a four-term sum."""
+    assert H % 4 == 0 and H >= 16
+    g = torch.Generator().manual_seed(seed)
+    cands = (5, 7, 11, 13, 3)
+    stride = next(s for s in (cands[(seed + n) % 5] for n in range(5)) if math.gcd(s, H) == 1 and s % H not in (1, H - 1))
+    j = torch.arange(H)
+    w = torch.zeros(4 * H, H, dtype=torch.float64)
+    for gate in range(4):
+        k = (stride * j + gate * (H // 4 + 1)) % H
+        val = (2.0 * torch.randint(0, 2, (H,), generator=g).double() - 1) * 2.0 ** -torch.randint(0, 4, (H,), generator=g).double()
+        w[gate * H + j, k] = val
+    return w
+
+
+# float32 emulations (NumPy, CPU only) of the activation forms of csrc/lstm_seq.hip: exp as exp2 of the log2(e)-scaled argument,
+# every operation rounded to float32.  Correctly rounded where the hardware instructions are within 1 ulp: they are used to show
+# that a float32 evaluation of these forms stays inside the derived bounds of tests/test_lstm_seq_exact_gpu.py.
+_LOG2E_F32 = np.float32(1.4426950408889634)
+
+
+def _exp_f32(x):
+    with np.errstate(over="ignore", under="ignore"):
+        return np.exp2((x * _LOG2E_F32).astype(np.float64)).astype(np.float32)
+
+
+def sq_sigmoid_f32(x):
+    """1 / (1 + exp(-x))."""
+    x = np.asarray(x, dtype=np.float32)
+    with np.errstate(over="ignore"):
+        return (np.float32(1) / (np.float32(1) + _exp_f32(-x))).astype(np.float32)
+
+
+def sq_tanh_f32(x):
+    """1 - 2 / (exp(2x) + 1): cancels near 0, its error there is absolute."""
+    x = np.asarray(x, dtype=np.float32)
+    with np.errstate(over="ignore"):
+        r = (np.float32(1) / (_exp_f32(np.float32(2) * x) + np.float32(1))).astype(np.float32)
+    return (np.float32(1) - np.float32(2) * r).astype(np.float32)
 
 
 # ---- actor head --------------------------------------------------------------------------------------------------------------

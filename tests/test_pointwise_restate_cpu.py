@@ -2,13 +2,17 @@
 gradients equal float64 autograd of the plain expression, the Adam step equals clip_grad_norm_ + torch.optim.Adam, the cell
 equals torch.nn.LSTMCell with masked state and its autograd, the actor head equals the plain torch expression, the acting
 network's layers (conv + ReLU over channels-last frames, linear, quantile-embedding product, output shares) equal torch's in
-float64; and the dyadic operands of the bit-exact GPU tests keep every sum exact in float32 and hold the ties and kinks they promise."""
+float64; and the dyadic operands of the bit-exact GPU tests keep every sum exact in float32 and hold the ties and kinks they promise.
+The LSTM time loop (forward sweep and its backward) equals a torch.nn.LSTMCell loop with per-step resets and its autograd; the
+selector W_hh has the properties it promises; and the bounds of tests/test_lstm_seq_exact_gpu.py are kept by a float32 evaluation
+of the kernels' forms and broken by each of five planted single-step errors."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import qmath
 from tests import pointwise_restate as R
+from tests import test_lstm_seq_exact_gpu as SQ         # the sweeps' derived bounds and input families (imports no GPU code)
 
 F64 = torch.float64
 
@@ -386,3 +390,200 @@ def test_dyadic_head_parts_operands(E, N, A, has_val):
     if A >= 2:
         assert bool(((q == q.max(-1, keepdim=True).values).sum(-1) == 2).all()) and torch.equal(R.first_max(q), d["first"])
         assert torch.equal(R.first_max(q.float()), d["first"])
+
+
+# ---- LSTM time loop ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("T", [1, 2, 5])
+def test_sweep_equals_an_lstmcell_time_loop_with_resets_and_its_autograd(T):
+    g = _g(40 + T)
+    B, H = 6, 16
+    cell = torch.nn.LSTMCell(4 * H, H).double()
+    w = torch.randn(4 * H, H, generator=g, dtype=F64) * 0.4
+    with torch.no_grad():                                             # gates = gx + h W_hh^T: W_ih = I, no bias
+        cell.weight_ih.copy_(torch.eye(4 * H, dtype=F64)), cell.weight_hh.copy_(w)
+        cell.bias_ih.zero_(), cell.bias_hh.zero_()
+    gx = torch.randn(T, B, 4 * H, generator=g, dtype=F64).requires_grad_(True)
+    h0, c0 = torch.randn(B, H, generator=g, dtype=F64), torch.randn(B, H, generator=g, dtype=F64)
+    keep = (torch.rand(T, B, generator=g) > 0.3).double()
+    keep[:, 0], keep[:, 1] = 1.0, 1.0
+    keep[0, 0] = 0.0                                                  # a reset at step 0 ...
+    keep[T - 1, 1] = 0.0                                              # ... and one at step T - 1
+    hx, cx, outs, cs = h0, c0, [], []
+    for t in range(T):                                                # modules/lstm.py:84-103
+        hx, cx = hx * keep[t].unsqueeze(1), cx * keep[t].unsqueeze(1)
+        hx, cx = cell(gx[t], (hx, cx))
+        outs.append(hx), cs.append(cx)
+    out, c_all = torch.stack(outs), torch.stack(cs)
+    out_r, c_r, gates, hm, cm = R.lstm_sweep_fwd(gx.detach(), w, h0, c0, keep)
+    _close(out_r, out.detach()), _close(c_r, c_all.detach())
+    assert hm.shape == cm.shape == (T + 1, B, H)
+    assert torch.equal(hm[0], h0 * keep[0].unsqueeze(1)) and torch.equal(cm[0], c0 * keep[0].unsqueeze(1))
+    assert torch.equal(hm[1:T], out_r[:T - 1] * keep[1:].unsqueeze(2)) and torch.equal(cm[1:T], c_r[:T - 1] * keep[1:].unsqueeze(2))
+    assert torch.equal(hm[T], out_r[T - 1]) and torch.equal(cm[T], c_r[T - 1])
+    assert float(hm[0, 0].abs().max()) == 0.0 and (T == 1 or float(hm[T - 1, 1].abs().max()) == 0.0)
+    pre = gx.detach() + hm[:T] @ w.t()
+    _close(gates, torch.cat([torch.sigmoid(pre[..., :2 * H]), torch.tanh(pre[..., 2 * H:3 * H]), torch.sigmoid(pre[..., 3 * H:])], -1))
+    d_out = torch.randn(T, B, H, generator=g, dtype=F64)
+    (d_out * out).sum().backward()
+    _close(R.lstm_sweep_bwd(gates, c_r, cm, d_out, keep, w), gx.grad)
+    assert float(R.lstm_sweep_bwd(gates, c_r, cm, None, keep, w).abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("H", [16, 128, 256, 512])
+def test_selector_whh_keeps_its_promises(H):
+    for seed in (H, H + 1, H + 2, H + 3, H + 4):
+        w = R.selector_whh(seed, H)
+        nz = w != 0
+        assert w.shape == (4 * H, H) and bool((nz.sum(1) == 1).all()) and bool((nz.sum(0) == 4).all())
+        mags = set(w[nz].abs().tolist())
+        assert mags <= {1.0, 0.5, 0.25, 0.125} and len(mags) == 4 and bool((w[nz] > 0).any()) and bool((w[nz] < 0).any())
+        k = nz.int().argmax(1).view(4, H)                                 # k[gate, hidden unit]
+        for gate in range(4):
+            assert sorted(k[gate].tolist()) == list(range(H))             # every k is read by exactly one row of each gate
+        assert all(len(set(k[:, j].tolist())) == 4 for j in range(H))     # the four gates of a unit read four different k
+        step = set(((k[:, 1:] - k[:, :-1]) % H).reshape(-1).tolist())
+        assert len(step) == 1 and step.pop() not in (0, 1, H - 1)         # neighbouring units do not read neighbouring k
+        assert len(set((k[:, 0] % H).tolist())) == 4                      # a per-gate offset
+        # one exact product per gate column, a four-term sum per column of the backward contraction
+        h = torch.randn(7, H, generator=_g(seed))
+        assert torch.equal((h @ w.float().t()).double(), h.double() @ w.t())
+        assert float(((h.double() @ w.t()).abs() - h.double().abs() @ w.abs().t()).abs().max()) == 0.0
+
+
+def test_activation_emulations_follow_the_forms():
+    x = np.linspace(-30, 30, 4001).astype(np.float32)
+    assert R.sq_sigmoid_f32(x).dtype == np.float32 and R.sq_tanh_f32(x).dtype == np.float32
+    assert float(np.abs(R.sq_sigmoid_f32(x) - 1 / (1 + np.exp(-x.astype(np.float64)))).max()) <= 3e-7
+    assert float(np.abs(R.sq_tanh_f32(x) - np.tanh(x.astype(np.float64))).max()) <= 3e-7
+    big = np.array([-100, 100], dtype=np.float32)
+    assert R.sq_sigmoid_f32(big).tolist() == [0.0, 1.0] and R.sq_tanh_f32(big).tolist() == [-1.0, 1.0] and float(R.sq_tanh_f32(np.float32(0))) == 0.0
+    tiny = np.float32(3e-6)                                               # the form cancels: an absolute error of u-size, far above 2u |g|
+    assert abs(float(R.sq_tanh_f32(tiny)) - 3e-6) > 2 * 2.0 ** -24 * 3e-6
+
+
+def _one_step(H, family, seed, B=32):
+    """A step's inputs as the GPU test sends them (float32 values, rows 1-3 in reset, h with +-2 / +-3.5) and a keep_next."""
+    inp = SQ.sweep_inputs(1, B, H, family, seed)
+    k0 = inp["keep"][0].unsqueeze(1)
+    kn = (torch.rand(B, generator=_g(seed + 1)) > 0.3).float()
+    kn[0], kn[4], kn[5] = 1.0, 0.0, 0.0
+    return dict(gx=inp["gx"][0], w=inp["w"], h=inp["h0"] * k0, c_in=inp["c0"] * k0, kn=kn, n=inp["n"])
+
+
+def _ref_step(s, planted=None):
+    """The float64 step and its bound; `planted`: one of the five errors, in float64.  -> (values, bounds) per quantity."""
+    gx, w, h, c_in, kn = (s[k].double() for k in ("gx", "w", "h", "c_in", "kn"))
+    H = h.shape[1]
+    hh = h.clone()
+    if planted == "swapped":
+        hh[:, [3, H // 2 + 1]] = h[:, [H // 2 + 1, 3]]
+    if planted == "bit30":
+        word = s["h"][0, 1:2].clone()
+        assert 0 < abs(float(word)) < 2
+        hh[0, 1] = float((word.view(torch.int32) | 0x40000000).view(torch.float32))
+    pre = gx + hh @ w.t()
+    if planted == "dropped":
+        col = H + 5
+        k = int(w[col].abs().argmax())
+        pre[:, col] -= hh[:, k] * w[col, k]
+    gates, c, out, e_g, e_c, e_h = SQ.fwd_step_bound(pre, (hh.abs() @ w.abs().t()) if s["n"] else None, s["n"], c_in)
+    if planted == "i-f":
+        i, f, g, o = gates.chunk(4, 1)
+        c = i * c_in + f * g
+        out = o * torch.tanh(c)
+    k = kn.unsqueeze(1)
+    vals = dict(gates=gates, c=c, h=out, h_next=out * k, c_next=c if planted == "c-unmasked" else c * k)
+    return vals, dict(gates=e_g, c=e_c, h=e_h, h_next=e_h * k, c_next=e_c * k)
+
+
+def _f32_step(s):
+    """The step as the sweep kernels evaluate it, every operation in float32 (NumPy)."""
+    gx, w, h, c_in, kn = (s[k].numpy() for k in ("gx", "w", "h", "c_in", "kn"))
+    H = h.shape[1]
+    pre = h @ w.T + gx
+    assert pre.dtype == np.float32
+    i, f, o = R.sq_sigmoid_f32(pre[:, :H]), R.sq_sigmoid_f32(pre[:, H:2 * H]), R.sq_sigmoid_f32(pre[:, 3 * H:])
+    g = R.sq_tanh_f32(pre[:, 2 * H:3 * H])
+    c = f * c_in + i * g
+    out = o * R.sq_tanh_f32(c)
+    k = kn[:, None]
+    return {n: torch.from_numpy(np.ascontiguousarray(v)).double() for n, v in
+            dict(gates=np.concatenate([i, f, g, o], 1), c=c, h=out, h_next=out * k, c_next=c * k).items()}
+
+
+@pytest.mark.parametrize("family", SQ.FAMILIES)
+@pytest.mark.parametrize("H", [128, 512])
+def test_forward_bound_is_kept_by_a_float32_evaluation(H, family):
+    s = _one_step(H, family, 50 + H)
+    want, bound = _ref_step(s)
+    got = _f32_step(s)
+    for name in want:
+        err = (got[name] - want[name]).abs()
+        assert bool((err <= bound[name]).all()), (name, float((err / bound[name].clamp(min=1e-300)).max()))
+    # a pre-activation of the saturated kind: exact gates inside the same bound
+    s["gx"] = torch.where(torch.arange(4 * H) % 3 == 0, torch.tensor(-100.0), torch.tensor(100.0)).expand_as(s["gx"]).contiguous()
+    want, bound = _ref_step(s)
+    got = _f32_step(s)
+    assert set(got["gates"].reshape(-1).tolist()) == {0.0, 1.0, -1.0}
+    for name in want:
+        assert bool(((got[name] - want[name]).abs() <= bound[name]).all()), name
+
+
+@pytest.mark.parametrize("H,family,planted", [(512, "selector", p) for p in ("dropped", "swapped", "c-unmasked", "i-f", "bit30")]
+                         + [(128, "gaussian", p) for p in ("dropped", "swapped", "c-unmasked", "i-f", "bit30")] + [(512, "gaussian", "dropped")])
+def test_forward_bound_catches_a_planted_error(H, family, planted):
+    """One k-term dropped from one column's sum, two h columns swapped, keep applied to h but not to c, gates i and f exchanged,
+    one h word left with bit 30 set: each breaks the bound of at least one quantity of the step.  With the dense W at H = 512 the
+    summation-order term n u sum |h_k w_k| is about 3e-4 of a pre-activation: the dropped term here is the column's LARGEST weight
+    (about 0.2 |h_k|) and shows, a term below that size would hide behind it — such terms rest on the selector W, where the
+    one product is the whole sum and the bound is u |pre|."""
+    s = _one_step(H, family, 60 + H)
+    want, bound = _ref_step(s)
+    bad, _ = _ref_step(s, planted)
+    assert any(bool(((bad[name] - want[name]).abs() > bound[name]).any()) for name in want)
+
+
+def _f32_bwd(gates, c_all, cm, d_out, keep, w):
+    """The backward recurrence in float32 in the sweep kernel's order: partial dh of 64 gate columns (4 gates x 16 hidden units of a
+    column group) per owner, the 32 partials added in source order; tanhf correctly rounded."""
+    T, _, H4 = gates.shape
+    H = H4 // 4
+    cols = [np.array([g * H + 16 * cg + j for g in range(4) for j in range(16)]) for cg in range(H // 16)]
+    dg = np.zeros_like(gates)
+    dhr = dcr = None
+    for t in range(T - 1, -1, -1):
+        first = t == T - 1
+        i, f, g, o = (gates[t][:, n * H:(n + 1) * H] for n in range(4))
+        kn = np.float32(1) if first else keep[t + 1][:, None]
+        dh = d_out[t] + (np.float32(0) if first else dhr * kn)
+        tc = np.tanh(c_all[t].astype(np.float64)).astype(np.float32)
+        dc = (np.float32(0) if first else dcr * kn) + dh * o * (np.float32(1) - tc * tc)
+        one = np.float32(1)
+        dg[t] = np.concatenate([dc * g * i * (one - i), dc * cm[t] * f * (one - f), dc * i * (one - g * g), dh * tc * o * (one - o)], 1)
+        dcr = dc * f
+        dhr = np.zeros_like(dh)
+        for cs in cols:
+            dhr = dhr + dg[t][:, cs] @ w[cs, :]
+        assert dhr.dtype == np.float32 and dg.dtype == np.float32
+    return dg
+
+
+@pytest.mark.parametrize("family", SQ.FAMILIES)
+def test_backward_bound_is_kept_by_a_float32_evaluation_and_broken_by_a_misplaced_partial(family):
+    T, B, H = 4, 16, 512
+    inp = SQ.sweep_inputs(T, B, H, family, 70)
+    saved = [t.float() for t in R.lstm_sweep_fwd(*(inp[k].double() for k in ("gx", "w", "h0", "c0", "keep")))]      # what a forward launch saves
+    _, c_all, gates, _, cm = saved
+    d_out = torch.randn(T, B, H, generator=_g(71))
+    args = [t.double() for t in (gates, c_all, cm, d_out, inp["keep"], inp["w"])]
+    want, bound = SQ.bwd_sweep_bound(*args, n=4 if family == "selector" else 96)
+    _close(want, R.lstm_sweep_bwd(*args))
+    got = torch.from_numpy(_f32_bwd(*(t.numpy() for t in (gates, c_all, cm, d_out, inp["keep"], inp["w"])))).double()
+    err = (got - want).abs()
+    assert bool((err <= bound).all()), float((err / bound.clamp(min=1e-300)).max())
+    if family == "selector":
+        # two 16-unit blocks of dh_rec handed to each other's owner at one step: far outside the bound
+        w2 = args[5].clone()
+        w2[:, 0:16], w2[:, 16:32] = args[5][:, 16:32], args[5][:, 0:16]
+        bad = R.lstm_sweep_bwd(*args[:5], w2)
+        assert bool(((bad - want).abs() > bound).any())
