@@ -1,6 +1,6 @@
 """Float64 restatements of the pointwise arithmetic that decides what is learned, written from the reference's formulas
 (not from the kernels), for tests/test_pointwise_restate_cpu.py (which proves them against oracle/qmath.py, torch autograd,
-torch.optim.Adam and torch.nn.LSTMCell) and the GPU tests of csrc/qmath.hip, optim.hip, lstm.hip and k_actor_head:
+torch.optim.Adam and torch.nn.LSTMCell) and the GPU tests of csrc/qmath.hip, optim.hip, lstm.hip, acting.hip and convert.hip:
 
   value rescaling h / h^-1            rltime/training/torch/torch_trainer.py:46-78
   n-step target tail                  torch_trainer.py:96-147: h(ret + float32(gamma)^n * h^-1(v) * mask)
@@ -17,6 +17,9 @@ torch.optim.Adam and torch.nn.LSTMCell) and the GPU tests of csrc/qmath.hip, opt
                                       epsilon_greedy.py:74-100
   conv + ReLU, linear layers          models/torch/modules/cnn.py:43-50, dqn.py:50-66 (for csrc/actnet.hip)
   quantile embedding product          policies/torch/iqn.py:67-106: relu(cos(pi i tau) W^T + b) * features
+  acting pre-step, episode statistics acting/actor.py:124-131, modules/lstm.py:131-161, training/policy_trainer.py:75-136,252-254
+  frame-stack shift                   env_wrappers/common.py:141-178 under an auto-resetting vector env
+  synthetic env draws, frame -> f32   acting/synthetic_env.py; modules/cnn.py:44-45 (NumPy, exact: for csrc/acting.hip, convert.hip)
 
 Every function computes in the dtype of its inputs (call it with float64 tensors).  The module also holds the dyadic
 operand generators: operands for which every sum a kernel can form is a float32 number, so that float32 arithmetic in any
@@ -576,3 +579,100 @@ def target_dqn_cases():
 def actor_head_dyadic_cases():
     return [dict(seed=700 + 8 * i + 2 * j + d, E=(1, 3, 4, 5, 33)[(i + j + d) % 5], N=N, A=A, dueling=bool(d))
             for i, N in enumerate((1, 32, 64)) for j, A in enumerate((1, 8)) for d in (0, 1)]
+
+
+# ---- the acting step's bookkeeping and byte movers (csrc/acting.hip, convert.hip) ---------------------------------------------
+# NumPy: everything here is exact (bytes, integers, one float32 multiply or add per value), so the GPU tests compare whole
+# buffers bit for bit.  A function takes the buffers as they are BEFORE the step and returns them as they must be after it:
+# whatever it does not assign (guard rows, pitch gaps, NULL outputs) must come back unchanged.
+STEP_ADVANCE = 2 ** 64 - 1                   # include/mirl.h MIRL_STEP_ADVANCE
+
+
+def episode_track(rewards, dones, actions, A, ep_reward, ep_len, out_reward, out_len, action_counts):
+    """PolicyTrainer._track_rewards (policy_trainer.py:93-136, no monitor env) and _format_action_hist's counts (:75-91) for
+    one vector step of E envs: the RAW reward joins the env's running sum, kept in float32 one addition per step, the length
+    grows by one; where `done`, (sum, length) is reported and both restart at 0, elsewhere (0.0, 0) is reported.  An action
+    outside [0, A) is not counted; actions or action_counts None: no histogram.
+    -> (ep_reward, ep_len, out_reward, out_len, action_counts); each buffer may be longer than E."""
+    E = len(rewards)
+    ep_reward, ep_len, out_reward, out_len = ep_reward.copy(), ep_len.copy(), out_reward.copy(), out_len.copy()
+    for e in range(E):
+        total = np.float32(ep_reward[e]) + np.float32(rewards[e])
+        length = int(ep_len[e]) + 1
+        if dones[e]:
+            out_reward[e], out_len[e] = total, length
+            total, length = np.float32(0.0), 0
+        else:
+            out_reward[e], out_len[e] = np.float32(0.0), 0
+        ep_reward[e], ep_len[e] = total, length
+    if action_counts is not None:
+        action_counts = action_counts.copy()
+        if actions is not None:
+            for a in actions[:E]:
+                if 0 <= int(a) < A:
+                    action_counts[int(a)] += 1
+    return ep_reward, ep_len, out_reward, out_len, action_counts
+
+
+def actor_pre(rewards_raw, dones, H, h, c, xh, xh_pitch, c_in, state_pack, initials, rewards_out, dones_out, clip,
+              actions=None, A=0, ep_reward=None, ep_len=None, out_reward=None, out_len=None, action_counts=None,
+              rng_step=None, step=0):
+    """Between env.step and the policy forward (acting/actor.py:124-131, modules/lstm.py:131-161, policy_trainer.py:93-136,
+    :252-254).  Per env e with mask = 1 - done (float32): h_in = h * mask, c_in = c * mask (a reset keeps the sign of the
+    zero); xh[e * xh_pitch + j] = h_in (the [features | h] tail; xh points at its first column), state_pack[e] = [h_in | c_in],
+    initials = float(done), dones_out = uint8(done), rewards_out = np.sign(raw) when clip else raw; the episode statistics
+    on the RAW reward when ep_reward is given; rng_step[0] = step, or + 1 (mod 2^64) when step == STEP_ADVANCE.
+    Flat buffers in, a dict of the same buffers after the step out (None stays None)."""
+    E = len(rewards_raw)
+    done = np.array([1 if d else 0 for d in dones[:E]], dtype=np.uint8)
+    out = {k: (None if v is None else v.copy()) for k, v in dict(
+        xh=xh, c_in=c_in, state_pack=state_pack, initials=initials, rewards_out=rewards_out, dones_out=dones_out,
+        ep_reward=ep_reward, ep_len=ep_len, out_reward=out_reward, out_len=out_len, action_counts=action_counts,
+        rng_step=rng_step).items()}
+    if H > 0:
+        mask = (np.float32(1.0) - done.astype(np.float32))[:, None]
+        h_in = h[:E * H].reshape(E, H) * mask
+        cc = c[:E * H].reshape(E, H) * mask
+        for e in range(E):
+            out["xh"][e * xh_pitch:e * xh_pitch + H] = h_in[e]
+        out["c_in"][:E * H] = cc.reshape(-1)
+        out["state_pack"][:2 * E * H] = np.concatenate([h_in, cc], axis=1).reshape(-1)
+    out["initials"][:E] = done.astype(np.float32)
+    out["dones_out"][:E] = done
+    raw = np.asarray(rewards_raw, dtype=np.float32)
+    out["rewards_out"][:E] = np.sign(raw) if clip else raw
+    if ep_reward is not None:
+        (out["ep_reward"], out["ep_len"], out["out_reward"], out["out_len"], out["action_counts"]) = episode_track(
+            raw, done, actions, A, ep_reward, ep_len, out_reward, out_len, action_counts)
+    if rng_step is not None:
+        out["rng_step"][0] = (int(rng_step[0]) + 1) % 2 ** 64 if step == STEP_ADVANCE else step
+    return out
+
+
+def stack_shift(inp, newest, dones):
+    """The frame-stack wrapper under an auto-resetting vector env (env_wrappers/common.py:141-178): inp (E, P, ...) uint8,
+    newest (E, ...), dones (E,) -> out[e] = [inp[e][1:], or zeros when done[e]; newest[e]]."""
+    out = np.empty_like(inp)
+    for e in range(inp.shape[0]):
+        out[e, :-1] = 0 if dones[e] else inp[e, 1:]
+        out[e, -1] = newest[e]
+    return out
+
+
+def synth_env_draws(seed, t, E, p_neg, p_nonpos, p_done, pool_n=1):
+    """Step t of the synthetic env (acting/synthetic_env.py): one Philox block per env keyed (seed ^ 0xE17, t, e); u0, u1 =
+    the top 24 bits of words 0 and 1 over 2^24; reward -1 where u0 < p_neg, else 0 where u0 < p_nonpos, else +1; done
+    where u1 < p_done (the thresholds as float32, both comparisons strict); the observation is pool batch t % pool_n.
+    -> (rewards float32 (E,), dones uint8 (E,), pool index, u0, u1)."""
+    w = [philox_4x32(seed ^ 0xE17, t, e) for e in range(E)]
+    u0 = np.array([(x[0] >> 8) / 16777216.0 for x in w], dtype=np.float32)
+    u1 = np.array([(x[1] >> 8) / 16777216.0 for x in w], dtype=np.float32)
+    p_neg, p_nonpos, p_done = np.float32(p_neg), np.float32(p_nonpos), np.float32(p_done)
+    rewards = np.where(u0 < p_neg, -1.0, np.where(u0 < p_nonpos, 0.0, 1.0)).astype(np.float32)
+    return rewards, (u1 < p_done).astype(np.uint8), t % pool_n, u0, u1
+
+
+def frames_to_f32_nhwc(x, scale):
+    """The CNN's input conversion (models/torch/modules/cnn.py:44-45) into channels-last: x (N, C, HW) uint8 ->
+    (N, HW, C) float32 = float32(x) * float32(scale), one rounding per value."""
+    return np.ascontiguousarray(x.transpose(0, 2, 1)).astype(np.float32) * np.float32(scale)

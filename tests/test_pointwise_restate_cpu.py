@@ -5,7 +5,9 @@ network's layers (conv + ReLU over channels-last frames, linear, quantile-embedd
 float64; and the dyadic operands of the bit-exact GPU tests keep every sum exact in float32 and hold the ties and kinks they promise.
 The LSTM time loop (forward sweep and its backward) equals a torch.nn.LSTMCell loop with per-step resets and its autograd; the
 selector W_hh has the properties it promises; and the bounds of tests/test_lstm_seq_exact_gpu.py are kept by a float32 evaluation
-of the kernels' forms and broken by each of five planted single-step errors."""
+of the kernels' forms and broken by each of five planted single-step errors.
+The acting step's bookkeeping (pre-step, episode statistics, frame-stack shift, synthetic env draws, frame conversion) gives the
+arrays worked out by hand for small cases, and the stack shift equals the synthetic env's torch expression of it."""
 import numpy as np
 import pytest
 import torch
@@ -587,3 +589,160 @@ def test_backward_bound_is_kept_by_a_float32_evaluation_and_broken_by_a_misplace
         w2[:, 0:16], w2[:, 16:32] = args[5][:, 16:32], args[5][:, 0:16]
         bad = R.lstm_sweep_bwd(*args[:5], w2)
         assert bool(((bad - want).abs() > bound).any())
+
+
+# ---- the acting step's bookkeeping (csrc/acting.hip): hand-worked cases, every expected array written out ------------------------
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
+
+
+def _f(*v):
+    return np.array(v, dtype=np.float32)
+
+
+def _i(*v):
+    return np.array(v, dtype=np.int32)
+
+
+def test_episode_track_on_a_hand_worked_stream():
+    """E = 3, A = 3, four steps.  Env 0: an episode ends mid-stream (step 1) and the next one starts from 0; env 1: done on the
+    very first step; env 2: every reward is -0.0 and its accumulator starts at -0.0 (-0.0 + -0.0 = -0.0 is reported, the restart
+    is +0.0 and +0.0 + -0.0 = +0.0).  Actions -1 and A = 3 are not counted."""
+    A = 3
+    steps = [  # rewards, dones, actions -> ep_reward, ep_len, out_reward, out_len, action_counts
+        (_f(1.0, 0.25, -0.0), [0, 1, 0], _i(-1, 3, 1), _f(1.0, 0.0, -0.0), _i(1, 0, 1), _f(0.0, 0.25, 0.0), _i(0, 1, 0), _i(0, 1, 0)),
+        (_f(2.0, -1.0, -0.0), [1, 0, 1], _i(0, 2, 2), _f(0.0, -1.0, 0.0), _i(0, 1, 0), _f(3.0, 0.0, -0.0), _i(2, 0, 2), _i(1, 1, 2)),
+        (_f(-0.5, -0.0, -0.0), [0, 0, 0], _i(1, 1, 1), _f(-0.5, -1.0, 0.0), _i(1, 2, 1), _f(0.0, 0.0, 0.0), _i(0, 0, 0), _i(1, 4, 2)),
+        (_f(4.0, 1.0, 0.0), [0, 1, 0], _i(3, -1, 0), _f(3.5, 0.0, 0.0), _i(2, 0, 2), _f(0.0, 0.0, 0.0), _i(0, 3, 0), _i(2, 4, 2)),
+    ]
+    epr, epl, counts = _f(0.0, 0.0, -0.0), _i(0, 0, 0), _i(0, 0, 0)
+    outr, outl = _f(9.0, 9.0, 9.0), _i(9, 9, 9)
+    for k, (r, d, a, w_epr, w_epl, w_outr, w_outl, w_counts) in enumerate(steps):
+        before = (epr.copy(), epl.copy(), counts.copy())
+        epr, epl, outr, outl, counts = R.episode_track(r, d, a, A, epr, epl, outr, outl, counts)
+        assert np.array_equal(_bits(epr), _bits(w_epr)) and np.array_equal(epl, w_epl), k
+        assert np.array_equal(_bits(outr), _bits(w_outr)) and np.array_equal(outl, w_outl), k
+        assert np.array_equal(counts, w_counts), k
+        assert epr.dtype == np.float32 and epl.dtype == np.int32 and counts.dtype == np.int32
+        assert np.array_equal(_bits(before[0]), _bits(steps[k - 1][3] if k else _f(0.0, 0.0, -0.0)))       # inputs are not modified
+    # no histogram without actions or without counts; buffers longer than E keep their tail
+    got = R.episode_track(_f(1.0), [1], None, A, _f(2.0, 7.0), _i(4, 7), _f(9.0, 9.0), _i(9, 9), _i(5, 5, 5))
+    for g, w in zip(got, (_f(0.0, 7.0), _i(0, 7), _f(3.0, 9.0), _i(5, 9), _i(5, 5, 5))):
+        assert np.array_equal(g, w)
+    assert R.episode_track(_f(1.0), [0], _i(1), A, _f(2.0), _i(4), _f(9.0), _i(9), None)[4] is None
+
+
+def test_episode_reward_is_a_sequential_float32_sum():
+    """Three rewards whose float32 running sum differs from the float64 sum rounded once: 2^24 + 1 + 1 stays 2^24 in float32."""
+    epr, epl, outr, outl = _f(0.0), _i(0), _f(0.0), _i(0)
+    for k, r in enumerate((16777216.0, 1.0, 1.0)):
+        epr, epl, outr, outl, _ = R.episode_track(_f(r), [k == 2], None, 1, epr, epl, outr, outl, None)
+    assert float(outr[0]) == 16777216.0 and int(outl[0]) == 3
+    assert float(np.float32(16777216.0 + 1.0 + 1.0)) == 16777218.0              # the float64 sum, rounded once, is another number
+
+
+def _pre_buffers():
+    return dict(xh=_f(*[9.0] * 7), c_in=_f(*[9.0] * 5), state_pack=_f(*[9.0] * 9), initials=_f(9.0, 9.0, 9.0),
+                rewards_out=_f(9.0, 9.0, 9.0), dones_out=np.array([7, 7, 7], dtype=np.uint8))
+
+
+def test_actor_pre_on_a_hand_worked_step():
+    """E = 2, H = 2, xh_pitch = 3; env 0 is done.  Its carry becomes the signed zero of x * 0: 1.5 -> +0.0, -2.0 -> -0.0,
+    -1.0 -> -0.0, 0.0 -> +0.0; env 1 keeps -0.0 as it is.  Column 2 of each xh row and every guard element keep the 9.0 / 7."""
+    h, c = _f(1.5, -2.0, -0.0, 3.0), _f(-1.0, 0.0, 4.0, -0.5)
+    raw, dones = _f(-2.5, -0.0), np.array([1, 0], dtype=np.uint8)
+    stats = dict(actions=_i(-1, 2), A=2, ep_reward=_f(1.0, 2.0), ep_len=_i(3, 4), out_reward=_f(9.0, 9.0), out_len=_i(9, 9),
+                 action_counts=_i(0, 0))
+    step = np.array([5], dtype=np.uint64)
+    got = R.actor_pre(raw, dones, 2, h, c, xh_pitch=3, clip=1, rng_step=step, step=11, **_pre_buffers(), **stats)
+    want = dict(xh=_f(0.0, -0.0, 9.0, -0.0, 3.0, 9.0, 9.0), c_in=_f(-0.0, 0.0, 4.0, -0.5, 9.0),
+                state_pack=_f(0.0, -0.0, -0.0, 0.0, -0.0, 3.0, 4.0, -0.5, 9.0), initials=_f(1.0, 0.0, 9.0),
+                rewards_out=_f(-1.0, 0.0, 9.0), ep_reward=_f(0.0, 2.0), out_reward=_f(-1.5, 0.0))
+    for k, w in want.items():
+        assert got[k].dtype == np.float32 and np.array_equal(_bits(got[k]), _bits(w)), k
+    assert np.array_equal(got["dones_out"], np.array([1, 0, 7], dtype=np.uint8))
+    assert np.array_equal(got["ep_len"], _i(0, 5)) and np.array_equal(got["out_len"], _i(4, 0))
+    assert np.array_equal(got["action_counts"], _i(0, 0))                 # -1 and A = 2: neither is counted
+    assert int(got["rng_step"][0]) == 11 and int(step[0]) == 5
+    # no clipping: the raw reward passes through with its sign bit; actions 1, 0 are counted; the counter advances by one
+    stats["actions"] = _i(1, 0)
+    got = R.actor_pre(raw, dones, 2, h, c, xh_pitch=3, clip=0, rng_step=step, step=R.STEP_ADVANCE, **_pre_buffers(), **stats)
+    assert np.array_equal(_bits(got["rewards_out"]), _bits(_f(-2.5, -0.0, 9.0)))
+    assert np.array_equal(got["action_counts"], _i(1, 1)) and int(got["rng_step"][0]) == 6
+    top = np.array([2 ** 64 - 1], dtype=np.uint64)
+    assert int(R.actor_pre(raw, dones, 2, h, c, xh_pitch=3, clip=0, rng_step=top, step=R.STEP_ADVANCE, **_pre_buffers())["rng_step"][0]) == 0
+    # clip is np.sign: a positive subnormal is +1, huge values are +-1, both zeros give +0.0
+    raw5 = _f(0.0, -0.0, 1e-45, 3e38, -3e38)
+    b = dict(initials=_f(*[9.0] * 5), rewards_out=_f(*[9.0] * 5), dones_out=np.zeros(5, dtype=np.uint8))
+    got = R.actor_pre(raw5, [0] * 5, 0, None, None, None, 0, None, None, clip=1, **b)
+    assert np.array_equal(_bits(got["rewards_out"]), _bits(_f(0.0, 0.0, 1.0, 1.0, -1.0)))
+    # H = 0, no statistics, no counter: nothing but initials / rewards / dones
+    assert all(got[k] is None for k in ("xh", "c_in", "state_pack", "ep_reward", "ep_len", "out_reward", "out_len", "action_counts", "rng_step"))
+
+
+def test_actor_pre_statistics_are_episode_track():
+    g = np.random.default_rng(5)
+    E, A = 7, 4
+    epr, epl = g.standard_normal(E).astype(np.float32), g.integers(0, 50, E).astype(np.int32)
+    outr, outl, counts = np.full(E + 1, 9, np.float32), np.full(E + 1, 9, np.int32), g.integers(0, 9, A).astype(np.int32)
+    raw, dones = g.standard_normal(E).astype(np.float32), g.integers(0, 2, E).astype(np.uint8)
+    actions = g.integers(-1, A + 1, E).astype(np.int32)
+    b = dict(initials=np.zeros(E, np.float32), rewards_out=np.zeros(E, np.float32), dones_out=np.zeros(E, np.uint8))
+    got = R.actor_pre(raw, dones, 0, None, None, None, 0, None, None, clip=1, actions=actions, A=A, ep_reward=epr, ep_len=epl,
+                      out_reward=outr, out_len=outl, action_counts=counts, **b)
+    want = R.episode_track(raw, dones, actions, A, epr, epl, outr, outl, counts)
+    for k, w in zip(("ep_reward", "ep_len", "out_reward", "out_len", "action_counts"), want):
+        assert np.array_equal(got[k], w), k
+    assert int(want[4].sum() - counts.sum()) == int(((actions >= 0) & (actions < A)).sum())
+
+
+def test_stack_shift_by_hand_and_against_the_env_fallback():
+    inp = np.array([[[1, 2], [3, 4], [5, 6]], [[7, 8], [9, 10], [11, 12]]], dtype=np.uint8)       # E = 2, P = 3, 2-byte planes
+    newest = np.array([[21, 22], [23, 24]], dtype=np.uint8)
+    want = np.array([[[3, 4], [5, 6], [21, 22]], [[0, 0], [0, 0], [23, 24]]], dtype=np.uint8)
+    assert np.array_equal(R.stack_shift(inp, newest, [0, 1]), want)
+    # the non-kernel branch of SyntheticAtariVecEnv._shift (a CPU env): the same operation in torch
+    from rltime_amd.acting.synthetic_env import SyntheticAtariVecEnv
+    g = np.random.default_rng(9)
+    for P, shape in ((2, (3, 5)), (4, (4, 4))):
+        env = SyntheticAtariVecEnv(5, frame_shape=(P,) + shape, device="cpu", pool=2, frame_stack=True)
+        stack = g.integers(0, 256, (5, P) + shape).astype(np.uint8)
+        newest = g.integers(0, 256, (5,) + shape).astype(np.uint8)
+        dones = np.array([0, 1, 1, 0, 1], dtype=bool)
+        env._stack = torch.from_numpy(stack.copy())
+        got = env._shift(torch.from_numpy(newest), torch.from_numpy(dones))
+        assert np.array_equal(got.numpy(), R.stack_shift(stack, newest, dones))
+
+
+def test_synth_env_draws_are_words_0_and_1_with_strict_thresholds():
+    seed, t, E = 1234, (1 << 32) + 5, 16                                  # the high word of t takes part
+    r, d, idx, u0, u1 = R.synth_env_draws(seed, t, E, 0.1, 0.9, 0.25, pool_n=3)
+    assert idx == t % 3 and r.dtype == np.float32 and d.dtype == np.uint8 and u0.dtype == np.float32
+    for e in range(E):
+        w = R.philox_4x32(seed ^ 0xE17, t, e)
+        assert float(u0[e]) == (w[0] >> 8) / 16777216.0 and float(u1[e]) == (w[1] >> 8) / 16777216.0
+        assert float(r[e]) == (-1.0 if u0[e] < np.float32(0.1) else 0.0 if u0[e] < np.float32(0.9) else 1.0)
+        assert int(d[e]) == int(u1[e] < np.float32(0.25))
+    assert torch.equal(torch.from_numpy(u0), R.philox_head_draws(seed ^ 0xE17, t, E, 6)[0])
+    assert not np.array_equal(u0, R.synth_env_draws(seed, 5, E, 0.1, 0.9, 0.25)[3])                # t mod 2^32 alone is another block
+    assert len(set(r.tolist())) == 3 and 0 < int(d.sum()) < E and not np.array_equal(u0, u1)
+    # a threshold equal to the uniform is not below it; the next float32 above is
+    k = int(np.argmax(u1))
+    up = np.nextafter(u1[k], np.float32(2))
+    assert R.synth_env_draws(seed, t, E, 0.1, 0.9, u1[k])[1][k] == 0 and R.synth_env_draws(seed, t, E, 0.1, 0.9, up)[1][k] == 1
+    k = int(np.argmax(u0))
+    up = np.nextafter(u0[k], np.float32(2))
+    assert R.synth_env_draws(seed, t, E, u0[k], 1.0, 0.0)[0][k] == 0.0 and R.synth_env_draws(seed, t, E, up, 1.0, 0.0)[0][k] == -1.0
+    assert R.synth_env_draws(seed, t, E, 0.0, u0[k], 0.0)[0][k] == 1.0 and R.synth_env_draws(seed, t, E, 0.0, up, 0.0)[0][k] == 0.0
+    # p_neg = 0, p_nonpos = 1: every reward is 0; p_done 0 / 1: nobody / everybody
+    r0, d0, _, _, _ = R.synth_env_draws(seed, t, E, 0.0, 1.0, 0.0)
+    assert not r0.any() and not d0.any() and R.synth_env_draws(seed, t, E, 0.0, 1.0, 1.0)[1].all()
+
+
+def test_frames_to_f32_nhwc_is_one_rounding_in_channels_last():
+    x = np.arange(24, dtype=np.uint8).reshape(1, 4, 6) * 11
+    got = R.frames_to_f32_nhwc(x, 0.3)
+    assert got.shape == (1, 6, 4) and got.dtype == np.float32
+    for p in range(6):
+        for ch in range(4):
+            assert got[0, p, ch] == np.float32(float(x[0, ch, p])) * np.float32(0.3)
