@@ -856,6 +856,41 @@ int mirl_adam_clip_step(int32_t count, float* const* param, float* const* grad, 
                         const float* lr_dev, double beta1, double beta2, double eps, double clip, void* workspace,
                         int64_t workspace_bytes, float* norm_out, void* stream);
 
+/* ---- the step guard: drop a poisoned learner step on the device (csrc/optim.hip, csrc/replay.hip) --------------------
+ * Not in the reference.  Opt-in: nothing above changes when these entry points are not called.  The guard is 8 int32
+ * words of CALLER-OWNED device memory, 16-byte aligned, zeroed by the caller before its first use:
+ *   [0] veto bits of the step in flight (MIRL_VETO_*)      [1] steps closed            [2] steps skipped
+ *   [3] / [4] / [5] steps skipped with MIRL_VETO_LOSS / _NORM / _STATUS set            [6], [7] reserved, stay 0
+ * One learner step is  open -> guarded Adam -> guarded update_losses  on one stream.  All four entry points return
+ * MIRL_ERR_ARG for bad arguments and then write nothing; none synchronises; all can be captured into a graph.        */
+#define MIRL_VETO_LOSS 1     /* a per-transition error offered to the replay is NaN or +-Inf */
+#define MIRL_VETO_NORM 2     /* the global gradient norm is NaN or +-Inf                      */
+#define MIRL_VETO_STATUS 4   /* an external status word is non-zero                          */
+/* Opens a step: ONE launch of ONE workgroup.  Scans rows[count] (float32, device; NULL with count 0) for a non-finite
+ * value, reads the n_status <= 4 device words status[i] points to (status is a HOST array; the pointers travel by value
+ * in the kernel arguments; a word may be mapped host memory) and OVERWRITES word [0] with the bits found — which also
+ * clears the previous step's.  Words [1] to [7] are not touched.                                                    */
+int mirl_step_guard_open(int32_t* guard, const float* rows, int64_t count, const int32_t* const* status,
+                         int32_t n_status, void* stream);
+/* mirl_adam_clip_step with the guard: k_adam_sqsum as there; the update skips when word [0] is non-zero or the norm is
+ * non-finite — then nothing is written to param, grad, exp_avg, exp_avg_sq or step.  norm_out is written as by the
+ * unguarded call.  Closes the step: ORs MIRL_VETO_NORM into [0] for a non-finite norm, increments [1], and on a skip [2]
+ * and the counter of every bit set.  A step that is not skipped is bit-identical to mirl_adam_clip_step.            */
+int mirl_adam_clip_step_guarded(int32_t count, float* const* param, float* const* grad, float* const* exp_avg,
+                                float* const* exp_avg_sq, float* const* step, const int64_t* numel, double lr,
+                                const float* lr_dev, double beta1, double beta2, double eps, double clip, void* workspace,
+                                int64_t workspace_bytes, float* norm_out, int32_t* guard, void* stream);
+/* mirl_replay_update_losses with the guard: the same four launches; with word [0] non-zero no loss is written and no
+ * sequence flagged, so losses and tree stay as they were.  The call's epoch is spent either way.  A no-op for
+ * non-prioritized buffers and count <= 0 like the unguarded call (the guard is checked first).                      */
+int mirl_replay_update_losses_guarded(mirl_replay* h, int64_t count, const int64_t* indices, const float* losses,
+                                      const int32_t* guard, void* stream);
+/* Device address of the persistent LSTM sweeps' status word (mirl_lstm_seq_status reads the same word on the host), to
+ * be handed to mirl_step_guard_open.  The same address for the life of the process.  Allocates the word when no sweep
+ * has run yet, so the FIRST call must not happen inside a stream capture.  How the sweeps set, clear and report the
+ * word is unchanged.                                                                                                */
+int mirl_lstm_seq_status_device(const int32_t** p);
+
 #ifdef __cplusplus
 }
 #endif

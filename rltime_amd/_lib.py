@@ -214,6 +214,10 @@ _SIGNATURES = {
     "mirl_cos_embed_rng": [_i64, _i32, _u64, _vp, _vp, _vp, _vp, _vp],
     "mirl_adam_clip_workspace_bytes": [_i32, _vp, _vp],
     "mirl_adam_clip_step": [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _f64, _f64, _f64, _f64, _vp, _i64, _vp, _vp],
+    "mirl_adam_clip_step_guarded": [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _f64, _f64, _f64, _f64, _vp, _i64, _vp, _vp, _vp],
+    "mirl_step_guard_open": [_vp, _vp, _i64, _vp, _i32, _vp],
+    "mirl_replay_update_losses_guarded": [_vp, _i64, _vp, _vp, _vp, _vp],
+    "mirl_lstm_seq_status_device": [_P(_vp)],
     "mirl_iqn_mul_fwd": [_i64, _i32, _i32, _vp, _vp, _vp, _vp],
     "mirl_iqn_mul_bwd": [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
     "mirl_dueling_tail_bwd": [_i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp],

@@ -848,6 +848,16 @@ extern "C" int mirl_lstm_seq_fwd_grid(int32_t B, int32_t H, int32_t* workgroups,
   return MIRL_OK;
 }
 
+extern "C" int mirl_lstm_seq_status_device(const int32_t** p) {
+  using namespace mirl;
+  if (!p) return fail(MIRL_ERR_ARG, "bad lstm_seq_status_device arguments");
+  int rc = seq_init(); if (rc) return rc;          // allocates the word when no sweep has run yet: not inside a capture
+  int* dev = nullptr;
+  MIRL_HIP(hipHostGetDevicePointer((void**)&dev, g_seq_status, 0));
+  *p = dev;
+  return MIRL_OK;
+}
+
 extern "C" int mirl_lstm_seq_status(int32_t* status) {
   if (!status) return fail(MIRL_ERR_ARG, "bad lstm_seq_status arguments");
   *status = g_seq_status ? *(volatile int*)g_seq_status : 0;

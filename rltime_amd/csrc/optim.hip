@@ -18,6 +18,13 @@
 // Tensor pointers travel by value in the kernel arguments (<= 32 tensors per launch), so a captured graph replays them
 // as they were at capture time — the .grad tensors of a captured backward have fixed addresses.  HBM-bound: 7 streams
 // of 4 bytes per parameter (g, m, v, p read; m, v, p written; + g written when the clip bites).
+//
+// The step guard (opt-in, mirl_step_guard_open + mirl_adam_clip_step_guarded): 8 int32 words of caller-owned device
+// memory.  k_step_guard_open (one workgroup) scans the per-transition errors bound for the replay for a non-finite value,
+// reads up to 4 external status words (the persistent LSTM sweeps' among them) and OVERWRITES word 0 with the veto bits
+// found; k_adam_update_guarded is k_adam_update with one more test — every workgroup already holds the norm, so
+// `skip = word 0 != 0 || norm non-finite` is the same in all of them without a barrier — and on skip writes nothing to
+// p, g, m, v or the step counters.  The workgroup that writes norm_out keeps the guard's counters.
 #include "common.hpp"
 
 namespace mirl {
@@ -71,8 +78,11 @@ k_adam_sqsum(AdamTensors t, AdamHyper h) {
   }
 }
 
-__global__ void __launch_bounds__(256)
-k_adam_update(AdamTensors t, AdamHyper h) {
+__device__ __forceinline__ bool nonfinite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+// GUARD = false is the update as it always was; GUARD = true adds the veto test after the norm (same arithmetic after it)
+template <bool GUARD>
+__device__ __forceinline__ void adam_update_body(const AdamTensors& t, const AdamHyper& h, int32_t* guard) {
   __shared__ double red[256];
   const int b = blockIdx.x, k = adam_find(t, b), tid = threadIdx.x;
   double acc = 0.0;
@@ -83,6 +93,25 @@ k_adam_update(AdamTensors t, AdamHyper h) {
   const float norm = (float)sqrt(red[0]);
   float coef = 1.f;
   if (h.clip > 0.0) { coef = (float)h.clip / (norm + 1e-6f); coef = coef > 1.f ? 1.f : coef; }
+  if constexpr (GUARD) {
+    // word 0 only gains MIRL_VETO_NORM while this kernel runs, and only when the norm every workgroup holds is non-finite:
+    // whichever value a workgroup reads, `skip` comes out the same (also in the second launch of > 32 tensors)
+    const int32_t open_bits = guard[0];
+    const bool bad_norm = nonfinite_bits(norm);
+    if (tid == 0 && t.chunk_base + b == 0) {
+      const int32_t bits = open_bits | (bad_norm ? MIRL_VETO_NORM : 0);
+      if (h.norm_out) { h.norm_out[0] = norm; h.norm_out[1] = norm * coef; }
+      if (bad_norm) guard[0] = bits;
+      guard[1] += 1;
+      if (bits) {
+        guard[2] += 1;
+        if (bits & MIRL_VETO_LOSS) guard[3] += 1;
+        if (bits & MIRL_VETO_NORM) guard[4] += 1;
+        if (bits & MIRL_VETO_STATUS) guard[5] += 1;
+      }
+    }
+    if (open_bits != 0 || bad_norm) return;
+  }
   const double step = h.partial[h.total_chunks + t.tensor_base + k];
   const double lr = h.lr_dev ? (double)h.lr_dev[0] : h.lr;
   const double bc1 = 1.0 - pow(h.beta1, step), bc2 = 1.0 - pow(h.beta2, step);
@@ -119,7 +148,43 @@ k_adam_update(AdamTensors t, AdamHyper h) {
   }
 #undef ADAM_ELEM
   if (tid == 0 && b == t.chunk0[k]) t.step[k][0] = (float)step;
-  if (tid == 0 && t.chunk_base + b == 0 && h.norm_out) { h.norm_out[0] = norm; h.norm_out[1] = norm * coef; }
+  if (!GUARD && tid == 0 && t.chunk_base + b == 0 && h.norm_out) { h.norm_out[0] = norm; h.norm_out[1] = norm * coef; }
+}
+
+__global__ void __launch_bounds__(256)
+k_adam_update(AdamTensors t, AdamHyper h) { adam_update_body<false>(t, h, nullptr); }
+
+__global__ void __launch_bounds__(256)
+k_adam_update_guarded(AdamTensors t, AdamHyper h, int32_t* guard) { adam_update_body<true>(t, h, guard); }
+
+// ---- the guard's opening: one workgroup, one launch per learner step ---------------------------------------------------
+#define GUARD_MAXS 4
+struct GuardStatus { const int32_t* p[GUARD_MAXS]; int n; };
+
+__global__ void __launch_bounds__(1024)
+k_step_guard_open(int32_t* guard, const float* __restrict__ rows, long long count, GuardStatus s) {
+  const int tid = threadIdx.x;
+  int bad = 0;
+  if (!((uintptr_t)rows & 15)) {
+    const long long n4 = count >> 2;
+    const uint4* r4 = (const uint4*)rows;
+    for (long long i = tid; i < n4; i += 1024) {
+      const uint4 x = r4[i];
+      bad |= ((x.x & 0x7f800000u) == 0x7f800000u) | ((x.y & 0x7f800000u) == 0x7f800000u) |
+             ((x.z & 0x7f800000u) == 0x7f800000u) | ((x.w & 0x7f800000u) == 0x7f800000u);
+    }
+    for (long long i = (n4 << 2) + tid; i < count; i += 1024) bad |= nonfinite_bits(rows[i]);
+  } else {
+    for (long long i = tid; i < count; i += 1024) bad |= nonfinite_bits(rows[i]);
+  }
+  bad = __syncthreads_or(bad);
+  if (tid == 0) {
+    int32_t bits = bad ? MIRL_VETO_LOSS : 0;
+    // (a status word may be mapped host memory that a running kernel of another stream sets: a system-scope load)
+    for (int i = 0; i < s.n; ++i)
+      if (__hip_atomic_load(s.p[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0) bits |= MIRL_VETO_STATUS;
+    guard[0] = bits;
+  }
 }
 
 static int64_t adam_chunks(int32_t count, const int64_t* numel) {
@@ -138,11 +203,11 @@ extern "C" int mirl_adam_clip_workspace_bytes(int32_t count, const int64_t* nume
   return MIRL_OK;
 }
 
-extern "C" int mirl_adam_clip_step(int32_t count, float* const* param, float* const* grad, float* const* exp_avg,
-                                   float* const* exp_avg_sq, float* const* step, const int64_t* numel, double lr,
-                                   const float* lr_dev, double beta1, double beta2, double eps, double clip, void* workspace,
-                                   int64_t workspace_bytes, float* norm_out, void* stream) {
-  using namespace mirl;
+namespace mirl {
+static int adam_clip_step_impl(int32_t count, float* const* param, float* const* grad, float* const* exp_avg,
+                               float* const* exp_avg_sq, float* const* step, const int64_t* numel, double lr,
+                               const float* lr_dev, double beta1, double beta2, double eps, double clip, void* workspace,
+                               int64_t workspace_bytes, float* norm_out, int32_t* guard, void* stream) {
   if (count < 1 || !param || !grad || !exp_avg || !exp_avg_sq || !step || !numel || !workspace)
     return fail(MIRL_ERR_ARG, "bad adam_clip_step arguments");
   if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0) || (!lr_dev && !(lr >= 0.0)))
@@ -177,10 +242,50 @@ extern "C" int mirl_adam_clip_step(int32_t count, float* const* param, float* co
       }
       t.chunk0[t.count] = c;
       if (pass == 0) hipLaunchKernelGGL(k_adam_sqsum, dim3((unsigned)c), dim3(256), 0, st, t, h);
-      else hipLaunchKernelGGL(k_adam_update, dim3((unsigned)c), dim3(256), 0, st, t, h);
+      else if (!guard) hipLaunchKernelGGL(k_adam_update, dim3((unsigned)c), dim3(256), 0, st, t, h);
+      else hipLaunchKernelGGL(k_adam_update_guarded, dim3((unsigned)c), dim3(256), 0, st, t, h, guard);
       MIRL_LAUNCH_CHECK();
       chunk_base += c;
     }
   }
+  return MIRL_OK;
+}
+}  // namespace mirl
+
+extern "C" int mirl_adam_clip_step(int32_t count, float* const* param, float* const* grad, float* const* exp_avg,
+                                   float* const* exp_avg_sq, float* const* step, const int64_t* numel, double lr,
+                                   const float* lr_dev, double beta1, double beta2, double eps, double clip, void* workspace,
+                                   int64_t workspace_bytes, float* norm_out, void* stream) {
+  return mirl::adam_clip_step_impl(count, param, grad, exp_avg, exp_avg_sq, step, numel, lr, lr_dev, beta1, beta2, eps, clip,
+                                   workspace, workspace_bytes, norm_out, nullptr, stream);
+}
+
+extern "C" int mirl_adam_clip_step_guarded(int32_t count, float* const* param, float* const* grad, float* const* exp_avg,
+                                           float* const* exp_avg_sq, float* const* step, const int64_t* numel, double lr,
+                                           const float* lr_dev, double beta1, double beta2, double eps, double clip,
+                                           void* workspace, int64_t workspace_bytes, float* norm_out, int32_t* guard,
+                                           void* stream) {
+  if (!guard || ((uintptr_t)guard & 15)) return mirl::fail(MIRL_ERR_ARG, "adam_clip_step_guarded: null / misaligned guard");
+  return mirl::adam_clip_step_impl(count, param, grad, exp_avg, exp_avg_sq, step, numel, lr, lr_dev, beta1, beta2, eps, clip,
+                                   workspace, workspace_bytes, norm_out, guard, stream);
+}
+
+extern "C" int mirl_step_guard_open(int32_t* guard, const float* rows, int64_t count, const int32_t* const* status,
+                                    int32_t n_status, void* stream) {
+  using namespace mirl;
+  if (!guard || ((uintptr_t)guard & 15)) return fail(MIRL_ERR_ARG, "step_guard_open: null / misaligned guard");
+  if (count < 0 || (count > 0 && !rows) || ((uintptr_t)rows & 3)) return fail(MIRL_ERR_ARG, "step_guard_open: bad rows / count");
+  if (n_status < 0 || n_status > GUARD_MAXS || (n_status > 0 && !status))
+    return fail(MIRL_ERR_ARG, "step_guard_open: 0 <= n_status <= 4");
+  GuardStatus s;
+  s.n = n_status;
+  for (int i = 0; i < GUARD_MAXS; ++i) {
+    s.p[i] = i < n_status ? status[i] : nullptr;
+    if (i < n_status && (!s.p[i] || ((uintptr_t)s.p[i] & 3))) return fail(MIRL_ERR_ARG, "step_guard_open: null / misaligned status word");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps("k_step_guard_open", (double)count * 4.0, st);
+  hipLaunchKernelGGL(k_step_guard_open, dim3(1), dim3(1024), 0, st, guard, rows, (long long)count, s);
+  MIRL_LAUNCH_CHECK();
   return MIRL_OK;
 }

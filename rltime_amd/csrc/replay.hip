@@ -742,8 +742,7 @@ k_gather_scalars(Dev d, int B, int R, int overlapped, const int32_t* __restrict_
 // twice the LAST pair wins.  Pass 1 elects that winner per transition with a
 // 64-bit atomicMax of (call epoch << 32 | pair index); pass 2 lets only the
 // winner write, and every pair marks the overlapped sequences it touches.
-__global__ void __launch_bounds__(256)
-k_loss_stamp(Dev d, int64_t n, const int64_t* __restrict__ idx, uint64_t epoch) {
+__device__ __forceinline__ void loss_stamp_body(const Dev& d, int64_t n, const int64_t* __restrict__ idx, uint64_t epoch) {
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   int64_t env_id = idx[2 * i], off = idx[2 * i + 1];
@@ -752,8 +751,8 @@ k_loss_stamp(Dev d, int64_t n, const int64_t* __restrict__ idx, uint64_t epoch) 
   if (e < 0 || e >= d.E || off < d.first[e] || off >= d.count[e]) return;   // :254 evicted meanwhile
   atomicMax(&d.stamp[slot_of(d, e, off)], (unsigned long long)((epoch << 32) | (uint64_t)i));
 }
-__global__ void __launch_bounds__(256)
-k_loss_write(Dev d, int64_t n, const int64_t* __restrict__ idx, const float* __restrict__ losses, uint64_t epoch) {
+__device__ __forceinline__ void loss_write_body(const Dev& d, int64_t n, const int64_t* __restrict__ idx,
+                                                const float* __restrict__ losses, uint64_t epoch) {
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   int64_t env_id = idx[2 * i], off = idx[2 * i + 1];
@@ -771,6 +770,26 @@ k_loss_write(Dev d, int64_t n, const int64_t* __restrict__ idx, const float* __r
     if (s >= 0) d.flag[s] = 1;
     base -= d.gap;
   }
+}
+__global__ void __launch_bounds__(256)
+k_loss_stamp(Dev d, int64_t n, const int64_t* __restrict__ idx, uint64_t epoch) { loss_stamp_body(d, n, idx, epoch); }
+__global__ void __launch_bounds__(256)
+k_loss_write(Dev d, int64_t n, const int64_t* __restrict__ idx, const float* __restrict__ losses, uint64_t epoch) {
+  loss_write_body(d, n, idx, losses, epoch);
+}
+// The step guard's forms (csrc/optim.hip): a vetoed step (word 0 of the guard non-zero) elects no winner, writes no loss
+// and flags no sequence, so the recalc and tree-fix launches that follow find no work.  The call's epoch is spent either
+// way; a later call's stamps are larger, so the missing ones do no harm.
+__global__ void __launch_bounds__(256)
+k_loss_stamp_guarded(Dev d, int64_t n, const int64_t* __restrict__ idx, uint64_t epoch, const int32_t* __restrict__ guard) {
+  if (guard[0] != 0) return;
+  loss_stamp_body(d, n, idx, epoch);
+}
+__global__ void __launch_bounds__(256)
+k_loss_write_guarded(Dev d, int64_t n, const int64_t* __restrict__ idx, const float* __restrict__ losses, uint64_t epoch,
+                     const int32_t* __restrict__ guard) {
+  if (guard[0] != 0) return;
+  loss_write_body(d, n, idx, losses, epoch);
 }
 __global__ void __launch_bounds__(256)
 k_recalc_flagged(Dev d) {
@@ -1080,7 +1099,8 @@ static int scatter(mirl_replay* h, const void* src, void* ring, const int32_t* s
   return MIRL_OK;
 }
 
-static int update_losses_impl(mirl_replay* h, int64_t count, const int64_t* indices, const float* losses, hipStream_t st);
+static int update_losses_impl(mirl_replay* h, int64_t count, const int64_t* indices, const float* losses, const int32_t* guard,
+                              hipStream_t st);
 
 // Reset observation of every env as "transition -1" of a de-duplicated shard (newest-plane ingest).
 __global__ void __launch_bounds__(256)
@@ -1219,7 +1239,7 @@ extern "C" int mirl_replay_ingest(mirl_replay* h, const mirl_ingest* in, void* s
                          h->td_idx, h->td_loss);
     }
     MIRL_LAUNCH_CHECK();
-    rc = update_losses_impl(h, K, h->td_idx, h->td_loss, st); if (rc) return rc;
+    rc = update_losses_impl(h, K, h->td_idx, h->td_loss, nullptr, st); if (rc) return rc;
   }
   return h->staging.mark(st);
 }
@@ -1716,18 +1736,31 @@ extern "C" int mirl_replay_update_losses(mirl_replay* h, int64_t count, const in
   if (!h->d.per || count <= 0) return MIRL_OK;           // history.py:332-335 no-op for non-prioritized buffers
   if (!indices || !losses) return fail(MIRL_ERR_ARG, "null indices/losses");
   if (count >= (1LL << 32)) return fail(MIRL_ERR_ARG, "too many loss rows");
-  return update_losses_impl(h, count, indices, losses, (hipStream_t)stream);
+  return update_losses_impl(h, count, indices, losses, nullptr, (hipStream_t)stream);
 }
 
-static int update_losses_impl(mirl_replay* h, int64_t count, const int64_t* indices, const float* losses, hipStream_t st) {
+extern "C" int mirl_replay_update_losses_guarded(mirl_replay* h, int64_t count, const int64_t* indices, const float* losses,
+                                                 const int32_t* guard, void* stream) {
+  if (!h) return fail(MIRL_ERR_ARG, "null handle");
+  if (!guard || ((uintptr_t)guard & 15)) return fail(MIRL_ERR_ARG, "update_losses_guarded: null / misaligned guard");
+  if (!h->d.per || count <= 0) return MIRL_OK;
+  if (!indices || !losses) return fail(MIRL_ERR_ARG, "null indices/losses");
+  if (count >= (1LL << 32)) return fail(MIRL_ERR_ARG, "too many loss rows");
+  return update_losses_impl(h, count, indices, losses, guard, (hipStream_t)stream);
+}
+
+static int update_losses_impl(mirl_replay* h, int64_t count, const int64_t* indices, const float* losses, const int32_t* guard,
+                              hipStream_t st) {
   Dev& d = h->d;
   uint64_t epoch = h->epoch++;
   unsigned g = (unsigned)((count + 255) / 256);
   { ProfScope ps("k_loss_stamp", (double)count * 24.0, st);
-    hipLaunchKernelGGL(k_loss_stamp, dim3(g), dim3(256), 0, st, d, count, indices, epoch); }
+    if (!guard) hipLaunchKernelGGL(k_loss_stamp, dim3(g), dim3(256), 0, st, d, count, indices, epoch);
+    else hipLaunchKernelGGL(k_loss_stamp_guarded, dim3(g), dim3(256), 0, st, d, count, indices, epoch, guard); }
   MIRL_LAUNCH_CHECK();
   { ProfScope ps("k_loss_write", (double)count * 32.0, st);
-    hipLaunchKernelGGL(k_loss_write, dim3(g), dim3(256), 0, st, d, count, indices, losses, epoch); }
+    if (!guard) hipLaunchKernelGGL(k_loss_write, dim3(g), dim3(256), 0, st, d, count, indices, losses, epoch);
+    else hipLaunchKernelGGL(k_loss_write_guarded, dim3(g), dim3(256), 0, st, d, count, indices, losses, epoch, guard); }
   MIRL_LAUNCH_CHECK();
   if (d.T >= 8 && d.T <= 128) {
     ProfScope ps("k_recalc_flagged_wave", (double)d.n_slots + (double)count * 4.0 * 2, st);

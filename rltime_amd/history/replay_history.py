@@ -504,8 +504,8 @@ class ReplayHistoryBuffer(History):
                                "loss_indices": loss_idx} if per else {}
         return batch
 
-    def update_losses(self, indices, losses):
-        """history.py:332-335 — nothing to do for uniform replay."""
+    def update_losses(self, indices, losses, guard=None):
+        """history.py:332-335 — nothing to do for uniform replay (with or without a step guard)."""
 
     # -- introspection (tests / logging) ----------------------------------------
     def stats(self):
@@ -688,10 +688,12 @@ class PrioritizedReplayHistoryBuffer(ReplayHistoryBuffer):
         consumed even when the call then returns None (:284 precedes :295)."""
         return np.array([random.random() for _ in range(mbatch)], dtype=np.float64)
 
-    def update_losses(self, indices, losses):
+    def update_losses(self, indices, losses, guard=None):
         """prioritized_replay_history.py:243-279.  ``indices`` (M, 2) int64 and
         ``losses`` (M,) float32; device tensors stay on the device (no host
-        round trip), numpy arrays are uploaded."""
+        round trip), numpy arrays are uploaded.  ``guard`` (not in the reference): the 8-word
+        int32 device tensor of a step guard (models/torch/optim.py) — a vetoed step then leaves
+        losses and tree as they were."""
         if self._h is None:
             return
         if not isinstance(indices, torch.Tensor):
@@ -701,9 +703,14 @@ class PrioritizedReplayHistoryBuffer(ReplayHistoryBuffer):
         indices = indices.to(self.device, torch.int64).reshape(-1, 2).contiguous()
         losses = losses.detach().to(self.device, torch.float32).reshape(-1).contiguous()
         assert indices.shape[0] == losses.shape[0]
-        check(lib.mirl_replay_update_losses(
-            self._h, losses.shape[0], ptr(indices), ptr(losses), stream()),
-            "mirl_replay_update_losses")
+        if guard is None:
+            check(lib.mirl_replay_update_losses(
+                self._h, losses.shape[0], ptr(indices), ptr(losses), stream()),
+                "mirl_replay_update_losses")
+        else:
+            check(lib.mirl_replay_update_losses_guarded(
+                self._h, losses.shape[0], ptr(indices), ptr(losses), ptr(guard), stream()),
+                "mirl_replay_update_losses_guarded")
         s = torch.cuda.current_stream()
         indices.record_stream(s)
         losses.record_stream(s)

@@ -12,7 +12,7 @@ class TorchTrainer(MultiStepTrainer):
     def _train(self, clip_grad=None, clip_grad_dynamic_alpha=None, adam_epsilon=1e-8,
                vf_scale_epsilon=None, apply_initial_lr=False, burn_in_full_forward=False,
                share_online_cnn=True, share_online_projection=True, selection_advantage_only=True,
-               graph_learner_step=False, **kwargs):
+               graph_learner_step=False, skip_invalid_steps=False, **kwargs):
         """torch_trainer.py:9-44.  apply_initial_lr=False mirrors the reference,
         whose train_init ignores `lr` (Adam starts at 1e-3, SURVEY A-14)."""
         self.clip_grad = float(clip_grad) if clip_grad is not None else None
@@ -38,7 +38,28 @@ class TorchTrainer(MultiStepTrainer):
         self.graph_learner_step = bool(graph_learner_step)
         self._graph_capture = graph_learner_step != "no-capture"
         self._gstep = None
+        # skip_invalid_steps (not in the reference): the step guard of csrc/optim.hip.  A learner step whose priority rows or
+        # gradient norm are non-finite, or whose guard finds the LSTM sweeps' status word set, is dropped ON THE DEVICE: it reaches
+        # neither the weights, the Adam state, the step counters nor the priority tree.  Off: nothing of it exists.
+        self.skip_invalid_steps = bool(skip_invalid_steps)
+        self._guard = None
+        self._guard_status = []
+        if self.skip_invalid_steps:
+            self._check_step_guard_config()
         super()._train(**kwargs)
+
+    def _check_step_guard_config(self):
+        """What skip_invalid_steps cannot cover is refused up front, never run unguarded."""
+        dp = getattr(self, "data_parallel", None)
+        if dp is not None and getattr(dp, "active", True):
+            raise ValueError("skip_invalid_steps cannot run under a process group: a veto every rank agrees on needs one "
+                             "more collective, which is not implemented")
+        if not self.policy.is_cuda():
+            raise ValueError("skip_invalid_steps needs a policy on the GPU: the guard lives in the HIP optimizer and replay "
+                             "kernels, and this is a CPU policy")
+        if self.clip_grad_dynamic_alpha is not None:
+            raise ValueError("skip_invalid_steps cannot be combined with clip_grad_dynamic_alpha: the moving average of the "
+                             "norm is updated outside the guarded kernels")
 
     def train_init(self, lr):
         """torch_trainer.py:80-83: Adam over the policy's parameters.  On a GPU it is `ClipAdam` — the same optimizer
@@ -53,7 +74,15 @@ class TorchTrainer(MultiStepTrainer):
         if self.policy.is_cuda() and os.environ.get("MIRL_CLIP_ADAM", "1") != "0":
             from rltime_amd.models.torch.optim import ClipAdam
             self.optimizer = ClipAdam(self.policy.parameters(), eps=self.adam_epsilon, **kw)
+            if getattr(self, "skip_invalid_steps", False):
+                from rltime_amd.models.torch import optim
+                dev = next(self.policy.parameters()).device
+                self._guard = optim.new_step_guard(dev)
+                # the status words a step is vetoed by: the persistent LSTM sweeps' (fetched here, outside any capture)
+                self._guard_status = [optim.sweep_status_word(dev)]
             return
+        if getattr(self, "skip_invalid_steps", False):
+            raise ValueError("skip_invalid_steps needs the fused optimizer step (ClipAdam), which is switched off")
         if graphed:
             # (torch's own `fused=True` form was tried here: under capture with a device learning rate its replays left the
             # eager trajectory at the first replayed step — tools/graph_step_deviation.py — so the fallback is the for-each form)
@@ -127,6 +156,8 @@ class TorchTrainer(MultiStepTrainer):
             dp.zero_grad()                  # .grad tensors are views of the all-reduce bucket
         else:
             self.optimizer.zero_grad(set_to_none=True)
+        if getattr(self, "_guard", None) is not None:
+            return self._train_batch_guarded(*args, **kwargs)
         self._compute_grads(*args, **kwargs)
         self._reduce_gradients()
         opt = self.optimizer
@@ -151,6 +182,58 @@ class TorchTrainer(MultiStepTrainer):
         if self.policy.is_cuda() and not torch.cuda.is_current_stream_capturing():
             self._check_sweeps()
         self.optimizer.step()
+
+    def _train_batch_guarded(self, *args, **kwargs):
+        """train_batch with skip_invalid_steps: gradients -> guard_open on the rows bound for the replay (and the status
+        words) -> guarded norm / clip / Adam -> guarded priority update.  The priority rows are held back until the
+        optimizer step is enqueued (the list a captured step uses), so that the eager and the graphed step treat a vetoed
+        step alike; in a capture the update follows each replay (_learner_step_graphed)."""
+        from rltime_amd.models.torch import optim
+        own = getattr(self, "_defer_losses", None) is None
+        if own:
+            self._defer_losses = []
+        first = len(self._defer_losses)
+        try:
+            self._compute_grads(*args, **kwargs)
+            self._reduce_gradients()          # a no-op today (_train refuses an active process group); kept for the day it is not
+            opt = self.optimizer
+            why = opt.why_not_fused() if hasattr(opt, "why_not_fused") else "the optimizer is not ClipAdam"
+            if why is not None:
+                raise ValueError("skip_invalid_steps: this step cannot take the guarded optimizer kernels (%s) and an "
+                                 "unguarded step is never taken in its place" % why)
+            rows = [losses.detach().reshape(-1) for _, losses in self._defer_losses[first:]]
+            rows = None if not rows else rows[0] if len(rows) == 1 else torch.cat(rows)
+            if rows is not None and not (rows.dtype == torch.float32 and rows.is_contiguous()):
+                rows = rows.float().contiguous()
+            if not torch.cuda.is_current_stream_capturing():
+                self._check_sweeps()
+            optim.guard_open(self._guard, rows, self._guard_status)
+            norms = opt.step_clipped(self.clip_grad if self.clip_grad else None, guard=self._guard)
+            self.value_log.log("grad_norm", norms[0], group="train")
+            if self.clip_grad:
+                self.value_log.log("grad_norm_clipped", norms[1], group="train")
+            if own:
+                for idx, losses in self._defer_losses:
+                    self._pre_update_losses()
+                    self.history_buffer.update_losses(idx, losses, guard=self._guard)
+        finally:
+            if own:
+                self._defer_losses = None
+
+    def _step_guard_counters(self):
+        """{skipped_steps, skipped_loss, skipped_norm, skipped_status, closed} of the step guard — synchronises; they
+        start at 0 with every run, resumed ones included (they are not part of a checkpoint)."""
+        if self._guard is None:
+            return None
+        w = self._guard.tolist()
+        return {"closed": w[1], "skipped_steps": w[2], "skipped_loss": w[3], "skipped_norm": w[4], "skipped_status": w[5]}
+
+    def _log_checkpoint(self):
+        if getattr(self, "_guard", None) is not None:
+            c = self._step_guard_counters()
+            for key in ("skipped_steps", "skipped_loss", "skipped_norm", "skipped_status"):
+                self.value_log.log(key, c[key], group="train")
+        super()._log_checkpoint()
 
     def _check_sweeps(self):
         """A persistent LSTM sweep that gave up (csrc/lstm_seq.hip: bounded spin, non-finite state) sets a pinned host
@@ -273,7 +356,10 @@ class TorchTrainer(MultiStepTrainer):
             if st["losses"]:
                 for idx, losses in st["losses"]:
                     self._pre_update_losses()
-                    self.history_buffer.update_losses(idx, losses)
+                    if self._guard is None:
+                        self.history_buffer.update_losses(idx, losses)
+                    else:
+                        self.history_buffer.update_losses(idx, losses, guard=self._guard)
             if st["logs"]:
                 vals = torch.stack([v.detach().reshape(()).float() for _, v, _, _ in st["logs"]])      # one launch for all scalars
                 for i, (key, _, a, k) in enumerate(st["logs"]):
