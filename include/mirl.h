@@ -478,7 +478,8 @@ int mirl_conv1_u8_fwd(int64_t N, int32_t H, int32_t W, const uint8_t* x, const f
  * stores (default non-temporal), bit 2 = conversions interleaved with the MFMA chain (default:
  * hoisted in front of it), bits 8-15 = frames per LDS fill (1 | 2, 0 = heuristic),
  * bits 16-23 = workgroups sharing one frame's tiles (0 = heuristic), bit 3 = wpk already holds
- * these weights packed by an earlier call with the same kernel choice, bit 5 = f32-MFMA kernel.  */
+ * these weights packed by an earlier call with the same kernel choice, bit 5 = f32-MFMA kernel.
+ * Any other bit is MIRL_ERR_ARG, before anything is launched.                                    */
 int mirl_conv1_u8_fwd_ex(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* weight,
                          int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w, const float* bias,
                          float scale, float* wpk, float* y, int32_t flags, void* stream);
@@ -498,7 +499,8 @@ int mirl_conv1_u8_wrw(int64_t N, int32_t H, int32_t W, const uint8_t* x, const f
                       float* scratch, float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w,
                       void* stream);
 /* the same with an explicit variant (tuning probe): flags bit 0 = byte->float conversions
- * interleaved with the MFMAs instead of hoisted in front of each k-step's 32 MFMAs.      */
+ * interleaved with the MFMAs instead of hoisted in front of each k-step's 32 MFMAs (f32-MFMA
+ * kernel only), bit 1 = f32-MFMA kernel.                                                   */
 int mirl_conv1_u8_wrw_ex(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* g, float scale,
                          float* scratch, float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w,
                          int32_t flags, void* stream);

@@ -199,7 +199,7 @@ extern "C" int mirl_synth_env_step(int32_t E, int64_t frame_bytes, const uint8_t
                                    uint64_t seed, float p_neg, float p_nonpos, float p_done, uint8_t* obs, float* rewards,
                                    uint8_t* dones, void* stream) {
   if (E <= 0 || frame_bytes <= 0 || (frame_bytes % 16) || pool_n <= 0 || !pool || !clock || !obs || !rewards || !dones ||
-      (slot != 0 && slot != 1) || ((uintptr_t)pool % 16) || ((uintptr_t)obs % 16) || ((uintptr_t)clock % 16))
+      (slot != 0 && slot != 1) || !mirl::aligned16(pool, obs, clock))
     return mirl::fail(MIRL_ERR_ARG, "bad synth_env_step arguments (16-byte aligned frame rows, slot 0 | 1)");
   const int row_q = (int)(frame_bytes / 16);
   int gx = (row_q + 255) / 256; if (gx > 8) gx = 8;
@@ -236,7 +236,7 @@ extern "C" int mirl_synth_env_step_pre(int32_t E, int64_t frame_bytes, const uin
                                        float* out_reward, int32_t* out_len, int32_t* action_counts, uint64_t* rng_step, uint64_t step,
                                        void* stream) {
   if (E <= 0 || frame_bytes <= 0 || (frame_bytes % 16) || pool_n <= 0 || !pool || !clock || !obs || !rewards || !dones ||
-      (slot != 0 && slot != 1) || ((uintptr_t)pool % 16) || ((uintptr_t)obs % 16) || ((uintptr_t)clock % 16))
+      (slot != 0 && slot != 1) || !mirl::aligned16(pool, obs, clock))
     return mirl::fail(MIRL_ERR_ARG, "bad synth_env_step arguments (16-byte aligned frame rows, slot 0 | 1)");
   mirl::ActorPreArgs p;
   int rc = fill_pre(p, E, H, A, actions, h, c, xh_tail, xh_pitch, c_in, state_pack, initials, rewards_out, dones_out, clip_rewards,
@@ -255,7 +255,7 @@ extern "C" int mirl_synth_env_step_pre(int32_t E, int64_t frame_bytes, const uin
 extern "C" int mirl_stack_shift(int32_t E, int32_t P, int32_t plane_bytes, const uint8_t* in, uint8_t* out, const uint8_t* newest,
                                 const uint8_t* dones, void* stream) {
   if (E <= 0 || P <= 1 || plane_bytes <= 0 || (plane_bytes % 16) || !in || !out || !newest || !dones || in == out ||
-      ((uintptr_t)in % 16) || ((uintptr_t)out % 16) || ((uintptr_t)newest % 16))
+      !mirl::aligned16(in, out, newest))
     return mirl::fail(MIRL_ERR_ARG, "bad stack_shift arguments (16-byte aligned planes, out != in)");
   const int pq = plane_bytes / 16;
   int gx = (P * pq + 255) / 256; if (gx > 8) gx = 8;

@@ -598,8 +598,6 @@ k_act_hidden(ActHiddenArgs a) {
 
 using namespace mirl;
 
-static bool an_al16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
 extern "C" int mirl_act_conv_supported(int32_t layer, int32_t Ci, int32_t Co, int32_t k, int32_t stride, int32_t Hi, int32_t Wi) {
   if (Co != 64 || Hi < k || Wi < k) return 0;
   if (layer == 2) return Ci == 32 && k == 4 && stride == 2;
@@ -616,7 +614,7 @@ extern "C" int mirl_act_conv_fwd(int32_t layer, int64_t frames, int32_t Hi, int3
   ActConvArgs a;
   a.x = x; a.w = w_taps; a.bias = bias; a.y = y; a.y_frame_pitch = y_frame_pitch;
   a.frames = (int)frames; a.Hi = Hi; a.Wi = Wi; a.Ho = (Hi - k) / s + 1; a.Wo = (Wi - k) / s + 1;
-  if (y_frame_pitch < (int64_t)a.Ho * a.Wo * 64 || !an_al16(x) || !an_al16(w_taps))
+  if (y_frame_pitch < (int64_t)a.Ho * a.Wo * 64 || !aligned16(x, w_taps))
     return fail(MIRL_ERR_ARG, "act_conv_fwd: 16-byte aligned x / w and a frame pitch >= Ho*Wo*64 are required");
   const int64_t M = frames * a.Ho * a.Wo;
   hipStream_t st = (hipStream_t)stream;
@@ -625,20 +623,12 @@ extern "C" int mirl_act_conv_fwd(int32_t layer, int64_t frames, int32_t Hi, int3
   static const int wlds_env = getenv("MIRL_ACT_CONV_WLDS") ? atoi(getenv("MIRL_ACT_CONV_WLDS")) : 1;
   if (M >= 6144 && wlds_env) {
     // hundreds of frames: weights resident in LDS, one persistent workgroup per CU (k_act_conv_wlds)
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const int64_t tiles = (M + 15) / 16;
-    unsigned grid = (unsigned)((tiles + 3) / 4); if (grid > (unsigned)cus) grid = (unsigned)cus;
+    const unsigned grid = capped_grid((tiles + 3) / 4, cu_count() ? cu_count() : 256);
     const size_t lds = sizeof(float) * 64 * (size_t)(k * k * Ci + 4);
-    static bool raised[2] = {false, false};
-    if (layer == 2) {
-      if (!raised[0]) { MIRL_HIP(hipFuncSetAttribute((const void*)k_act_conv_wlds<32, 4, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); raised[0] = true; }
-      hipLaunchKernelGGL((k_act_conv_wlds<32, 4, 4, 2>), dim3(grid), dim3(512), lds, st, a);
-    } else {
-      if (!raised[1]) { MIRL_HIP(hipFuncSetAttribute((const void*)k_act_conv_wlds<64, 3, 3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); raised[1] = true; }
-      hipLaunchKernelGGL((k_act_conv_wlds<64, 3, 3, 1>), dim3(grid), dim3(512), lds, st, a);
-    }
+    const auto kw = layer == 2 ? k_act_conv_wlds<32, 4, 4, 2> : k_act_conv_wlds<64, 3, 3, 1>;
+    if (int rc = raise_lds_limit(kw, 160 * 1024)) return rc;
+    hipLaunchKernelGGL(kw, dim3(grid), dim3(512), lds, st, a);
     MIRL_LAUNCH_CHECK();
     return MIRL_OK;
   }
@@ -685,7 +675,7 @@ extern "C" int mirl_act_lstm_fwd(int32_t E, int32_t H, int32_t K, const float* x
                                  const float* c_in, float* h_out, float* c_out, void* workspace, void* stream) {
   if (!xh || !w || !bias || !c_in || !h_out || !c_out || !workspace) return fail(MIRL_ERR_ARG, "bad act_lstm_fwd arguments");
   if (!mirl_act_lstm_supported(E, H, K)) return fail(MIRL_ERR_ARG, "act_lstm_fwd: E <= 64, H % 8 == 0 and K % 16 == 0 are required");
-  if (xh_pitch < K || (xh_pitch % 4) || !an_al16(xh) || !an_al16(w) || !an_al16(workspace)) return fail(MIRL_ERR_ARG, "act_lstm_fwd: 16-byte aligned rows are required");
+  if (xh_pitch < K || (xh_pitch % 4) || !aligned16(xh, w, workspace)) return fail(MIRL_ERR_ARG, "act_lstm_fwd: 16-byte aligned rows are required");
   ActLstmArgs a;
   a.xh = xh; a.xh_pitch = xh_pitch; a.w = w; a.bias = bias; a.c_in = c_in; a.h_out = h_out; a.c_out = c_out;
   a.E = E; a.H = H; a.K = K;
@@ -700,8 +690,7 @@ extern "C" int mirl_act_lstm_fwd(int32_t E, int32_t H, int32_t K, const float* x
   if (rt == 1) hipLaunchKernelGGL(k_act_lstm<1>, grid, dim3(512), lds, st, a);
   else if (rt == 2) hipLaunchKernelGGL(k_act_lstm<2>, grid, dim3(512), lds, st, a);
   else {
-    static bool raised = false;
-    if (!raised) { MIRL_HIP(hipFuncSetAttribute((const void*)k_act_lstm<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)); raised = true; }
+    if (int rc = raise_lds_limit(k_act_lstm<4>, 96 * 1024)) return rc;
     hipLaunchKernelGGL(k_act_lstm<4>, grid, dim3(512), lds, st, a);
   }
   MIRL_LAUNCH_CHECK();
@@ -724,7 +713,7 @@ extern "C" int mirl_act_head_parts(int32_t HID, int32_t NO, int32_t* parts, int3
 extern "C" int mirl_act_embed(int32_t E, int32_t N, int32_t H, int32_t D, const float* h, const float* freq, const float* taus,
                               uint64_t seed, const uint64_t* step, const float* wq, const float* bq, float* x, float* tau_out, void* stream) {
   if (E <= 0 || N <= 0 || H <= 0 || (H % 16) || D <= 0 || (D % 16) || D > 64 || !h || !freq || !wq || !bq || !x || (!taus && !step) ||
-      (int64_t)E * N > (1 << 24) || !an_al16(wq) || !an_al16(h) || !an_al16(bq) || !an_al16(x))
+      (int64_t)E * N > (1 << 24) || !aligned16(wq, h, bq, x))
     return fail(MIRL_ERR_ARG, "bad act_embed arguments (H % 16, D in {16, 32, 48, 64}, taus or a step word, 16-byte aligned h / wq / bq / x)");
   ActEmbedArgs a;
   a.h = h; a.freq = freq; a.taus = taus; a.wq = wq; a.bq = bq; a.x = x; a.tau_out = tau_out; a.seed = seed; a.step = step;
@@ -757,7 +746,7 @@ static int fill_select(ActSelectArgs& q, int32_t E, int32_t N, int32_t A, int32_
                        int32_t has_val, const double* eps, const double* expo, double eps_min, uint64_t rng_seed, const uint64_t* rng_step,
                        int32_t* actions, float* qvalues) {
   if (E <= 0 || N <= 0 || A <= 0 || A + (has_val ? 1 : 0) > pitch || pitch > 32 || (pitch % 8) || parts <= 0 || !part || !bout || !actions ||
-      !qvalues || (eps && !rng_step) || !an_al16(part) || (int64_t)parts * E * N * pitch * 4 >= (1LL << 31))
+      !qvalues || (eps && !rng_step) || !aligned16(part) || (int64_t)parts * E * N * pitch * 4 >= (1LL << 31))
     return fail(MIRL_ERR_ARG, "bad act_head_select arguments");
   q.part = part; q.bout = bout; q.eps = eps; q.expo = expo; q.eps_min = eps_min; q.rng_seed = rng_seed; q.rng_step = rng_step;
   q.actions = actions; q.qvalues = qvalues; q.E = E; q.N = N; q.A = A; q.P = parts; q.has_val = has_val ? 1 : 0;
@@ -783,7 +772,7 @@ static int fill_hidden(ActHiddenArgs& a, int32_t R, int32_t H, int32_t HID, int3
                        const float* wout, float* part) {
   if (!x || !wfc || !bfc || !wout || !part || R <= 0) return fail(MIRL_ERR_ARG, "bad act_head_hidden arguments");
   if (!mirl_act_head_supported(R, 1, H, 0, HID, NO)) return fail(MIRL_ERR_ARG, "act_head_hidden: unsupported shape (H in {64 .. 1024} a power of two, HID % 16; NO <= 32)");
-  if (!an_al16(x) || !an_al16(wfc) || !an_al16(wout) || !an_al16(part) || (HID % 4)) return fail(MIRL_ERR_ARG, "act_head_hidden: 16-byte aligned operands are required");
+  if (!aligned16(x, wfc, wout, part) || (HID % 4)) return fail(MIRL_ERR_ARG, "act_head_hidden: 16-byte aligned operands are required");
   a.x = x; a.wfc = wfc; a.bfc = bfc; a.wout = wout; a.part = part;
   a.R = R; a.H = H; a.HID = HID; a.NO = NO; a.NOP = (NO + 7) / 8 * 8;
   return MIRL_OK;

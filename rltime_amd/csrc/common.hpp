@@ -1,12 +1,14 @@
-// common.hpp — error plumbing and the pinned->device parameter staging ring.
+// common.hpp — error plumbing, the launchers' shared host helpers and the pinned->device parameter staging ring.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/mirl.h"
+#include "host_util.hpp"
 
 namespace mirl {
 
@@ -26,6 +28,31 @@ inline int fail(int code, const std::string& msg) { last_error_ref() = msg; retu
     if (_e != hipSuccess)                                                      \
       return ::mirl::fail(MIRL_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(_e)); \
   } while (0)
+
+// The two helpers below remember their answer for the process.  The assumption, made here once for every launcher: ONE
+// device per process, driven from one caller thread — neither a kernel's limit nor the CU count is keyed by device.
+
+// Allow `fn` up to `bytes` of dynamic LDS (above the 64 KB a kernel gets unasked).  Set on the first call per kernel.
+inline int raise_lds_limit(const void* fn, size_t bytes) {
+  static std::unordered_set<const void*> raised;
+  if (raised.count(fn)) return MIRL_OK;
+  MIRL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  raised.insert(fn);
+  return MIRL_OK;
+}
+template <typename K>
+inline int raise_lds_limit(K* kernel, size_t bytes) { return raise_lds_limit((const void*)kernel, bytes); }
+
+// compute units of the device (0 if it cannot be asked)
+inline int cu_count() {
+  static int cus = -1;
+  if (cus < 0) {
+    int dev = 0;
+    cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
+  }
+  return cus;
+}
 
 // Small host->device parameter blocks (op lists, rng draws) travel through a
 // ring of pinned host buffers with a matching device buffer each, copied with

@@ -193,8 +193,7 @@ extern "C" int mirl_conv3_fwd(int64_t N, int32_t H, int32_t W, int32_t C, int32_
   using namespace mirl;
   if (N <= 0 || !x || !w || !y) return fail(MIRL_ERR_ARG, "bad conv3_fwd arguments");
   if (!mirl_conv3_fwd_supported(C, F, KH, KW, S, H, W)) return fail(MIRL_ERR_ARG, "conv3_fwd: unsupported layer shape");
-  if (((uintptr_t)x % 16) || ((uintptr_t)w % 16) || ((uintptr_t)y % 16) || (bias && ((uintptr_t)bias % 16)))
-    return fail(MIRL_ERR_ARG, "conv3_fwd: pointers must be 16-byte aligned");
+  if (!aligned16(x, w, y, bias)) return fail(MIRL_ERR_ARG, "conv3_fwd: pointers must be 16-byte aligned");
   const int OH = (H - KH) / S + 1, OW = (W - KW) / S + 1;
   const int64_t M = N * OH * OW;
   if (M >= (1LL << 31) * 256) return fail(MIRL_ERR_ARG, "conv3_fwd: too many output positions for one launch");
@@ -203,8 +202,7 @@ extern "C" int mirl_conv3_fwd(int64_t N, int32_t H, int32_t W, int32_t C, int32_
   g.H = H; g.W = W; g.C = C; g.OH = OH; g.OW = OW; g.S = S;
   g.seg_steps = KW * C / 16; g.seg_jump = (int64_t)(W - KW) * C; g.relu = relu ? 1 : 0;
   hipStream_t st = (hipStream_t)stream;
-  static bool attr = false;
-  if (!attr) { MIRL_HIP(hipFuncSetAttribute((const void*)k_conv3_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, C3_LDS)); attr = true; }
+  if (int rc = raise_lds_limit(k_conv3_fwd, C3_LDS)) return rc;
   ProfScope ps("k_conv3_fwd", 4.0 * ((double)N * H * W * C + (double)M * F + (double)F * g.K), st, 2.0 * (double)M * F * g.K);
   hipLaunchKernelGGL(k_conv3_fwd, dim3((unsigned)((M + 255) / 256)), dim3(512), C3_LDS, st, g);
   MIRL_LAUNCH_CHECK();

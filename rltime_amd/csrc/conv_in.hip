@@ -66,12 +66,29 @@ k_conv1_pack_w(const float* __restrict__ w, int64_t so, int64_t sc, int64_t sh, 
 
 __device__ __forceinline__ float c1_byte(uint32_t v, int b) { return (float)((v >> (8 * b)) & 0xffu); }
 
+// LDS fill of the forward and f32-pipe weight-gradient kernels: `frames` frames x 4 planes from frame n0 on are one
+// contiguous run of 16 B vectors in HBM; only the LDS side has the padded plane pitch.  C1_LD loads in flight per lane.
+// Uses the kernel's x, n0, frames, HW, hw16, tid and c1_lds.  (A macro, not a function: as an inlined function the
+// kernels come out with another register allocation.)
+#define C1_STAGE(pitch_)                                                                        \
+  {                                                                                             \
+    const int vecs = frames * C1_PLANES * hw16;                                                 \
+    const uint4* s4 = reinterpret_cast<const uint4*>(x + (int64_t)n0 * (C1_PLANES * HW));       \
+    for (int o0 = tid; o0 < vecs; o0 += 256 * C1_LD) {                                          \
+      uint4 v[C1_LD];                                                                           \
+      _Pragma("unroll") for (int k = 0; k < C1_LD; ++k) { const int o = o0 + k * 256; v[k] = s4[o < vecs ? o : vecs - 1]; } \
+      _Pragma("unroll") for (int k = 0; k < C1_LD; ++k) {                                       \
+        const int o = o0 + k * 256;                                                             \
+        if (o < vecs) { const int pl = o / hw16; *reinterpret_cast<uint4*>(c1_lds + pl * pitch_ + (o - pl * hw16) * 16) = v[k]; } \
+      }                                                                                         \
+    }                                                                                           \
+  }
+
 // x: uint8 [N][4][H][W]; y: float [N][OH][OW][32] (NHWC memory of the logical
 // (N, 32, OH, OW) tensor).  Work unit u = (frame group, part): a group is FPI
 // consecutive frames, `split` parts share a group's tiles (split > 1 only for
 // small N, to spread few frames over the chip).  NTS: non-temporal output stores.
-// DBG: timing experiments only (tools/conv_in_probe.py): bit 0 no u8->f32
-// conversion, bit 1 no output stores, bit 2 no refill after the first unit.
+// BULK: all conversions of a tile in front of its MFMA chain.
 //
 // VALU work next to the MFMA chain is NOT free here (both are issued through the
 // SIMD's one VALU port; measured: the 64 conversions + 64 scale multiplies per tile
@@ -93,6 +110,29 @@ __device__ __forceinline__ float c1_byte(uint32_t v, int b) { return (float)((v 
     px_[2 * kh] = *reinterpret_cast<const uint32_t*>(base_ + kh * W);                           \
     px_[2 * kh + 1] = *reinterpret_cast<const uint32_t*>(base_ + kh * W + 4);                   \
   }
+// a wave's tiles tt, tt + step, ... < tend, each through COMPUTE_(pixel words, frame, position): two tiles per trip
+// with ping-pong pixel registers, the next tile's LDS reads issued ahead of the current tile's chain
+#define C1_TILE_WALK(COMPUTE_)                                                                  \
+  {                                                                                             \
+    uint32_t pxa[2 * C1_K], pxb[2 * C1_K];                                                      \
+    int fa, pa, fb = 0, pb = 0;                                                                 \
+    const uint8_t* base;                                                                        \
+    C1_TILE_ADDR(tt, fa, pa, base);                                                             \
+    C1_TILE_READ(base, pxa);                                                                    \
+    for (;;) {                                                                                  \
+      const bool more_b = tt + step < tend;                                                     \
+      if (more_b) { C1_TILE_ADDR(tt + step, fb, pb, base); C1_TILE_READ(base, pxb); }           \
+      __builtin_amdgcn_sched_barrier(0);            /* LDS words of the next tile in flight before this chain */ \
+      COMPUTE_(pxa, fa, pa);                                                                    \
+      if (!more_b) break;                                                                       \
+      tt += 2 * step;                                                                           \
+      const bool more_a = tt < tend;                                                            \
+      if (more_a) { C1_TILE_ADDR(tt, fa, pa, base); C1_TILE_READ(base, pxa); }                  \
+      __builtin_amdgcn_sched_barrier(0);                                                        \
+      COMPUTE_(pxb, fb, pb);                                                                    \
+      if (!more_a) break;                                                                       \
+    }                                                                                           \
+  }
 // one tile: 128 MFMAs on two accumulator chains, then + bias, ReLU, two 16 B stores
 #define C1_TILE_COMPUTE(px_, f_, p_)                                                            \
   {                                                                                             \
@@ -100,13 +140,13 @@ __device__ __forceinline__ float c1_byte(uint32_t v, int b) { return (float)((v 
     float vv_[C1_TAPS];                                                                         \
     /* tap s = kh*8 + kw: word kh*2 + (kw>>2), byte kw&3 */                                     \
     _Pragma("unroll") for (int s = 0; s < C1_TAPS; ++s)                                         \
-      vv_[s] = (DBG & 1) ? __uint_as_float(px_[s >> 2] & 0x3fffffffu) : c1_byte(px_[s >> 2], s & 3); \
+      vv_[s] = c1_byte(px_[s >> 2], s & 3);                                                     \
     if (BULK) __builtin_amdgcn_sched_barrier(0);   /* all conversions before the chain */       \
     _Pragma("unroll") for (int s = 0; s < C1_TAPS; ++s) {                                       \
       a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wr0[s], vv_[s], a0, 0, 0, 0);                   \
       a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wr1[s], vv_[s], a1, 0, 0, 0);                   \
     }                                                                                           \
-    if ((DBG & 2) ? (a0.x == 12345.678f) : (p_ < OHW)) {                                        \
+    if (p_ < OHW) {                                                                             \
       cv_f4 o0 = a0 + b0, o1 = a1 + b1;                                                         \
       o0.x = o0.x > 0.f ? o0.x : 0.f; o0.y = o0.y > 0.f ? o0.y : 0.f; o0.z = o0.z > 0.f ? o0.z : 0.f; o0.w = o0.w > 0.f ? o0.w : 0.f; \
       o1.x = o1.x > 0.f ? o1.x : 0.f; o1.y = o1.y > 0.f ? o1.y : 0.f; o1.z = o1.z > 0.f ? o1.z : 0.f; o1.w = o1.w > 0.f ? o1.w : 0.f; \
@@ -116,7 +156,7 @@ __device__ __forceinline__ float c1_byte(uint32_t v, int b) { return (float)((v 
     }                                                                                           \
   }
 
-template <int FPI, int NTS, int DBG, int BULK = 0>
+template <int FPI, int NTS, int BULK = 0>
 __global__ void __launch_bounds__(256, 2)
 k_conv1_u8_fwd(int N, int H, int W, int OH, int OW, unsigned ow_magic, int pitch, int split, const uint8_t* __restrict__ x,
                const float* __restrict__ wpk, const float* __restrict__ bias, float* __restrict__ y) {
@@ -134,52 +174,16 @@ k_conv1_u8_fwd(int N, int H, int W, int OH, int OW, unsigned ow_magic, int pitch
     const int group = split == 1 ? u : u / split, part = u - group * split;
     const int n0 = group * FPI;
     const int frames = N - n0 < FPI ? N - n0 : FPI;
-    if (!first && !(DBG & 4)) __syncthreads();      // every wave is done reading the previous frames
-    if (first || !(DBG & 4)) {
-      // the unit's frames x 4 planes are one contiguous run of 16 B vectors in HBM; only
-      // the LDS side has the padded plane pitch.  C1_LD loads in flight per lane.
-      const int vecs = frames * C1_PLANES * hw16;
-      const uint4* s4 = reinterpret_cast<const uint4*>(x + (int64_t)n0 * (C1_PLANES * HW));
-      for (int o0 = tid; o0 < vecs; o0 += 256 * C1_LD) {
-        uint4 v[C1_LD];
-#pragma unroll
-        for (int k = 0; k < C1_LD; ++k) { const int o = o0 + k * 256; v[k] = s4[o < vecs ? o : vecs - 1]; }
-#pragma unroll
-        for (int k = 0; k < C1_LD; ++k) {
-          const int o = o0 + k * 256;
-          if (o < vecs) { const int pl = o / hw16; *reinterpret_cast<uint4*>(c1_lds + pl * pitch + (o - pl * hw16) * 16) = v[k]; }
-        }
-      }
-      __syncthreads();
-    }
+    if (!first) __syncthreads();      // every wave is done reading the previous frames
     first = false;
-    // this wave's tiles: tt = part*4 + wave, + step, ... < frames * tiles; two tiles per
-    // trip with ping-pong pixel registers, the next tile's LDS reads issued ahead
+    C1_STAGE(pitch);
+    __syncthreads();
     const int tend = frames * tiles;
-    int tt = part * 4 + wave;
+    int tt = part * 4 + wave;      // this wave's tiles: tt, + step, ... < frames * tiles
     if (tt >= tend) continue;
-    uint32_t pxa[2 * C1_K], pxb[2 * C1_K];
-    int fa, pa, fb = 0, pb = 0;
-    const uint8_t* base;
-    C1_TILE_ADDR(tt, fa, pa, base);
-    C1_TILE_READ(base, pxa);
-    for (;;) {
-      const bool more_b = tt + step < tend;
-      if (more_b) { C1_TILE_ADDR(tt + step, fb, pb, base); C1_TILE_READ(base, pxb); }
-      __builtin_amdgcn_sched_barrier(0);            // LDS words of the next tile in flight before this chain
-      C1_TILE_COMPUTE(pxa, fa, pa);
-      if (!more_b) break;
-      tt += 2 * step;
-      const bool more_a = tt < tend;
-      if (more_a) { C1_TILE_ADDR(tt, fa, pa, base); C1_TILE_READ(base, pxa); }
-      __builtin_amdgcn_sched_barrier(0);
-      C1_TILE_COMPUTE(pxb, fb, pb);
-      if (!more_a) break;
-    }
+    C1_TILE_WALK(C1_TILE_COMPUTE);
   }
 }
-#undef C1_TILE_ADDR
-#undef C1_TILE_READ
 #undef C1_TILE_COMPUTE
 
 // ---------------------------------------------------------------------------
@@ -193,14 +197,6 @@ k_conv1_u8_fwd(int N, int H, int W, int OH, int OW, unsigned ow_magic, int pitch
 // (2 x 16 x 4 VGPRs), the lo parts in LDS (16 KB, one ds_read_b128 per MFMA); the three parts accumulate on
 // separate chains and are added smallest first.  Byte -> bf16 is v_cvt_f32_ubyteN + one v_perm_b32 per pair (the
 // upper half of the f32 is the exact bf16).  Staging, tile walk and epilogue are the f32 kernel's.
-typedef __bf16 cv_bf8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ unsigned c1_pk_bf(float lo, float hi) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
 // wpk3[((part*2 + m)*8 + kh)*64 + lane] = 8 bf16 (kw = 0..7) of part `part` of w[f][c][kh][kw] * scale with the
 // A-operand lane map row i = lane & 15 -> filter f = (i>>2)*8 + m*4 + (i&3) (as k_conv1_pack_w), k group lane >> 4 = c
 __global__ void __launch_bounds__(256)
@@ -210,23 +206,19 @@ k_conv1_pack_w3(const float* __restrict__ w, int64_t so, int64_t sc, int64_t sh,
   const int lane = t & 63, kh = (t >> 6) & 7, m = t >> 9;
   const int i = lane & 15, c = lane >> 4;
   const int f = (i >> 2) * 8 + m * 4 + (i & 3);
-  unsigned ph[4], pm[4], pl[4];
+  float v[2][4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float x0 = w[f * so + c * sc + kh * sh + (2 * e) * sw] * scale, x1 = w[f * so + c * sc + kh * sh + (2 * e + 1) * sw] * scale;
-    ph[e] = c1_pk_bf(x0, x1);
-    const float r0 = x0 - __uint_as_float(ph[e] << 16), r1 = x1 - __uint_as_float(ph[e] & 0xffff0000u);
-    pm[e] = c1_pk_bf(r0, r1);
-    const float s0 = r0 - __uint_as_float(pm[e] << 16), s1 = r1 - __uint_as_float(pm[e] & 0xffff0000u);
-    pl[e] = c1_pk_bf(s0, s1);
-  }
+  for (int kw = 0; kw < C1_K; ++kw) v[kw >> 2][kw & 3] = w[f * so + c * sc + kh * sh + kw * sw] * scale;
+  uint2 h0, m0, l0, h1, m1, l1;
+  g3_split4(v[0], h0, m0, l0);
+  g3_split4(v[1], h1, m1, l1);
   const int o = (m * 8 + kh) * 64 + lane;
-  wpk3[o] = make_uint4(ph[0], ph[1], ph[2], ph[3]);
-  wpk3[16 * 64 + o] = make_uint4(pm[0], pm[1], pm[2], pm[3]);
-  wpk3[32 * 64 + o] = make_uint4(pl[0], pl[1], pl[2], pl[3]);
+  wpk3[o] = make_uint4(h0.x, h0.y, h1.x, h1.y);
+  wpk3[16 * 64 + o] = make_uint4(m0.x, m0.y, m1.x, m1.y);
+  wpk3[32 * 64 + o] = make_uint4(l0.x, l0.y, l1.x, l1.y);
 }
 
-__device__ __forceinline__ cv_bf8 c1_as_bf8(uint4 v) { return __builtin_bit_cast(cv_bf8, v); }
+__device__ __forceinline__ g3_bf16x8 c1_as_bf8(uint4 v) { return __builtin_bit_cast(g3_bf16x8, v); }
 
 // bytes (2e, 2e+1) of v -> two bf16 in one dword
 __device__ __forceinline__ unsigned c1_bytes_bf(uint32_t v, int e) {
@@ -234,24 +226,11 @@ __device__ __forceinline__ unsigned c1_bytes_bf(uint32_t v, int e) {
   return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
 }
 
-#define C1_TILE_ADDR(tt_, f_, p_, base_)                                                        \
-  {                                                                                             \
-    f_ = (FPI > 1 && tt_ >= tiles) ? 1 : 0;                                                     \
-    p_ = (tt_ - f_ * tiles) * 16 + j;                                                           \
-    const int pc_ = p_ < OHW ? p_ : OHW - 1;                                                    \
-    const int oh_ = OW == 1 ? pc_ : (int)__umulhi((unsigned)pc_, ow_magic);                     \
-    base_ = c1_lds + (f_ * C1_PLANES + kq) * pitch + (oh_ * C1_S) * W + (pc_ - oh_ * OW) * C1_S; \
-  }
-#define C1_TILE_READ(base_, px_)                                                                \
-  _Pragma("unroll") for (int kh = 0; kh < C1_K; ++kh) {                                         \
-    px_[2 * kh] = *reinterpret_cast<const uint32_t*>(base_ + kh * W);                           \
-    px_[2 * kh + 1] = *reinterpret_cast<const uint32_t*>(base_ + kh * W + 4);                   \
-  }
 #define C1B_TILE_COMPUTE(px_, f_, p_)                                                           \
   {                                                                                             \
     cv_f4 h0 = {0.f, 0.f, 0.f, 0.f}, m0 = h0, l0 = h0, h1 = h0, m1 = h0, l1 = h0;               \
     _Pragma("unroll") for (int kh = 0; kh < C1_K; ++kh) {                                       \
-      const cv_bf8 b_ = c1_as_bf8(make_uint4(c1_bytes_bf(px_[2 * kh], 0), c1_bytes_bf(px_[2 * kh], 1),       \
+      const g3_bf16x8 b_ = c1_as_bf8(make_uint4(c1_bytes_bf(px_[2 * kh], 0), c1_bytes_bf(px_[2 * kh], 1),       \
                                              c1_bytes_bf(px_[2 * kh + 1], 0), c1_bytes_bf(px_[2 * kh + 1], 1))); \
       l0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c1_as_bf8(wlo[kh * 64 + lane]), b_, l0, 0, 0, 0);          \
       l1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c1_as_bf8(wlo[(C1_K + kh) * 64 + lane]), b_, l1, 0, 0, 0); \
@@ -277,7 +256,7 @@ k_conv1_u8_fwd_bf(int N, int H, int W, int OH, int OW, unsigned ow_magic, int pi
   extern __shared__ __align__(16) uint8_t c1_lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 15, kq = lane >> 4;
-  cv_bf8 wh0[C1_K], wh1[C1_K], wm0[C1_K], wm1[C1_K];
+  g3_bf16x8 wh0[C1_K], wh1[C1_K], wm0[C1_K], wm1[C1_K];
 #pragma unroll
   for (int kh = 0; kh < C1_K; ++kh) {
     wh0[kh] = c1_as_bf8(wpk3[kh * 64 + lane]);             wh1[kh] = c1_as_bf8(wpk3[(C1_K + kh) * 64 + lane]);
@@ -296,46 +275,17 @@ k_conv1_u8_fwd_bf(int N, int H, int W, int OH, int OW, unsigned ow_magic, int pi
     const int frames = N - n0 < FPI ? N - n0 : FPI;
     if (!first) __syncthreads();      // every wave is done reading the previous frames
     first = false;
-    {
-      const int vecs = frames * C1_PLANES * hw16;
-      const uint4* s4 = reinterpret_cast<const uint4*>(x + (int64_t)n0 * (C1_PLANES * HW));
-      for (int o0 = tid; o0 < vecs; o0 += 256 * C1_LD) {
-        uint4 v[C1_LD];
-#pragma unroll
-        for (int k = 0; k < C1_LD; ++k) { const int o = o0 + k * 256; v[k] = s4[o < vecs ? o : vecs - 1]; }
-#pragma unroll
-        for (int k = 0; k < C1_LD; ++k) {
-          const int o = o0 + k * 256;
-          if (o < vecs) { const int pl = o / hw16; *reinterpret_cast<uint4*>(c1_lds + pl * pitch + (o - pl * hw16) * 16) = v[k]; }
-        }
-      }
-      __syncthreads();
-    }
+    C1_STAGE(pitch);
+    __syncthreads();
     const int tend = frames * tiles;
     int tt = part * 4 + wave;
     if (tt >= tend) continue;
-    uint32_t pxa[2 * C1_K], pxb[2 * C1_K];
-    int fa, pa, fb = 0, pb = 0;
-    const uint8_t* base;
-    C1_TILE_ADDR(tt, fa, pa, base);
-    C1_TILE_READ(base, pxa);
-    for (;;) {
-      const bool more_b = tt + step < tend;
-      if (more_b) { C1_TILE_ADDR(tt + step, fb, pb, base); C1_TILE_READ(base, pxb); }
-      __builtin_amdgcn_sched_barrier(0);            // LDS words of the next tile in flight before this chain
-      C1B_TILE_COMPUTE(pxa, fa, pa);
-      if (!more_b) break;
-      tt += 2 * step;
-      const bool more_a = tt < tend;
-      if (more_a) { C1_TILE_ADDR(tt, fa, pa, base); C1_TILE_READ(base, pxa); }
-      __builtin_amdgcn_sched_barrier(0);
-      C1B_TILE_COMPUTE(pxb, fb, pb);
-      if (!more_a) break;
-    }
+    C1_TILE_WALK(C1B_TILE_COMPUTE);
   }
 }
 #undef C1_TILE_ADDR
 #undef C1_TILE_READ
+#undef C1_TILE_WALK
 #undef C1B_TILE_COMPUTE
 
 // ---------------------------------------------------------------------------
@@ -426,20 +376,7 @@ k_conv1_u8_wrw(int N, int H, int W, int OH, int OW, unsigned ow_magic, int pitch
     const int frames = N - n0 < FPI ? N - n0 : FPI;
     if (!first) __syncthreads();
     first = false;
-    {
-      const int vecs = frames * C1_PLANES * hw16;
-      const uint4* s4 = reinterpret_cast<const uint4*>(x + (int64_t)n0 * (C1_PLANES * HW));
-      for (int o0 = tid; o0 < vecs; o0 += 256 * C1_LD) {
-        uint4 v[C1_LD];
-#pragma unroll
-        for (int k = 0; k < C1_LD; ++k) { const int o = o0 + k * 256; v[k] = s4[o < vecs ? o : vecs - 1]; }
-#pragma unroll
-        for (int k = 0; k < C1_LD; ++k) {
-          const int o = o0 + k * 256;
-          if (o < vecs) { const int pl = o / hw16; *reinterpret_cast<uint4*>(c1_lds + pl * Pd + (o - pl * hw16) * 16) = v[k]; }
-        }
-      }
-    }
+    C1_STAGE(Pd);
     __syncthreads();
     const int bend = frames * blocks;
     int bb = wave;
@@ -497,6 +434,7 @@ k_conv1_u8_wrw(int N, int H, int W, int OH, int OW, unsigned ow_magic, int pitch
 }
 #undef C1_WRW_LOAD
 #undef C1_WRW_COMPUTE
+#undef C1_STAGE
 
 // ---------------------------------------------------------------------------------------------------------------
 // The same weight gradient on the bf16 matrix pipe, still an f32 result (the forward's argument turned around): a uint8
@@ -726,16 +664,52 @@ static int c1_wrw_b3(int64_t N, int32_t H, int32_t W, const uint8_t* x, const fl
   size_t lds = (size_t)C1_PLANES * Pd * 2;
   if (lds > 80 * 1024) return MIRL_OK;                             // two workgroups per CU or the f32-pipe kernel
   if (lds < (size_t)slab * 4) lds = (size_t)slab * 4;              // the workgroup's partial is reduced there
-  const unsigned grid = (unsigned)(N < 512 ? N : 512);
-  static bool attr[2] = {false, false};
-  const void* fn = (const void*)k_conv1_u8_wrw_b3<MASK>;
-  if (!attr[MASK]) { MIRL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024)); attr[MASK] = true; }
+  const unsigned grid = capped_grid(N, 512);
+  if (int rc = raise_lds_limit(k_conv1_u8_wrw_b3<MASK>, 80 * 1024)) return rc;
   ProfScope ps("k_conv1_u8_wrw_b3", (double)N * (C1_PLANES * HW + (MASK ? 2.0 : 1.0) * OH * OW * C1_F * 4), st,
                (double)N * OH * OW * 2.0 * C1_PLANES * C1_K * C1_K * C1_F);
   hipLaunchKernelGGL((k_conv1_u8_wrw_b3<MASK>), dim3(grid), dim3(256), lds, st, (int)N, H, W, OH, OW, Pd, x, g, scratch, y, slab);
   MIRL_LAUNCH_CHECK();
   *grid_out = grid;
   *ran = true;
+  return MIRL_OK;
+}
+
+// Launcher behind mirl_conv1_u8_wrw_ex and mirl_conv1_u8_wrw_masked, which check the arguments.  MASK: g is the gradient
+// w.r.t. the layer's output, masked by y > 0 while it is loaded, and db receives its column sums; a slab then carries C1_F
+// more floats.  f32_pipe / interleaved: flag bits 1 / 0 of mirl_conv1_u8_wrw_ex.
+template <bool MASK>
+static int c1_wrw(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* g, const float* y, float scale, float* scratch,
+                  float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w, float* db, bool f32_pipe, bool interleaved,
+                  hipStream_t st) {
+  const int OH = (H - C1_K) / C1_S + 1, OW = (W - C1_K) / C1_S + 1, HW = H * W, pitch = c1_pitch(HW);
+  const int slab = C1_DW + (MASK ? C1_F : 0);
+  bool b3 = false;
+  unsigned grid = 0;
+  if (!f32_pipe) {
+    if (int rc = c1_wrw_b3<MASK>(N, H, W, x, g, y, scratch, slab, &grid, st, &b3)) return rc;
+  }
+  if (!b3) {
+    const int fpi = (N >= 1024 && 2 * C1_PLANES * pitch <= 64 * 1024) ? 2 : 1;
+    grid = capped_grid((N + fpi - 1) / fpi, 512);
+    size_t lds = (size_t)fpi * C1_PLANES * pitch;
+    if (lds < (size_t)slab * 4) lds = (size_t)slab * 4;            // the workgroup's partial slab is reduced there
+    ProfScope ps("k_conv1_u8_wrw", (double)N * (C1_PLANES * HW + (MASK ? 2.0 : 1.0) * OH * OW * C1_F * 4), st,
+                 (double)N * OH * OW * 2.0 * C1_PLANES * C1_K * C1_K * C1_F);
+#define C1_WLAUNCH(FPI_, WC_, PC_, BULK_) \
+  hipLaunchKernelGGL((k_conv1_u8_wrw<FPI_, WC_, PC_, BULK_, MASK>), dim3(grid), dim3(256), lds, st, (int)N, H, W, OH, OW, magic_u32(OW), pitch, x, g, scratch, y, slab)
+    const bool atari = W == 84 && pitch == 7232;
+    if (fpi == 2 && atari && !interleaved) C1_WLAUNCH(2, 84, 7232, 1);
+    else if (fpi == 2 && atari) { if constexpr (!MASK) C1_WLAUNCH(2, 84, 7232, 0); }      // the interleaved schedule exists unmasked only
+    else if (fpi == 2) C1_WLAUNCH(2, 0, 0, 0);
+    else if (atari) C1_WLAUNCH(1, 84, 7232, 0);
+    else C1_WLAUNCH(1, 0, 0, 0);
+#undef C1_WLAUNCH
+    MIRL_LAUNCH_CHECK();
+  }
+  ProfScope ps("k_conv1_wrw_reduce", (double)grid * slab * 4, st);
+  hipLaunchKernelGGL(k_conv1_wrw_reduce, dim3((slab + 255) / 256), dim3(256), 0, st, scratch, (int)grid, scale, dw, ws_o, ws_c, ws_h, ws_w, slab, db);
+  MIRL_LAUNCH_CHECK();
   return MIRL_OK;
 }
 }  // namespace mirl
@@ -753,95 +727,64 @@ extern "C" int mirl_conv1_u8_supported(int32_t C, int32_t H, int32_t W, int32_t 
   return C1_PLANES * c1_pitch(H * W) <= 64 * 1024 ? 1 : 0;
 }
 
-// flags: bit 0 = plain (cached) output stores instead of non-temporal ones; bit 3 = skip the weight
-// packing (wpk was packed by an earlier call with the same weights and scale); bit 2 = byte->float
-// conversions interleaved with the MFMA chain instead of hoisted in front of it; bits 8.. =
-// frames per LDS fill override (1 or 2), bits 16.. = split override; bits 24-26 =
-// timing-experiment variants (see the kernel).
+// flags: bit 0 = plain (cached) output stores instead of non-temporal ones; bit 2 = byte->float conversions interleaved
+// with the MFMA chain instead of hoisted in front of it; bit 3 = skip the weight packing (wpk was packed by an earlier
+// call with the same weights and scale); bit 5 = the f32-MFMA kernel (probe / A-B); bits 8-15 = frames per LDS fill
+// override (1 or 2); bits 16-23 = split override.  Any other bit is refused.
 extern "C" int mirl_conv1_u8_fwd_ex(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* weight, int64_t ws_o,
                                     int64_t ws_c, int64_t ws_h, int64_t ws_w, const float* bias, float scale, float* wpk,
                                     float* y, int32_t flags, void* stream) {
   using namespace mirl;
   if (N <= 0 || N >= (1LL << 30) || !x || !weight || !bias || !wpk || !y) return fail(MIRL_ERR_ARG, "bad conv1_u8_fwd arguments");
   if (!mirl_conv1_u8_supported(C1_PLANES, H, W, C1_F, C1_K, C1_S)) return fail(MIRL_ERR_ARG, "conv1_u8_fwd: unsupported frame shape");
-  if (((uintptr_t)x % 16) || ((uintptr_t)y % 16) || ((uintptr_t)bias % 16) || ((uintptr_t)wpk % 16))
-    return fail(MIRL_ERR_ARG, "conv1_u8_fwd: pointers must be 16-byte aligned");
+  if (!aligned16(x, y, bias, wpk)) return fail(MIRL_ERR_ARG, "conv1_u8_fwd: pointers must be 16-byte aligned");
+  if (flags & ~(1 | 4 | 8 | 32 | 0xffff00)) return fail(MIRL_ERR_ARG, "conv1_u8_fwd: unknown flag bits");
+  const bool nts = !(flags & 1), interleaved = flags & 4, packed = flags & 8, f32_pipe = flags & 32;
+  int fpi = (flags >> 8) & 0xff, split = (flags >> 16) & 0xff;
   hipStream_t st = (hipStream_t)stream;
   const int OH = (H - C1_K) / C1_S + 1, OW = (W - C1_K) / C1_S + 1, HW = H * W, pitch = c1_pitch(HW);
   const int tiles = (OH * OW + 15) / 16;
   static const int bf_env0 = getenv("MIRL_CONV1_BF16") ? atoi(getenv("MIRL_CONV1_BF16")) : 1;
   const int bf_env = g_conv1_bf16 >= 0 ? g_conv1_bf16 : bf_env0;
-  const int dbg0 = (flags >> 24) & 7;
-  const bool bf = bf_env && !dbg0 && !(flags & 32) && !(flags & 4);      // bit 5: force the f32-MFMA kernel (probe / A-B)
+  const bool bf = bf_env && !f32_pipe && !interleaved;
   // which kernel's operand order a scratch block holds is remembered per pointer (host side, one caller thread per the
   // library's contract): a `packed` call whose kernel choice differs from the packing call's is refused instead of
   // reading a mismatched layout
   static std::unordered_map<const void*, int> packed_as;
-  if (flags & 8) {
+  if (packed) {                                           // wpk already holds these weights packed (acting steps between updates)
     auto it = packed_as.find((const void*)wpk);
     if (it == packed_as.end() || it->second != (bf ? 2 : 1))
       return fail(MIRL_ERR_STATE, "conv1_u8_fwd: flags bit 3 (weights already packed) but this scratch block was not packed by the same kernel variant");
   } else {
     packed_as[(const void*)wpk] = bf ? 2 : 1;
-  }
-  if (!(flags & 8)) {                                     // bit 3: wpk already holds these weights packed (acting steps between updates)
     ProfScope ps("k_conv1_pack_w", 2.0 * C1_WPK * 4, st);
     if (bf) hipLaunchKernelGGL(k_conv1_pack_w3, dim3(4), dim3(256), 0, st, weight, ws_o, ws_c, ws_h, ws_w, scale, (uint4*)wpk);
     else hipLaunchKernelGGL(k_conv1_pack_w, dim3((C1_WPK + 255) / 256), dim3(256), 0, st, weight, ws_o, ws_c, ws_h, ws_w, scale, wpk);
     MIRL_LAUNCH_CHECK();
   }
-  int fpi = (flags >> 8) & 0xff, split = (flags >> 16) & 0xff;
   if (fpi != 1 && fpi != 2) fpi = (N >= 1024 && 2 * C1_PLANES * pitch <= 64 * 1024) ? 2 : 1;
   if (fpi == 2 && 2 * C1_PLANES * pitch > 64 * 1024) fpi = 1;
   const int max_split = (tiles + 3) / 4;
   if (split <= 0) split = N >= 512 ? 1 : (int)((512 + N - 1) / N);
   if (split > max_split) split = max_split;
   if (fpi == 2) split = 1;
-  const int64_t units = (N + fpi - 1) / fpi * split;
-  const unsigned grid = (unsigned)(units < 512 ? units : 512);
+  const unsigned grid = capped_grid((N + fpi - 1) / fpi * split, 512);
   const size_t lds = (size_t)fpi * C1_PLANES * pitch + (bf ? 16 * 1024 : 0);
   ProfScope ps("k_conv1_u8_fwd", (double)N * (C1_PLANES * HW + (double)OH * OW * C1_F * 4), st,
                (double)N * OH * OW * 2.0 * C1_PLANES * C1_K * C1_K * C1_F);
-  const bool nts = !(flags & 1);
+#define C1_LAUNCH(KERNEL_, WPK_) \
+  hipLaunchKernelGGL(KERNEL_, dim3(grid), dim3(256), lds, st, (int)N, H, W, OH, OW, magic_u32(OW), pitch, split, x, WPK_, bias, y)
   if (bf) {
-    const uint4* w3 = (const uint4*)wpk;
-#define C1B_LAUNCH(FPI_, NTS_) \
-  hipLaunchKernelGGL((k_conv1_u8_fwd_bf<FPI_, NTS_>), dim3(grid), dim3(256), lds, st, (int)N, H, W, OH, OW, ow_magic_bf, pitch, split, x, w3, bias, y)
-    const unsigned ow_magic_bf = OW > 1 ? (unsigned)(((1ULL << 32) + OW - 1) / OW) : 0u;
-    static bool attr_set = false;
-    if (!attr_set) {                                        // 2 frames + 16 KB of weight parts = 74 KB of dynamic LDS
-      MIRL_HIP(hipFuncSetAttribute((const void*)k_conv1_u8_fwd_bf<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-      MIRL_HIP(hipFuncSetAttribute((const void*)k_conv1_u8_fwd_bf<2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-      MIRL_HIP(hipFuncSetAttribute((const void*)k_conv1_u8_fwd_bf<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-      MIRL_HIP(hipFuncSetAttribute((const void*)k_conv1_u8_fwd_bf<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-      attr_set = true;
-    }
-    if (fpi == 2) { if (nts) C1B_LAUNCH(2, 1); else C1B_LAUNCH(2, 0); }
-    else          { if (nts) C1B_LAUNCH(1, 1); else C1B_LAUNCH(1, 0); }
-#undef C1B_LAUNCH
-    MIRL_LAUNCH_CHECK();
-    return MIRL_OK;
-  }
-  const int dbg = (flags >> 24) & 7;
-  const unsigned ow_magic = OW > 1 ? (unsigned)(((1ULL << 32) + OW - 1) / OW) : 0u;   // exact n / OW for n < 2^16
-#define C1_LAUNCH(FPI_, NTS_, DBG_) \
-  hipLaunchKernelGGL((k_conv1_u8_fwd<FPI_, NTS_, DBG_>), dim3(grid), dim3(256), lds, st, (int)N, H, W, OH, OW, ow_magic, pitch, split, x, wpk, bias, y)
-  if (dbg) {                                             // timing experiments, fpi 2 + nt stores only
-    if (fpi != 2 || !nts) return fail(MIRL_ERR_ARG, "conv1_u8_fwd: debug variants exist for fpi 2 with nt stores only");
-    switch (dbg) {
-      case 1: C1_LAUNCH(2, 1, 1); break;  case 2: C1_LAUNCH(2, 1, 2); break;
-      case 4: C1_LAUNCH(2, 1, 4); break;  case 7: C1_LAUNCH(2, 1, 7); break;
-      default: return fail(MIRL_ERR_ARG, "conv1_u8_fwd: unknown debug variant");
-    }
-  } else if (fpi == 2 && nts && !(flags & 4)) {
-    // all 64 byte->float conversions of a tile in front of its MFMA chain: 2.20 vs 2.41 ms per
-    // 41 472 frames (conversions interleaved with the chain delay MFMA issue; 250 VGPRs, still
-    // 2 waves per SIMD).  Bit 2 of flags keeps the interleaved variant for the probe.
-    hipLaunchKernelGGL((k_conv1_u8_fwd<2, 1, 0, 1>), dim3(grid), dim3(256), lds, st, (int)N, H, W, OH, OW, ow_magic, pitch, split, x, wpk, bias, y);
-  } else if (fpi == 2) {
-    if (nts) C1_LAUNCH(2, 1, 0); else C1_LAUNCH(2, 0, 0);
+    const auto k = fpi == 2 ? (nts ? k_conv1_u8_fwd_bf<2, 1> : k_conv1_u8_fwd_bf<2, 0>) : (nts ? k_conv1_u8_fwd_bf<1, 1> : k_conv1_u8_fwd_bf<1, 0>);
+    if (int rc = raise_lds_limit(k, 96 * 1024)) return rc;      // 2 frames + 16 KB of weight parts = 74 KB of dynamic LDS
+    C1_LAUNCH(k, (const uint4*)wpk);
   } else {
-    if (nts) C1_LAUNCH(1, 1, 0); else C1_LAUNCH(1, 0, 0);
+    // fpi 2 with nt stores: all 64 byte->float conversions of a tile in front of its MFMA chain (BULK): 2.20 vs 2.41 ms
+    // per 41 472 frames (conversions interleaved with the chain delay MFMA issue; 250 VGPRs, still 2 waves per SIMD).
+    // Bit 2 of flags keeps the interleaved variant for the probe.
+    const auto k = fpi == 2 ? (nts ? (interleaved ? k_conv1_u8_fwd<2, 1> : k_conv1_u8_fwd<2, 1, 1>) : k_conv1_u8_fwd<2, 0>)
+                            : (nts ? k_conv1_u8_fwd<1, 1> : k_conv1_u8_fwd<1, 0>);
+    C1_LAUNCH(k, (const float*)wpk);
   }
 #undef C1_LAUNCH
   MIRL_LAUNCH_CHECK();
@@ -868,53 +811,16 @@ extern "C" int mirl_conv1_u8_wrw_scratch_floats(int64_t* out) {
   return MIRL_OK;
 }
 
-// flags bit 0: conversions interleaved with the MFMAs (the first version) instead of hoisted per k-step
+// flags bit 0: conversions interleaved with the MFMAs (the first version) instead of hoisted per k-step; bit 1: the
+// f32-pipe kernel
 extern "C" int mirl_conv1_u8_wrw_ex(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* g, float scale,
                                     float* scratch, float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w,
                                     int32_t flags, void* stream) {
   using namespace mirl;
   if (N <= 0 || N >= (1LL << 30) || !x || !g || !scratch || !dw) return fail(MIRL_ERR_ARG, "bad conv1_u8_wrw arguments");
   if (!mirl_conv1_u8_supported(C1_PLANES, H, W, C1_F, C1_K, C1_S)) return fail(MIRL_ERR_ARG, "conv1_u8_wrw: unsupported frame shape");
-  if (((uintptr_t)x % 16) || ((uintptr_t)g % 16) || ((uintptr_t)scratch % 16))
-    return fail(MIRL_ERR_ARG, "conv1_u8_wrw: pointers must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const int OH = (H - C1_K) / C1_S + 1, OW = (W - C1_K) / C1_S + 1, HW = H * W, pitch = c1_pitch(HW);
-  const int fpi = (N >= 1024 && 2 * C1_PLANES * pitch <= 64 * 1024) ? 2 : 1;
-  const int64_t units = (N + fpi - 1) / fpi;
-  const unsigned grid = (unsigned)(units < 512 ? units : 512);
-  size_t lds = (size_t)fpi * C1_PLANES * pitch;
-  if (lds < (size_t)C1_DW * 4) lds = (size_t)C1_DW * 4;          // the workgroup's 32 KB partial is reduced there
-  const unsigned ow_magic = OW > 1 ? (unsigned)(((1ULL << 32) + OW - 1) / OW) : 0u;
-  bool b3 = false;
-  unsigned b3_grid = 0;
-  if (!(flags & 2)) {                                               // flags bit 1: force the f32-pipe kernel
-    if (int rc = c1_wrw_b3<false>(N, H, W, x, g, nullptr, scratch, (int)C1_DW, &b3_grid, st, &b3)) return rc;
-  }
-  if (b3) {
-    ProfScope ps("k_conv1_wrw_reduce", (double)b3_grid * C1_DW * 4, st);
-    hipLaunchKernelGGL(k_conv1_wrw_reduce, dim3((C1_DW + 255) / 256), dim3(256), 0, st, scratch, (int)b3_grid, scale, dw, ws_o, ws_c, ws_h, ws_w,
-                       (int)C1_DW, (float*)nullptr);
-    MIRL_LAUNCH_CHECK();
-    return MIRL_OK;
-  }
-  {
-    ProfScope ps("k_conv1_u8_wrw", (double)N * (C1_PLANES * HW + (double)OH * OW * C1_F * 4), st,
-                 (double)N * OH * OW * 2.0 * C1_PLANES * C1_K * C1_K * C1_F);
-#define C1_WLAUNCH(FPI_, WC_, PC_) \
-  hipLaunchKernelGGL((k_conv1_u8_wrw<FPI_, WC_, PC_>), dim3(grid), dim3(256), lds, st, (int)N, H, W, OH, OW, ow_magic, pitch, x, g, scratch, (const float*)nullptr, (int)C1_DW)
-    const bool atari = W == 84 && pitch == 7232;
-    if (fpi == 2 && atari && !(flags & 1))
-      hipLaunchKernelGGL((k_conv1_u8_wrw<2, 84, 7232, 1>), dim3(grid), dim3(256), lds, st, (int)N, H, W, OH, OW, ow_magic, pitch, x, g, scratch, (const float*)nullptr, (int)C1_DW);
-    else if (fpi == 2) { if (atari) C1_WLAUNCH(2, 84, 7232); else C1_WLAUNCH(2, 0, 0); }
-    else               { if (atari) C1_WLAUNCH(1, 84, 7232); else C1_WLAUNCH(1, 0, 0); }
-#undef C1_WLAUNCH
-    MIRL_LAUNCH_CHECK();
-  }
-  ProfScope ps("k_conv1_wrw_reduce", (double)grid * C1_DW * 4, st);
-  hipLaunchKernelGGL(k_conv1_wrw_reduce, dim3((C1_DW + 255) / 256), dim3(256), 0, st, scratch, (int)grid, scale, dw, ws_o, ws_c, ws_h, ws_w,
-                     (int)C1_DW, (float*)nullptr);
-  MIRL_LAUNCH_CHECK();
-  return MIRL_OK;
+  if (!aligned16(x, g, scratch)) return fail(MIRL_ERR_ARG, "conv1_u8_wrw: pointers must be 16-byte aligned");
+  return c1_wrw<false>(N, H, W, x, g, nullptr, scale, scratch, dw, ws_o, ws_c, ws_h, ws_w, nullptr, flags & 2, flags & 1, (hipStream_t)stream);
 }
 
 // Weight AND bias gradient from the gradient w.r.t. the layer's output: dy masked by the forward output y > 0 while it is
@@ -925,43 +831,8 @@ extern "C" int mirl_conv1_u8_wrw_masked(int64_t N, int32_t H, int32_t W, const u
   using namespace mirl;
   if (N <= 0 || N >= (1LL << 30) || !x || !dy || !y || !scratch || !dw || !db) return fail(MIRL_ERR_ARG, "bad conv1_u8_wrw_masked arguments");
   if (!mirl_conv1_u8_supported(C1_PLANES, H, W, C1_F, C1_K, C1_S)) return fail(MIRL_ERR_ARG, "conv1_u8_wrw: unsupported frame shape");
-  if (((uintptr_t)x % 16) || ((uintptr_t)dy % 16) || ((uintptr_t)y % 16) || ((uintptr_t)scratch % 16))
-    return fail(MIRL_ERR_ARG, "conv1_u8_wrw: pointers must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const int OH = (H - C1_K) / C1_S + 1, OW = (W - C1_K) / C1_S + 1, HW = H * W, pitch = c1_pitch(HW);
-  const int fpi = (N >= 1024 && 2 * C1_PLANES * pitch <= 64 * 1024) ? 2 : 1;
-  const int64_t units = (N + fpi - 1) / fpi;
-  const unsigned grid = (unsigned)(units < 512 ? units : 512);
-  const int slab = C1_DW + C1_F;
-  size_t lds = (size_t)fpi * C1_PLANES * pitch;
-  if (lds < (size_t)slab * 4) lds = (size_t)slab * 4;
-  const unsigned ow_magic = OW > 1 ? (unsigned)(((1ULL << 32) + OW - 1) / OW) : 0u;
-  bool b3 = false;
-  unsigned b3_grid = 0;
-  if (int rc = c1_wrw_b3<true>(N, H, W, x, dy, y, scratch, slab, &b3_grid, st, &b3)) return rc;
-  if (b3) {
-    ProfScope ps("k_conv1_wrw_reduce", (double)b3_grid * slab * 4, st);
-    hipLaunchKernelGGL(k_conv1_wrw_reduce, dim3((slab + 255) / 256), dim3(256), 0, st, scratch, (int)b3_grid, scale, dw, ws_o, ws_c, ws_h, ws_w, slab, db);
-    MIRL_LAUNCH_CHECK();
-    return MIRL_OK;
-  }
-  {
-    ProfScope ps("k_conv1_u8_wrw", (double)N * (C1_PLANES * HW + 2.0 * OH * OW * C1_F * 4), st,
-                 (double)N * OH * OW * 2.0 * C1_PLANES * C1_K * C1_K * C1_F);
-#define C1_MLAUNCH(FPI_, WC_, PC_, BULK_) \
-  hipLaunchKernelGGL((k_conv1_u8_wrw<FPI_, WC_, PC_, BULK_, true>), dim3(grid), dim3(256), lds, st, (int)N, H, W, OH, OW, ow_magic, pitch, x, dy, scratch, y, slab)
-    const bool atari = W == 84 && pitch == 7232;
-    if (fpi == 2 && atari) C1_MLAUNCH(2, 84, 7232, 1);
-    else if (fpi == 2) C1_MLAUNCH(2, 0, 0, 0);
-    else if (atari) C1_MLAUNCH(1, 84, 7232, 0);
-    else C1_MLAUNCH(1, 0, 0, 0);
-#undef C1_MLAUNCH
-    MIRL_LAUNCH_CHECK();
-  }
-  ProfScope ps("k_conv1_wrw_reduce", (double)grid * slab * 4, st);
-  hipLaunchKernelGGL(k_conv1_wrw_reduce, dim3((slab + 255) / 256), dim3(256), 0, st, scratch, (int)grid, scale, dw, ws_o, ws_c, ws_h, ws_w, slab, db);
-  MIRL_LAUNCH_CHECK();
-  return MIRL_OK;
+  if (!aligned16(x, dy, y, scratch)) return fail(MIRL_ERR_ARG, "conv1_u8_wrw: pointers must be 16-byte aligned");
+  return c1_wrw<true>(N, H, W, x, dy, y, scale, scratch, dw, ws_o, ws_c, ws_h, ws_w, db, false, false, (hipStream_t)stream);
 }
 
 extern "C" int mirl_conv1_u8_wrw(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* g, float scale,

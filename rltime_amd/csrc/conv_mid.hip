@@ -472,6 +472,36 @@ static size_t c3b_lds_bytes(int fpi, int OH, int OW) {
   return planes > xchg ? planes : xchg;
 }
 
+// What the data-gradient entry points share once their arguments are checked: pack the weights, then the kernel
+// instantiation for `fpi` frames per LDS fill (k2 / k1) on a capped persistent grid.  The kernel-specific numbers are the caller's.
+struct BwdDataLaunch {
+  const char *pack_name, *name;      // profile names
+  double pack_bytes, bytes, flop;    // algorithmic bytes of the two launches, matrix-pipe work of the second
+  unsigned pack_grid;
+  int fpi;
+  size_t lds, lds_limit;             // dynamic LDS of the launch; the limit to raise for it (0: within the default)
+  int grid_cap, block, magic_div;    // most workgroups, threads per workgroup, the divisor whose magic the kernel takes
+};
+template <typename WPK>              // float: f32-pipe operand order; uint4: packed bf16 parts
+static int bwd_data_launch(const BwdDataLaunch& c, void (*pack)(const float*, int64_t, int64_t, int64_t, int64_t, WPK*),
+                           void (*k2)(int, int, int, unsigned, const float*, const WPK*, float*),
+                           void (*k1)(int, int, int, unsigned, const float*, const WPK*, float*), int64_t N, int32_t OH, int32_t OW,
+                           const float* g, const float* weight, int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w, float* wpk,
+                           float* dx, hipStream_t st) {
+  {
+    ProfScope ps(c.pack_name, c.pack_bytes, st);
+    hipLaunchKernelGGL(pack, dim3(c.pack_grid), dim3(256), 0, st, weight, ws_o, ws_c, ws_h, ws_w, reinterpret_cast<WPK*>(wpk));
+    MIRL_LAUNCH_CHECK();
+  }
+  const auto k = c.fpi == 2 ? k2 : k1;
+  if (c.lds_limit) { if (int rc = raise_lds_limit(k, c.lds_limit)) return rc; }
+  ProfScope ps(c.name, c.bytes, st, c.flop);
+  hipLaunchKernelGGL(k, dim3(capped_grid((N + c.fpi - 1) / c.fpi, c.grid_cap)), dim3(c.block), c.lds, st, (int)N, OH, OW,
+                     magic_u32(c.magic_div), g, reinterpret_cast<const WPK*>(wpk), dx);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
 }  // namespace mirl
 
 extern "C" int mirl_conv2_bwd_data_supported(int32_t C, int32_t F, int32_t K, int32_t S, int32_t IH, int32_t IW, int32_t OH, int32_t OW) {
@@ -487,27 +517,18 @@ extern "C" int mirl_conv2_bwd_data(int64_t N, int32_t OH, int32_t OW, const floa
   if (N <= 0 || N >= (1LL << 30) || !g || !weight || !wpk || !dx) return fail(MIRL_ERR_ARG, "bad conv2_bwd_data arguments");
   if (!mirl_conv2_bwd_data_supported(C2_C, C2_F, C2_K, C2_S, 2 * OH + 2, 2 * OW + 2, OH, OW))
     return fail(MIRL_ERR_ARG, "conv2_bwd_data: unsupported shape");
-  if (((uintptr_t)g % 16) || ((uintptr_t)dx % 16) || ((uintptr_t)wpk % 16))
-    return fail(MIRL_ERR_ARG, "conv2_bwd_data: pointers must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  {
-    ProfScope ps("k_conv2_pack_w", 2.0 * C2_WPK * 4, st);
-    hipLaunchKernelGGL(k_conv2_pack_w, dim3((C2_WPK + 255) / 256), dim3(256), 0, st, weight, ws_o, ws_c, ws_h, ws_w, wpk);
-    MIRL_LAUNCH_CHECK();
-  }
-  const int fpi = (N >= 1024 && c2_lds_bytes(2, OH, OW) <= 64 * 1024) ? 2 : 1;
-  const int64_t units = (N + fpi - 1) / fpi;
-  const unsigned grid = (unsigned)(units < 512 ? units : 512);
-  const int V = OW + 1;
-  const unsigned v_magic = V > 1 ? (unsigned)(((1ULL << 32) + V - 1) / V) : 0u;
+  if (!aligned16(g, dx, wpk)) return fail(MIRL_ERR_ARG, "conv2_bwd_data: pointers must be 16-byte aligned");
+  BwdDataLaunch c;
+  c.pack_name = "k_conv2_pack_w"; c.pack_bytes = 2.0 * C2_WPK * 4; c.pack_grid = (C2_WPK + 255) / 256;
+  c.fpi = (N >= 1024 && c2_lds_bytes(2, OH, OW) <= 64 * 1024) ? 2 : 1;
+  c.lds = c2_lds_bytes(c.fpi, OH, OW); c.lds_limit = 0;
+  c.grid_cap = 512; c.block = 256; c.magic_div = OW + 1;
   // flop: the convolution's own 2 * K*K*C*F per output position (the zero border the kernel multiplies instead of masking
   // edges is issued work, not algorithmic work)
-  ProfScope ps("k_conv2_bwd_data", (double)N * ((double)OH * OW * C2_F * 4 + (double)(2 * OH + 2) * (2 * OW + 2) * C2_C * 4), st,
-               (double)N * OH * OW * 2.0 * C2_K * C2_K * C2_C * C2_F);
-  if (fpi == 2) hipLaunchKernelGGL((k_conv2_bwd_data<2>), dim3(grid), dim3(256), c2_lds_bytes(2, OH, OW), st, (int)N, OH, OW, v_magic, g, wpk, dx);
-  else          hipLaunchKernelGGL((k_conv2_bwd_data<1>), dim3(grid), dim3(256), c2_lds_bytes(1, OH, OW), st, (int)N, OH, OW, v_magic, g, wpk, dx);
-  MIRL_LAUNCH_CHECK();
-  return MIRL_OK;
+  c.name = "k_conv2_bwd_data"; c.bytes = (double)N * ((double)OH * OW * C2_F * 4 + (double)(2 * OH + 2) * (2 * OW + 2) * C2_C * 4);
+  c.flop = (double)N * OH * OW * 2.0 * C2_K * C2_K * C2_C * C2_F;
+  return bwd_data_launch<float>(c, k_conv2_pack_w, k_conv2_bwd_data<2>, k_conv2_bwd_data<1>, N, OH, OW, g, weight, ws_o, ws_c, ws_h, ws_w, wpk,
+                                dx, (hipStream_t)stream);
 }
 
 extern "C" int mirl_conv2_bwd_data_wpk_floats(int64_t* floats) {
@@ -526,30 +547,16 @@ extern "C" int mirl_conv2_bwd_data_ex(int64_t N, int32_t OH, int32_t OW, const f
   if (N <= 0 || N >= (1LL << 30) || !g || !weight || !wpk || !dx) return fail(MIRL_ERR_ARG, "bad conv2_bwd_data arguments");
   if (!mirl_conv2_bwd_data_supported(C2_C, C2_F, C2_K, C2_S, 2 * OH + 2, 2 * OW + 2, OH, OW) || c2b_lds_bytes(1, OH, OW) > 160 * 1024)
     return fail(MIRL_ERR_ARG, "conv2_bwd_data: unsupported shape");
-  if (((uintptr_t)g % 16) || ((uintptr_t)dx % 16) || ((uintptr_t)wpk % 16))
-    return fail(MIRL_ERR_ARG, "conv2_bwd_data: pointers must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  {
-    ProfScope ps("k_conv2_pack_w3b", 4.0 * C2_WPK + C2B_WPK_BYTES, st);
-    hipLaunchKernelGGL(k_conv2_pack_w3b, dim3((C2B_SLOTS * 64 + 255) / 256), dim3(256), 0, st, weight, ws_o, ws_c, ws_h, ws_w,
-                       reinterpret_cast<uint4*>(wpk));
-    MIRL_LAUNCH_CHECK();
-  }
-  const int fpi = (N >= 512 && c2b_lds_bytes(2, OH, OW) <= 160 * 1024) ? 2 : 1;
-  const size_t lds = c2b_lds_bytes(fpi, OH, OW);
-  const int64_t units = (N + fpi - 1) / fpi;
-  const unsigned grid = (unsigned)(units < 256 ? units : 256);
-  const int V = OW + 1;
-  const unsigned v_magic = V > 1 ? (unsigned)(((1ULL << 32) + V - 1) / V) : 0u;
-  static bool attr[2] = {false, false};
-  const void* fn = fpi == 2 ? (const void*)k_conv2_bwd_data_b3<2> : (const void*)k_conv2_bwd_data_b3<1>;
-  if (!attr[fpi - 1]) { MIRL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr[fpi - 1] = true; }
-  ProfScope ps("k_conv2_bwd_data_b3", (double)N * ((double)OH * OW * C2_F * 4 + (double)(2 * OH + 2) * (2 * OW + 2) * C2_C * 4), st,
-               (double)N * OH * OW * 2.0 * C2_K * C2_K * C2_C * C2_F);
-  if (fpi == 2) hipLaunchKernelGGL((k_conv2_bwd_data_b3<2>), dim3(grid), dim3(512), lds, st, (int)N, OH, OW, v_magic, g, reinterpret_cast<const uint4*>(wpk), dx);
-  else          hipLaunchKernelGGL((k_conv2_bwd_data_b3<1>), dim3(grid), dim3(512), lds, st, (int)N, OH, OW, v_magic, g, reinterpret_cast<const uint4*>(wpk), dx);
-  MIRL_LAUNCH_CHECK();
-  return MIRL_OK;
+  if (!aligned16(g, dx, wpk)) return fail(MIRL_ERR_ARG, "conv2_bwd_data: pointers must be 16-byte aligned");
+  BwdDataLaunch c;
+  c.pack_name = "k_conv2_pack_w3b"; c.pack_bytes = 4.0 * C2_WPK + C2B_WPK_BYTES; c.pack_grid = (C2B_SLOTS * 64 + 255) / 256;
+  c.fpi = (N >= 512 && c2b_lds_bytes(2, OH, OW) <= 160 * 1024) ? 2 : 1;
+  c.lds = c2b_lds_bytes(c.fpi, OH, OW); c.lds_limit = 160 * 1024;
+  c.grid_cap = 256; c.block = 512; c.magic_div = OW + 1;
+  c.name = "k_conv2_bwd_data_b3"; c.bytes = (double)N * ((double)OH * OW * C2_F * 4 + (double)(2 * OH + 2) * (2 * OW + 2) * C2_C * 4);
+  c.flop = (double)N * OH * OW * 2.0 * C2_K * C2_K * C2_C * C2_F;
+  return bwd_data_launch<uint4>(c, k_conv2_pack_w3b, k_conv2_bwd_data_b3<2>, k_conv2_bwd_data_b3<1>, N, OH, OW, g, weight, ws_o, ws_c, ws_h, ws_w,
+                                wpk, dx, (hipStream_t)stream);
 }
 
 // Measured (MI355X, 40 960 frames of 9 x 9 x 64): 1.46-1.50 ms against 2.10-2.13 ms for the f32-pipe kernel above = 0.35 of
@@ -580,29 +587,15 @@ extern "C" int mirl_conv3_bwd_data(int64_t N, int32_t OH, int32_t OW, const floa
   if (N <= 0 || N >= (1LL << 30) || !g || !weight || !wpk || !dx) return fail(MIRL_ERR_ARG, "bad conv3_bwd_data arguments");
   if (wpk_floats < C3B_WPK_BYTES / 4) return fail(MIRL_ERR_ARG, "conv3_bwd_data: wpk smaller than mirl_conv3_bwd_data_wpk_floats()");
   if (!mirl_conv3_bwd_data_supported(C3B_C, C3B_F, C3B_K, 1, OH + 2, OW + 2, OH, OW)) return fail(MIRL_ERR_ARG, "conv3_bwd_data: unsupported shape");
-  if (((uintptr_t)g % 16) || ((uintptr_t)dx % 16) || ((uintptr_t)wpk % 16))
-    return fail(MIRL_ERR_ARG, "conv3_bwd_data: pointers must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  {
-    ProfScope ps("k_conv3_pack_w3b", 4.0 * C3B_F * C3B_C * 9 + C3B_WPK_BYTES, st);
-    hipLaunchKernelGGL(k_conv3_pack_w3b, dim3((C3B_SLOTS * 64 + 255) / 256), dim3(256), 0, st, weight, ws_o, ws_c, ws_h, ws_w,
-                       reinterpret_cast<uint4*>(wpk));
-    MIRL_LAUNCH_CHECK();
-  }
+  if (!aligned16(g, dx, wpk)) return fail(MIRL_ERR_ARG, "conv3_bwd_data: pointers must be 16-byte aligned");
   const int IHW = (OH + 2) * (OW + 2);
-  const int fpi = (N >= 512 && 2 * IHW <= 16 * C3B_MAXT && c3b_lds_bytes(2, OH, OW) <= 150 * 1024) ? 2 : 1;
-  const size_t lds = c3b_lds_bytes(fpi, OH, OW);
-  const int64_t units = (N + fpi - 1) / fpi;
-  const unsigned grid = (unsigned)(units < 256 ? units : 256);
-  const int IW = OW + 2;
-  const unsigned iw_magic = (unsigned)(((1ULL << 32) + IW - 1) / IW);
-  static bool attr[2] = {false, false};
-  const void* fn = fpi == 2 ? (const void*)k_conv3_bwd_data_b3<2> : (const void*)k_conv3_bwd_data_b3<1>;
-  if (!attr[fpi - 1]) { MIRL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); attr[fpi - 1] = true; }
-  ProfScope ps("k_conv3_bwd_data_b3", (double)N * 4.0 * C3B_F * ((double)OH * OW + (double)IHW), st,
-               (double)N * OH * OW * 2.0 * C3B_K * C3B_K * C3B_C * C3B_F);
-  if (fpi == 2) hipLaunchKernelGGL((k_conv3_bwd_data_b3<2>), dim3(grid), dim3(512), lds, st, (int)N, OH, OW, iw_magic, g, reinterpret_cast<const uint4*>(wpk), dx);
-  else          hipLaunchKernelGGL((k_conv3_bwd_data_b3<1>), dim3(grid), dim3(512), lds, st, (int)N, OH, OW, iw_magic, g, reinterpret_cast<const uint4*>(wpk), dx);
-  MIRL_LAUNCH_CHECK();
-  return MIRL_OK;
+  BwdDataLaunch c;
+  c.pack_name = "k_conv3_pack_w3b"; c.pack_bytes = 4.0 * C3B_F * C3B_C * 9 + C3B_WPK_BYTES; c.pack_grid = (C3B_SLOTS * 64 + 255) / 256;
+  c.fpi = (N >= 512 && 2 * IHW <= 16 * C3B_MAXT && c3b_lds_bytes(2, OH, OW) <= 150 * 1024) ? 2 : 1;
+  c.lds = c3b_lds_bytes(c.fpi, OH, OW); c.lds_limit = 150 * 1024;
+  c.grid_cap = 256; c.block = 512; c.magic_div = OW + 2;
+  c.name = "k_conv3_bwd_data_b3"; c.bytes = (double)N * 4.0 * C3B_F * ((double)OH * OW + (double)IHW);
+  c.flop = (double)N * OH * OW * 2.0 * C3B_K * C3B_K * C3B_C * C3B_F;
+  return bwd_data_launch<uint4>(c, k_conv3_pack_w3b, k_conv3_bwd_data_b3<2>, k_conv3_bwd_data_b3<1>, N, OH, OW, g, weight, ws_o, ws_c, ws_h, ws_w,
+                                wpk, dx, (hipStream_t)stream);
 }

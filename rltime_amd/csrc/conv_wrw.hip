@@ -241,7 +241,7 @@ static int cw_geometry(int64_t N, int H, int W, int C, int F, int KH, int KW, in
     a->T = T; a->NT = NT; a->FPI = best; a->KP = (best * OHW + 31) / 32 * 32;
     a->Cp = C + 2; a->xplane = (best * H * W * (C + 2) + 7) / 8 * 8; a->gpitch = a->KP + 8;
     const int64_t units = (N + best - 1) / best;
-    *grid = (unsigned)(units < 256 ? units : 256);
+    *grid = capped_grid(units, 256);
     *lds = best_lds;
   }
   return 1;
@@ -267,17 +267,15 @@ extern "C" int mirl_conv_wrw_b3(int64_t N, int32_t H, int32_t W, int32_t C, int3
   unsigned grid = 0;
   if (N <= 0 || N >= (1LL << 30) || !x || !g || !scratch || !dw) return fail(MIRL_ERR_ARG, "bad conv_wrw_b3 arguments");
   if (!cw_geometry(N, H, W, C, F, KH, KW, S, &a, &lds, &grid)) return fail(MIRL_ERR_ARG, "conv_wrw_b3: unsupported layer shape");
-  if (((uintptr_t)x % 16) || ((uintptr_t)g % 16) || ((uintptr_t)scratch % 16) || ((uintptr_t)dw % 16))
-    return fail(MIRL_ERR_ARG, "conv_wrw_b3: pointers must be 16-byte aligned");
+  if (!aligned16(x, g, scratch, dw)) return fail(MIRL_ERR_ARG, "conv_wrw_b3: pointers must be 16-byte aligned");
   if (scratch_bytes < (int64_t)grid * CW_F * a.T * (int64_t)sizeof(float)) return fail(MIRL_ERR_ARG, "conv_wrw_b3: scratch too small");
   a.x = x; a.g = g; a.partial = (float*)scratch;
   hipStream_t st = (hipStream_t)stream;
   const int tpw = (a.NT + 7) / 8;
   const void* fns[CW_MAXT] = {(const void*)k_conv_wrw_b3<1>, (const void*)k_conv_wrw_b3<2>, (const void*)k_conv_wrw_b3<3>,
                               (const void*)k_conv_wrw_b3<4>, (const void*)k_conv_wrw_b3<5>};
-  static bool attr[CW_MAXT] = {false, false, false, false, false};
   const void* fn = fns[tpw - 1];
-  if (!attr[tpw - 1]) { MIRL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); attr[tpw - 1] = true; }
+  if (int rc = raise_lds_limit(fn, 150 * 1024)) return rc;
   {
     ProfScope ps("k_conv_wrw_b3", 4.0 * (double)N * ((double)H * W * C + (double)a.OH * a.OW * CW_F), st,
                  2.0 * (double)N * a.OH * a.OW * CW_F * a.T);

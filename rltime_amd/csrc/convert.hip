@@ -98,7 +98,7 @@ extern "C" int mirl_frames_to_f32_nhwc_ex(int64_t N, int32_t C, int32_t HW, cons
   if (N <= 0 || C <= 0 || HW <= 0 || !src || !dst) return mirl::fail(MIRL_ERR_ARG, "bad frames_to_f32_nhwc arguments");
   hipStream_t st = (hipStream_t)stream;
   mirl::ProfScope ps("k_frames_to_f32_nhwc", (double)N * C * HW * 5.0, st);
-  if (C == 4 && (HW % 16) == 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0) {
+  if (C == 4 && (HW % 16) == 0 && mirl::aligned16(src, dst)) {
     const int tiles = (HW + MIRL_CV_TILE - 1) / MIRL_CV_TILE;
     // one 1024-pixel tile per workgroup: measured best at the config-D block
     // (62 464 frames: 1.50 ms = 73 % of the HBM peak with cached loads + non-temporal

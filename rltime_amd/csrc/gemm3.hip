@@ -665,17 +665,41 @@ extern "C" int mirl_gemm3_workspace_bytes(int32_t layout, int64_t M, int64_t N, 
   return MIRL_OK;
 }
 
+namespace mirl {
+// optional operands of the fused forms (G3Args has their meaning); all null: the plain product
+struct G3Opt {
+  const float* mul = nullptr; int64_t ldmul = 0; int32_t mul_shift = 0;
+  float* pre = nullptr; int64_t ldpre = 0;
+  const float* w2 = nullptr; float* part = nullptr;
+  float* gsum = nullptr; int64_t ldgsum = 0;
+};
+
+struct G3Kernel { const void* fn; const char* name; };
+// the one place a k_gemm3 instantiation (and its profile name) is picked.  vec: 16-byte epilogue stores (G3Args::vec_ok);
+// narrow: weight gradient of a narrow layer, eight waves stacked along M, 12 MFMAs per K-step (k_gemm3 NARROW)
+static G3Kernel g3_kernel(int layout, int vec, bool mul, bool w2, bool gsum, bool narrow) {
+  static const void* const plain[4][2] = {{(const void*)k_gemm3<true, true, 0, false>, (const void*)k_gemm3<true, true, 0, true>},
+                                          {(const void*)k_gemm3<true, false, 0, false>, (const void*)k_gemm3<true, false, 0, true>},
+                                          {nullptr /* split K takes 16-byte aligned rows only (checked by g3_launch): vec holds */, (const void*)k_gemm3<false, false, 0, true>},
+                                          {(const void*)k_gemm3<true, true, 1, false>, (const void*)k_gemm3<true, true, 1, true>}};
+  static const char* const names[4] = {"k_gemm3_nt", "k_gemm3_nn", "k_gemm3_tn", "k_gemm3_nt_mul"};
+  if (gsum) return {(const void*)k_gemm3<true, false, 3, true>, "k_gemm3_nn_qp"};
+  if (w2) return {(const void*)k_gemm3<true, true, 2, true>, "k_gemm3_nt_head"};
+  if (narrow) return {(const void*)k_gemm3<false, false, 0, true, true>, "k_gemm3_tn"};
+  const int which = mul ? 3 : layout;
+  return {plain[which][vec], names[which]};
+}
+}  // namespace mirl
+
 static int g3_launch(int32_t layout, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B,
                      int64_t ldb, float* C, int64_t ldc, const float* bias, int32_t relu, void* workspace,
-                     int64_t workspace_bytes, const float* mul, int64_t ldmul, int32_t mul_shift, float* pre, int64_t ldpre,
-                     void* stream, const float* w2 = nullptr, float* part = nullptr,
-                     float* gsum = nullptr, int64_t ldgsum = 0) {
+                     int64_t workspace_bytes, void* stream, const mirl::G3Opt& o = mirl::G3Opt()) {
   using namespace mirl;
   if (!mirl_gemm3_supported(layout, M, N, K)) return fail(MIRL_ERR_ARG, "gemm3: unsupported layout / shape");
-  if (!A || !B || (!C && !w2)) return fail(MIRL_ERR_ARG, "gemm3: null operand");
+  if (!A || !B || (!C && !o.w2)) return fail(MIRL_ERR_ARG, "gemm3: null operand");
   const bool akc = layout != 2, bkc = layout == 0;
-  if (akc && ((lda % 4) || ((uintptr_t)A % 16) || lda < K)) return fail(MIRL_ERR_ARG, "gemm3: A must be 16-byte aligned with lda % 4 == 0");
-  if (bkc && ((ldb % 4) || ((uintptr_t)B % 16) || ldb < K)) return fail(MIRL_ERR_ARG, "gemm3: B must be 16-byte aligned with ldb % 4 == 0");
+  if (akc && ((lda % 4) || !aligned16(A) || lda < K)) return fail(MIRL_ERR_ARG, "gemm3: A must be 16-byte aligned with lda % 4 == 0");
+  if (bkc && ((ldb % 4) || !aligned16(B) || ldb < K)) return fail(MIRL_ERR_ARG, "gemm3: B must be 16-byte aligned with ldb % 4 == 0");
   if (!akc && lda < M) return fail(MIRL_ERR_ARG, "gemm3: lda < M");
   if (!bkc && ldb < N) return fail(MIRL_ERR_ARG, "gemm3: ldb < N");
   if (ldc < N) return fail(MIRL_ERR_ARG, "gemm3: ldc < N");
@@ -684,84 +708,61 @@ static int g3_launch(int32_t layout, int64_t M, int64_t N, int64_t K, const floa
   G3Args g;
   g.A = A; g.B = B; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
   g.relu = relu ? 1 : 0;
-  g.mul = mul; g.ldmul = ldmul; g.mul_shift = mul_shift; g.pre = pre; g.ldpre = ldpre;
-  g.w2 = w2; g.part = part; g.gsum = gsum; g.ldgsum = ldgsum;
-  g.vec_ok = (N % 4 == 0) && (ldc % 4 == 0) && !((uintptr_t)C % 16) && (!w2 || !((uintptr_t)w2 % 16)) && (!bias || !((uintptr_t)bias % 16)) &&
-             (!mul || ((ldmul % 4 == 0) && !((uintptr_t)mul % 16))) && (!pre || ((ldpre % 4 == 0) && !((uintptr_t)pre % 16)));
+  g.mul = o.mul; g.ldmul = o.ldmul; g.mul_shift = o.mul_shift; g.pre = o.pre; g.ldpre = o.ldpre;
+  g.w2 = o.w2; g.part = o.part; g.gsum = o.gsum; g.ldgsum = o.ldgsum;
+  // null optional operands count as aligned
+  g.vec_ok = (N % 4 == 0) && (ldc % 4 == 0) && aligned16(C, o.w2, bias, o.mul, o.pre) && (!o.mul || o.ldmul % 4 == 0) && (!o.pre || o.ldpre % 4 == 0);
   g.mt = (int)((M + 255) / 256); g.nt = (int)((N + 255) / 256);
   g.splits = 1; g.steps_per_split = (int)(K / 16);
   unsigned grid = (unsigned)(8 * ((g.mt + 7) / 8) * g.nt);                 // one tile per workgroup
   if (K <= 128) {          // short K: the tile is mostly epilogue — let the next tile's loads fly during the stores
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const unsigned resident = (unsigned)(cus / 8 * 8);                        // one workgroup per CU (147 KB of LDS each)
-    if (grid > resident) grid = resident;
+    const unsigned resident = (unsigned)(cu_count() / 8 * 8);                 // one workgroup per CU (147 KB of LDS each)
+    if (resident && grid > resident) grid = resident;
   }
   if (layout == 2) {
     g.splits = g3_splits(M, N, K);
     const int64_t need = (int64_t)g.splits * M * N * (int64_t)sizeof(float);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace % 16) || (ldc % 4) || ((uintptr_t)C % 16))
+    if (!workspace || workspace_bytes < need || (ldc % 4) || !aligned16(workspace, C))
       return fail(MIRL_ERR_ARG, "gemm3: split-K workspace too small / misaligned");
     g.steps_per_split = (int)((K / 16 + g.splits - 1) / g.splits);
     g.C = (float*)workspace; g.ldc = N;
     grid = (unsigned)(g.mt * g.nt * g.splits);
   }
   const int vec = g.vec_ok ? 1 : 0;
+  const double flop = 2.0 * (double)M * (double)N * (double)K;
   // too few 256 x 256 tiles for the chip: the 256 x 128 tile (plain NT with bias / ReLU; mirl_gemm3_mid_set(0) keeps the big tile)
-  if (g_g3_mid_mode != 0 && layout == 0 && !mul && !w2 && !gsum && vec && (N % 4) == 0 && (int64_t)g.mt * g.nt < 192 && N > 128 &&
+  if (g_g3_mid_mode != 0 && layout == 0 && !o.mul && !o.w2 && !o.gsum && vec && (N % 4) == 0 && (int64_t)g.mt * g.nt < 192 && N > 128 &&
       ((int64_t)g.mt * ((N + G3M_BROWS - 1) / G3M_BROWS) >= 192 || (int64_t)g.mt * g.nt < 24)) {
     // (between: neither tiling fills the chip — the callers' area gate, models/torch/gemm3.py _MIN_AREA, keeps those
     //  products on the library; tiny products take the smaller tile for its shorter tail)
-    static bool mid_attr = false;
-    if (!mid_attr) { MIRL_HIP(hipFuncSetAttribute((const void*)k_gemm3_mid, hipFuncAttributeMaxDynamicSharedMemorySize, G3M_LDS)); mid_attr = true; }
+    if (int rc = raise_lds_limit(k_gemm3_mid, G3M_LDS)) return rc;
     g.nt = (int)((N + G3M_BROWS - 1) / G3M_BROWS);
     const unsigned mgrid = (unsigned)(8 * ((g.mt + 7) / 8) * g.nt);
-    ProfScope ps("k_gemm3_nt_mid", 4.0 * ((double)M * K + (double)N * K + (double)M * N), st, 2.0 * (double)M * (double)N * (double)K);
+    ProfScope ps("k_gemm3_nt_mid", 4.0 * ((double)M * K + (double)N * K + (double)M * N), st, flop);
     void* kargs[] = {(void*)&g};
     MIRL_HIP(hipLaunchKernel((const void*)k_gemm3_mid, dim3(mgrid), dim3(512), kargs, G3M_LDS, st));
     return MIRL_OK;
   }
-  static bool attr[4][2] = {{false, false}, {false, false}, {false, false}, {false, false}};
-  const void* fns[4][2] = {{(const void*)k_gemm3<true, true, 0, false>, (const void*)k_gemm3<true, true, 0, true>},
-                           {(const void*)k_gemm3<true, false, 0, false>, (const void*)k_gemm3<true, false, 0, true>},
-                           {nullptr /* split K takes 16-byte aligned rows only (checked above): vec holds */, (const void*)k_gemm3<false, false, 0, true>},
-                           {(const void*)k_gemm3<true, true, 1, false>, (const void*)k_gemm3<true, true, 1, true>}};
-  const int which = (mul && !gsum) ? 3 : layout;
-  const void* fn = fns[which][vec];
-  if (gsum) {
-    if (!vec || layout != 1 || !mul || mul_shift != 5 || !pre || !part || (ldgsum % 4) || ((uintptr_t)gsum % 16) || ((uintptr_t)part % 16) || (M % 32))
+  if (o.gsum) {
+    if (!vec || layout != 1 || !o.mul || o.mul_shift != 5 || !o.pre || !o.part || (o.ldgsum % 4) || !aligned16(o.gsum, o.part) || (M % 32))
       return fail(MIRL_ERR_ARG, "gemm3: the fused feature-product backward needs the NN form, groups of 32 rows and 16-byte aligned rows");
-    static bool qp_attr = false;
-    fn = (const void*)k_gemm3<true, false, 3, true>;
-    if (!qp_attr) { MIRL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS)); qp_attr = true; }
-  } else if (w2) {
-    if (!vec || layout != 0 || mul || !part) return fail(MIRL_ERR_ARG, "gemm3: the fused following layer needs the NT form with 16-byte aligned rows");
-    static bool hd_attr = false;
-    fn = (const void*)k_gemm3<true, true, 2, true>;
-    if (!hd_attr) { MIRL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS)); hd_attr = true; }
-  } else if (layout == 2 && N <= 64) {
-    // weight gradient of a narrow layer: eight waves stacked along M, 12 MFMAs per K-step (k_gemm3 NARROW)
-    static bool nr_attr = false;
-    fn = (const void*)k_gemm3<false, false, 0, true, true>;
-    if (!nr_attr) { MIRL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS)); nr_attr = true; }
-  } else
-  if (!attr[which][vec]) { MIRL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS)); attr[which][vec] = true; }
+  } else if (o.w2) {
+    if (!vec || layout != 0 || o.mul || !o.part) return fail(MIRL_ERR_ARG, "gemm3: the fused following layer needs the NT form with 16-byte aligned rows");
+  }
+  const G3Kernel k = g3_kernel(layout, vec, o.mul, o.w2, o.gsum, layout == 2 && N <= 64);
+  if (int rc = raise_lds_limit(k.fn, G3_LDS)) return rc;
   {
-    const double flop = 2.0 * (double)M * (double)N * (double)K;
     // HBM bytes: both operands read once, the result (and the pre-product embedding / the multiplier rows) written / read once
     double bytes = 4.0 * ((double)M * K + (double)N * K + (double)M * N * (layout == 2 ? (double)g.splits : 1.0));
-    if (mul) bytes += 4.0 * ((pre ? (double)M * N : 0.0) + (double)(M >> mul_shift) * N * (gsum ? 2.0 : 1.0));
-    if (w2) bytes += 4.0 * (8.0 * (double)N + 8.0 * (double)M * (double)((N + 63) / 64)) - (C ? 0.0 : 4.0 * (double)M * N);
-    ProfScope ps(gsum ? "k_gemm3_nn_qp" : mul ? "k_gemm3_nt_mul" : w2 ? "k_gemm3_nt_head" : layout == 0 ? "k_gemm3_nt" : layout == 1 ? "k_gemm3_nn" : "k_gemm3_tn", bytes, st, flop);
+    if (o.mul) bytes += 4.0 * ((o.pre ? (double)M * N : 0.0) + (double)(M >> o.mul_shift) * N * (o.gsum ? 2.0 : 1.0));
+    if (o.w2) bytes += 4.0 * (8.0 * (double)N + 8.0 * (double)M * (double)((N + 63) / 64)) - (C ? 0.0 : 4.0 * (double)M * N);
+    ProfScope ps(k.name, bytes, st, flop);
     void* kargs[] = {(void*)&g};
-    MIRL_HIP(hipLaunchKernel(fn, dim3(grid), dim3(512), kargs, G3_LDS, st));
+    MIRL_HIP(hipLaunchKernel(k.fn, dim3(grid), dim3(512), kargs, G3_LDS, st));
   }
   if (layout == 2) {
     ProfScope ps("k_gemm3_reduce", (double)(g.splits + 1) * (double)M * (double)N * 4.0, st);
-    const int64_t total = M * (N / 4);
-    unsigned rg = (unsigned)((total + 255) / 256); if (rg > 4096) rg = 4096;
-    hipLaunchKernelGGL(k_gemm3_reduce, dim3(rg), dim3(256), 0, st, (const float*)workspace, g.splits, M, N, C, ldc);
+    hipLaunchKernelGGL(k_gemm3_reduce, dim3(capped_grid((M * (N / 4) + 255) / 256, 4096)), dim3(256), 0, st, (const float*)workspace, g.splits, M, N, C, ldc);
     MIRL_LAUNCH_CHECK();
   }
   return MIRL_OK;
@@ -770,7 +771,7 @@ static int g3_launch(int32_t layout, int64_t M, int64_t N, int64_t K, const floa
 extern "C" int mirl_gemm3(int32_t layout, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B,
                           int64_t ldb, float* C, int64_t ldc, const float* bias, int32_t relu, void* workspace,
                           int64_t workspace_bytes, void* stream) {
-  return g3_launch(layout, M, N, K, A, lda, B, ldb, C, ldc, bias, relu, workspace, workspace_bytes, nullptr, 0, 0, nullptr, 0, stream);
+  return g3_launch(layout, M, N, K, A, lda, B, ldb, C, ldc, bias, relu, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mirl_gemm3_mid_set(int32_t mode) {
@@ -785,7 +786,9 @@ extern "C" int mirl_gemm3_nt_mul(int64_t M, int64_t N, int64_t K, const float* A
   using namespace mirl;
   if (!mul || group_shift < 0 || group_shift > 30 || ldmul < N || (pre && ldpre < N))
     return fail(MIRL_ERR_ARG, "gemm3_nt_mul: bad multiplier / pre-activation arguments");
-  return g3_launch(0, M, N, K, A, lda, B, ldb, C, ldc, bias, relu, nullptr, 0, mul, ldmul, group_shift, pre, ldpre, stream);
+  G3Opt o;
+  o.mul = mul; o.ldmul = ldmul; o.mul_shift = group_shift; o.pre = pre; o.ldpre = ldpre;
+  return g3_launch(0, M, N, K, A, lda, B, ldb, C, ldc, bias, relu, nullptr, 0, stream, o);
 }
 
 // ---- a data gradient g W whose consumer is the backward of the IQN feature product: that backward in the epilogue ----
@@ -799,10 +802,12 @@ extern "C" int mirl_gemm3_nn_qp(int64_t M, int64_t N, int64_t K, const float* A,
                                 const float* emb, int64_t ldemb, const float* x, int64_t ldx, float* d_pre, int64_t ldd,
                                 float* dx, int64_t lddx, float* db_partial, void* stream) {
   using namespace mirl;
-  if (!emb || !x || !d_pre || !dx || !db_partial || ldemb < N || ldx < N || lddx < N || (ldemb % 4) || ((uintptr_t)emb % 16))
+  if (!emb || !x || !d_pre || !dx || !db_partial || ldemb < N || ldx < N || lddx < N || (ldemb % 4) || !aligned16(emb))
     return fail(MIRL_ERR_ARG, "gemm3_nn_qp: bad embedding / feature / output arguments");
-  return g3_launch(1, M, N, K, A, lda, B, ldb, d_pre, ldd, nullptr, 0, nullptr, 0, x, ldx, 5, const_cast<float*>(emb), ldemb, stream,
-                   nullptr, db_partial, dx, lddx);
+  G3Opt o;
+  o.mul = x; o.ldmul = ldx; o.mul_shift = 5; o.pre = const_cast<float*>(emb); o.ldpre = ldemb;
+  o.part = db_partial; o.gsum = dx; o.ldgsum = lddx;
+  return g3_launch(1, M, N, K, A, lda, B, ldb, d_pre, ldd, nullptr, 0, nullptr, 0, stream, o);
 }
 
 // ---- a wide layer and the narrow one that follows it, in one pass over the activation ----------------------------
@@ -824,17 +829,16 @@ extern "C" int mirl_gemm3_nt_head(int64_t M, int64_t N, int64_t K, const float* 
   using namespace mirl;
   int64_t need = 0;
   if (O < 1 || O > 8 || !w2 || !out2 || ldo < O || !workspace || mirl_gemm3_head_workspace_bytes(M, N, &need) || workspace_bytes < need ||
-      ((uintptr_t)workspace % 16) || (N % 4))
+      !aligned16(workspace) || (N % 4))
     return fail(MIRL_ERR_ARG, "bad gemm3_nt_head arguments (1 <= O <= 8, N % 4 == 0, 16-byte aligned workspace of head_workspace_bytes)");
   if (!C) ldc = N;
-  int rc = g3_launch(0, M, N, K, A, lda, B, ldb, C, ldc, bias, relu, nullptr, 0, nullptr, 0, 0, nullptr, 0, stream, w2,
-                     (float*)workspace);
-  if (rc) return rc;
+  G3Opt o;
+  o.w2 = w2; o.part = (float*)workspace;
+  if (int rc = g3_launch(0, M, N, K, A, lda, B, ldb, C, ldc, bias, relu, nullptr, 0, stream, o)) return rc;
   const int ncb = (int)((N + 255) / 256 * 4);
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps("k_g3_head_reduce", 4.0 * (8.0 * ncb + O) * (double)M, st);
-  unsigned grid = (unsigned)((2 * M + 255) / 256); if (grid > 16384) grid = 16384;
-  hipLaunchKernelGGL(k_g3_head_reduce, dim3(grid), dim3(256), 0, st, (const float*)workspace, ncb, M, (int)O, bias2, out2, ldo);
+  hipLaunchKernelGGL(k_g3_head_reduce, dim3(capped_grid((2 * M + 255) / 256, 16384)), dim3(256), 0, st, (const float*)workspace, ncb, M, (int)O, bias2, out2, ldo);
   MIRL_LAUNCH_CHECK();
   return MIRL_OK;
 }

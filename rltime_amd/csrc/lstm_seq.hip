@@ -669,15 +669,9 @@ k_lstm_seq_bwd(SeqBwdArgs a, unsigned* __restrict__ counters, float* P, int64_t 
 }
 
 static int* g_seq_status = nullptr;       // pinned host word the kernels write on a spin timeout
-static int g_seq_cus = 0;
 
 static int seq_init() {
   if (g_seq_status) return MIRL_OK;
-  int dev = 0;
-  MIRL_HIP(hipGetDevice(&dev));
-  hipDeviceProp_t prop;
-  MIRL_HIP(hipGetDeviceProperties(&prop, dev));
-  g_seq_cus = prop.multiProcessorCount;
   int* p = nullptr;
   MIRL_HIP(hipHostMalloc((void**)&p, 64, hipHostMallocMapped));
   *p = 0;
@@ -687,7 +681,7 @@ static int seq_init() {
 
 // small batches: four times as many, four times narrower waves (k_lstm_seq_fwd_narrow) while they all
 // fit the chip at once (every wave a step waits for must be resident)
-static bool seq_narrow(int nrb, int H) { return nrb * (H / 4) <= g_seq_cus; }
+static bool seq_narrow(int nrb, int H) { return nrb * (H / 4) <= cu_count(); }
 
 template <int H>
 static int seq_launch(const SeqFwdArgs& a, void* workspace, hipStream_t st) {
@@ -706,7 +700,7 @@ static int seq_launch(const SeqFwdArgs& a, void* workspace, hipStream_t st) {
     MIRL_LAUNCH_CHECK();
     return MIRL_OK;
   }
-  int ncl = g_seq_cus / NCG;
+  int ncl = cu_count() / NCG;
   if (ncl < 1) return fail(MIRL_ERR_ARG, "lstm_seq_fwd: fewer compute units than column groups");
   if (ncl > nrb) ncl = nrb;
   const size_t cnt_bytes = (size_t)tiles * 32 * sizeof(unsigned);
@@ -717,11 +711,7 @@ static int seq_launch(const SeqFwdArgs& a, void* workspace, hipStream_t st) {
   float* X = (float*)((char*)workspace + align_up(cnt_bytes, 256));
   MIRL_HIP(hipMemsetAsync(workspace, 0, align_up(cnt_bytes, 256) + (size_t)(2 * x_half) * sizeof(float), st));
   const size_t lds = (size_t)(64 * (H + 4) + 4 * 16 * SQ_TP) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    MIRL_HIP(hipFuncSetAttribute((const void*)k_lstm_seq_fwd<H>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  if (int rc = raise_lds_limit(k_lstm_seq_fwd<H>, lds)) return rc;
   int* status_dev = nullptr;
   MIRL_HIP(hipHostGetDevicePointer((void**)&status_dev, g_seq_status, 0));
   hipLaunchKernelGGL(k_lstm_seq_fwd<H>, dim3((unsigned)(ncl * NCG)), dim3(256), lds, st, a, counters, X, x_half, ncl, status_dev);
@@ -733,18 +723,14 @@ template <int H>
 static int seq_bwd_launch(const SeqBwdArgs& a, void* workspace, hipStream_t st) {
   constexpr int NCG = H / 16;
   const int tiles = a.B / 16, nrb = (a.B + 63) / 64;
-  int ncl = g_seq_cus / NCG;
+  int ncl = cu_count() / NCG;
   if (ncl < 1) return fail(MIRL_ERR_ARG, "lstm_seq_bwd: fewer compute units than column groups");
   if (ncl > nrb) ncl = nrb;
   const size_t cnt_bytes = align_up((size_t)tiles * 32 * sizeof(unsigned), 256);
   const int64_t p_half = (int64_t)tiles * NCG * NCG * 256;
   MIRL_HIP(hipMemsetAsync(workspace, 0, cnt_bytes, st));
   const size_t lds = (size_t)(64 * 16 * SQB_LP + 4 * 1024) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    MIRL_HIP(hipFuncSetAttribute((const void*)k_lstm_seq_bwd<H>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  if (int rc = raise_lds_limit(k_lstm_seq_bwd<H>, lds)) return rc;
   int* status_dev = nullptr;
   MIRL_HIP(hipHostGetDevicePointer((void**)&status_dev, g_seq_status, 0));
   hipLaunchKernelGGL(k_lstm_seq_bwd<H>, dim3((unsigned)(ncl * NCG)), dim3(256), lds, st, a, (unsigned*)workspace,
@@ -803,7 +789,7 @@ extern "C" int mirl_lstm_seq_fwd(int32_t T, int32_t B, int32_t H, float* gx, con
   if (!mirl_lstm_seq_supported(T, B, H)) return fail(MIRL_ERR_ARG, "lstm_seq_fwd: unsupported shape (B multiple of 16, H in {128, 256, 512})");
   if (!gx || !w_hh || !h0 || !c0 || !keep || !workspace || (!hm != !cm) || (!h_last != !c_last) || (!hm && !h_last))
     return fail(MIRL_ERR_ARG, "bad lstm_seq_fwd arguments");
-  if (((uintptr_t)w_hh % 16) || ((uintptr_t)workspace % 256)) return fail(MIRL_ERR_ARG, "lstm_seq_fwd needs a 16-byte aligned w_hh and a 256-byte aligned workspace");
+  if (!aligned16(w_hh) || ((uintptr_t)workspace % 256)) return fail(MIRL_ERR_ARG, "lstm_seq_fwd needs a 16-byte aligned w_hh and a 256-byte aligned workspace");
   int rc = seq_init();
   if (rc) return rc;
   if (*(volatile int*)g_seq_status) {
@@ -835,13 +821,13 @@ extern "C" int mirl_lstm_seq_fwd_grid(int32_t B, int32_t H, int32_t* workgroups,
     *workgroups = nrb * (H / 4);
     lds = (int64_t)(16 * (H + 4) + 4 * 64) * (int64_t)sizeof(float);
   } else {
-    int ncl = g_seq_cus / NCG;
+    int ncl = cu_count() / NCG;
     if (ncl > nrb) ncl = nrb;
     *workgroups = ncl * NCG;
     lds = (int64_t)(64 * (H + 4) + 4 * 16 * SQ_TP) * (int64_t)sizeof(float);
   }
   *lds_bytes = lds;
-  *compute_units = g_seq_cus;
+  *compute_units = cu_count();
   int64_t per = (160 * 1024) / (lds > 0 ? lds : 1);
   if (per > 8) per = 8;                       // 32 waves per compute unit, 4 per workgroup
   *per_compute_unit = (int32_t)per;

@@ -415,7 +415,6 @@ k_tail_bwd_w(const float* __restrict__ ga, const float* __restrict__ gv, const f
 }
 
 static inline bool pow2_quads(int C) { int cq = C / 4; return (C % 4) == 0 && cq >= 1 && cq <= 256 && (256 % cq) == 0; }
-static inline bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
 
 }  // namespace mirl
 
@@ -426,7 +425,7 @@ extern "C" int mirl_bias_relu_rows(int64_t rows, int32_t C, float* y, const floa
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = rows * C;
   ProfScope ps("k_bias_relu_rows", 2.0 * n * 4, st);
-  if ((C % 4) == 0 && aligned16(y) && aligned16(bias)) {
+  if ((C % 4) == 0 && aligned16(y, bias)) {
     const int64_t n4 = n / 4, blocks = (n4 + 1023) / 1024;
     if (blocks >= (1LL << 31)) return fail(MIRL_ERR_ARG, "bias_relu_rows: tensor too large for one launch");
     hipLaunchKernelGGL(k_bias_relu_rows, dim3((unsigned)blocks), dim3(256), 0, st, (nn_f4*)y, (const nn_f4*)bias, n4, C / 4);
@@ -453,7 +452,7 @@ extern "C" int mirl_colsum_blocks(int64_t rows, int32_t C, int32_t* blocks) {
 extern "C" int mirl_relu_bwd_bias_rows(int64_t rows, int32_t C, const float* dy, const float* y, float* g, float* db,
                                        float* partial, int32_t blocks, void* stream) {
   if (rows <= 0 || C <= 0 || !dy || !y || !g || !db || !partial || blocks <= 0) return fail(MIRL_ERR_ARG, "bad relu_bwd_bias_rows arguments");
-  if (!pow2_quads(C) || !aligned16(dy) || !aligned16(y) || !aligned16(g) || !aligned16(partial))
+  if (!pow2_quads(C) || !aligned16(dy, y, g, partial))
     return fail(MIRL_ERR_ARG, "relu_bwd_bias_rows: C must be 4 * a power of two <= 1024 and pointers 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const int64_t rpb = (rows + blocks - 1) / blocks;
@@ -472,7 +471,7 @@ extern "C" int mirl_relu_bwd_bias_rows(int64_t rows, int32_t C, const float* dy,
 }
 
 extern "C" int mirl_cos_embed(int64_t rows, int32_t D, const float* tau, const float* freq, float* phi, void* stream) {
-  if (rows <= 0 || D <= 0 || (D % 4) || !tau || !freq || !phi || !aligned16(freq) || !aligned16(phi))
+  if (rows <= 0 || D <= 0 || (D % 4) || !tau || !freq || !phi || !aligned16(freq, phi))
     return fail(MIRL_ERR_ARG, "bad cos_embed arguments (embedding_dim must be a multiple of 4)");
   hipStream_t st = (hipStream_t)stream;
   const int64_t n4 = rows * (D / 4), blocks = (n4 + 255) / 256;
@@ -485,7 +484,7 @@ extern "C" int mirl_cos_embed(int64_t rows, int32_t D, const float* tau, const f
 
 extern "C" int mirl_cos_embed_rng(int64_t rows, int32_t D, uint64_t seed, const uint64_t* step, const float* freq, float* phi,
                                   float* tau_out, void* stream) {
-  if (rows <= 0 || rows >= (1LL << 32) || D <= 0 || (D % 4) || !step || !freq || !phi || !aligned16(freq) || !aligned16(phi))
+  if (rows <= 0 || rows >= (1LL << 32) || D <= 0 || (D % 4) || !step || !freq || !phi || !aligned16(freq, phi))
     return fail(MIRL_ERR_ARG, "bad cos_embed_rng arguments (embedding_dim must be a multiple of 4)");
   hipStream_t st = (hipStream_t)stream;
   const int64_t n4 = rows * (D / 4), blocks = (n4 + 255) / 256;
@@ -498,7 +497,7 @@ extern "C" int mirl_cos_embed_rng(int64_t rows, int32_t D, uint64_t seed, const 
 
 extern "C" int mirl_iqn_mul_fwd(int64_t M, int32_t N, int32_t C, const float* x, const float* emb, float* out, void* stream) {
   if (M <= 0 || N <= 0 || C <= 0 || !x || !emb || !out) return fail(MIRL_ERR_ARG, "bad iqn_mul_fwd arguments");
-  if (!pow2_quads(C) || !aligned16(x) || !aligned16(emb) || !aligned16(out))
+  if (!pow2_quads(C) || !aligned16(x, emb, out))
     return fail(MIRL_ERR_ARG, "iqn_mul_fwd: C must be 4 * a power of two <= 1024 and pointers 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   int64_t blocks = M < 4096 ? M : 4096;
@@ -516,7 +515,7 @@ extern "C" int mirl_iqn_mul_bwd(int64_t M, int32_t N, int32_t C, const float* g,
                                 float* d_pre, float* dx, float* db, float* partial, int32_t blocks, void* stream) {
   if (M <= 0 || N <= 0 || C <= 0 || !g || !emb || !x || !d_pre || !dx || !db || !partial || blocks <= 0)
     return fail(MIRL_ERR_ARG, "bad iqn_mul_bwd arguments");
-  if (!pow2_quads(C) || !aligned16(g) || !aligned16(emb) || !aligned16(x) || !aligned16(d_pre) || !aligned16(dx) || !aligned16(partial))
+  if (!pow2_quads(C) || !aligned16(g, emb, x, d_pre, dx, partial))
     return fail(MIRL_ERR_ARG, "iqn_mul_bwd: C must be 4 * a power of two <= 1024 and pointers 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const int64_t gpb = (M + blocks - 1) / blocks;
@@ -540,11 +539,11 @@ static int tail_bwd_launch(int64_t M, int32_t H1, int32_t Hv, int32_t A, int32_t
   using namespace mirl;
   if (M <= 0 || H1 <= 0 || Hv <= 0 || A <= 0 || Q <= 0 || !ga || !gv || !wo || !wq || !both || !g || !db || !partial || blocks <= 0)
     return fail(MIRL_ERR_ARG, "bad dueling_tail_bwd arguments");
-  if (A > MIRL_TAIL_MAXK || Q > MIRL_TAIL_MAXK || (H1 % 4) || !pow2_quads(H1 + Hv) || !aligned16(both) || !aligned16(g) || !aligned16(partial))
+  if (A > MIRL_TAIL_MAXK || Q > MIRL_TAIL_MAXK || (H1 % 4) || !pow2_quads(H1 + Hv) || !aligned16(both, g, partial))
     return fail(MIRL_ERR_ARG, "dueling_tail_bwd: outputs per branch <= 16, H1 % 4 == 0, H1 + Hv = 4 * 2^k <= 1024, 16-byte aligned pointers");
   const bool wgrad = dwj != nullptr;
   const int KW = A > Q ? A : Q;
-  if (wgrad && (KW > MIRL_TAIL_WGK || !partial_w || !aligned16(partial_w) || !aligned16(dwj)))
+  if (wgrad && (KW > MIRL_TAIL_WGK || !partial_w || !aligned16(partial_w, dwj)))
     return fail(MIRL_ERR_ARG, "dueling_tail_bwd_w: outputs per branch <= 8, 16-byte aligned buffers");
   hipStream_t st = (hipStream_t)stream;
   const int C = H1 + Hv;

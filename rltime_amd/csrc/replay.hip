@@ -1119,7 +1119,7 @@ extern "C" int mirl_replay_prime_stack(mirl_replay* h, const uint8_t* newest_pla
   if (!d.planes) return fail(MIRL_ERR_ARG, "prime_stack: the shard does not de-duplicate frame stacks");
   if (h->book.total_items() != 0) return fail(MIRL_ERR_STATE, "prime_stack: only before the first transition");
   if (stride <= 0) stride = d.plane_bytes;
-  if (((uintptr_t)newest_planes % 16) || (stride % 16)) return fail(MIRL_ERR_ARG, "prime_stack: 16-byte aligned planes");
+  if (!aligned16(newest_planes) || (stride % 16)) return fail(MIRL_ERR_ARG, "prime_stack: 16-byte aligned planes");
   hipLaunchKernelGGL(k_prime_stack, dim3(d.E), dim3(256), 0, (hipStream_t)stream, d, newest_planes, stride);
   MIRL_LAUNCH_CHECK();
   return MIRL_OK;
@@ -1156,7 +1156,7 @@ extern "C" int mirl_replay_ingest(mirl_replay* h, const mirl_ingest* in, void* s
   // ring and the device rings exactly where they were
   if (d.planes && in->newest_plane_only && (h->book.cfg.acting_priority_init && d.per))
     return fail(MIRL_ERR_ARG, "newest_plane_only ingest cannot be combined with acting_priority_init");
-  if (d.planes && !in->newest_plane_only && (((uintptr_t)in->frames) % 16))
+  if (d.planes && !in->newest_plane_only && !aligned16(in->frames))
     return fail(MIRL_ERR_ARG, "stack_planes: the frames array must be 16-byte aligned");
   int rc = h->book.ingest(K, in->env_ids_host, h->plan);
   if (rc) { last_error_ref() = h->book.err; return rc; }
@@ -1695,7 +1695,7 @@ extern "C" int mirl_replay_gather(mirl_replay* h, int32_t B, const int32_t* env,
   Dev& d = h->d;
   int rc;
   if (d.planes) {
-    if (((uintptr_t)out->frames) % 16) return fail(MIRL_ERR_ARG, "stack_planes: the frames output must be 16-byte aligned");
+    if (!aligned16(out->frames)) return fail(MIRL_ERR_ARG, "stack_planes: the frames output must be 16-byte aligned");
     const int64_t blocks = (int64_t)h->rows * B;
     rc = timed_launch(h, h->prof, st, [&] {
       // algorithmic bytes: every output stack written once + every distinct plane of a
@@ -1877,7 +1877,7 @@ __global__ void __launch_bounds__(256) k_copy16_v(u32x4* __restrict__ dst, const
 }
 
 extern "C" int mirl_copy_bytes_ex(void* dst, const void* src, int64_t bytes, int32_t nt, void* stream) {
-  if (!dst || !src || bytes <= 0 || (bytes % 16) || ((uintptr_t)dst % 16) || ((uintptr_t)src % 16)) return fail(MIRL_ERR_ARG, "copy needs 16-byte aligned pointers and size");
+  if (!dst || !src || bytes <= 0 || (bytes % 16) || !aligned16(dst, src)) return fail(MIRL_ERR_ARG, "copy needs 16-byte aligned pointers and size");
   const int64_t n = bytes / 16;
   hipStream_t cs = (hipStream_t)stream;
   if (nt >= 2) {

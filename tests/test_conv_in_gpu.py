@@ -68,6 +68,30 @@ def test_launch_shapes_agree_bitwise(n, h, w):
     assert float((f32k - base).abs().max()) <= 2e-6 * float(base.abs().max())
 
 
+def test_unknown_flag_bits_are_refused_before_any_launch():
+    """Bits 24-26 once selected timing-experiment variants of the kernel; they are unknown bits now, like every bit
+    mirl.h does not name: MIRL_ERR_ARG, and neither the output nor the weight scratch is touched."""
+    from rltime_amd._lib import lib
+    g = torch.Generator(device="cuda").manual_seed(24)
+    x = torch.randint(0, 256, (1, 4, 16, 16), dtype=torch.uint8, device="cuda", generator=g)
+    wt = torch.randn(32, 4, 8, 8, device="cuda", generator=g) * 0.05
+    b = torch.randn(32, device="cuda", generator=g) * 0.1
+    y = torch.full((1, 32, 3, 3), -12345.0, device="cuda").contiguous(memory_format=torch.channels_last)
+    wpk = torch.full((12288,), -54321.0, device="cuda")
+    p = lambda t: C.c_void_p(t.data_ptr())
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    so, sc, sh, sw = wt.stride()
+    for flags in (1 << 24, 7 << 24, 2, 16, 1 << 30):                    # the retired bits, and three that never meant anything
+        rc = lib.mirl_conv1_u8_fwd_ex(1, 16, 16, p(x), p(wt), so, sc, sh, sw, p(b), 1.0 / 255.0, p(wpk), p(y), flags, st)
+        torch.cuda.synchronize()
+        assert rc == -1, (flags, rc)                                   # MIRL_ERR_ARG
+        assert bool((y == -12345.0).all()) and bool((wpk == -54321.0).all()), flags
+    # the same call without the bits runs
+    assert lib.mirl_conv1_u8_fwd_ex(1, 16, 16, p(x), p(wt), so, sc, sh, sw, p(b), 1.0 / 255.0, p(wpk), p(y), 0, st) == 0
+    torch.cuda.synchronize()
+    assert not bool((y == -12345.0).any())
+
+
 @pytest.mark.parametrize("n,h,w", [(2, 84, 84), (257, 84, 84), (2050, 84, 84), (5, 44, 52)])
 def test_real_weights_within_tolerance(n, h, w):
     g = torch.Generator(device="cuda").manual_seed(n)

@@ -51,9 +51,6 @@ def main():
         if n > 1000:
             variants = [("default", None), ("fpi2 nt", 2 << 8), ("fpi1 nt", 1 << 8), ("fpi2 cached", (2 << 8) | 1),
                         ("fpi2 nt conversions-before-chain", (2 << 8) | 4)]
-            # timing experiments (results are NOT the convolution): what each part costs
-            for dbg, what in ((1, "no u8->f32 conversion"), (2, "no output stores"), (4, "no LDS refill"), (7, "MFMA chain only")):
-                variants.append(("fpi2 nt EXPERIMENT " + what, (2 << 8) | (dbg << 24)))
         else:
             variants = [("default", None)] + [("fpi1 split%d %s" % (s, "cached" if c else "nt"), c | (1 << 8) | (s << 16))
                                              for s in (0, 2, 4, 7) for c in (0, 1)]
