@@ -808,6 +808,27 @@ int mirl_synth_env_step_pre(int32_t E, int64_t frame_bytes, const uint8_t* pool,
                             float* rewards_out, uint8_t* dones_out, int32_t clip_rewards, float* ep_reward, int32_t* ep_len,
                             float* out_reward, int32_t* out_len, int32_t* action_counts, uint64_t* rng_step, uint64_t step,
                             void* stream);
+/* One step of Catch as a device-native vector env (csrc/acting.hip k_catch_env_step): a G x G grid of (S / G)-pixel cells on
+ * P <= 4 history planes of S x S uint8 (plane P - 1 newest; S % G == 0, S * S % 16 == 0, S <= 8192, E <= 65535).  The ball falls
+ * one row per step from row 0 of a column drawn as (word 0 of Philox4x32-10(seed ^ 0xCA7C, t, env) * G) >> 32; the paddle on
+ * row G - 1 starts at G / 2 and moves by -1 (action 1) or +1 (action 2), clamped, any other action value leaves it.  At ball
+ * row G - 1 the reward is +1 (ball column == paddle column) or -1, done = 1, and the next episode starts in the same step with
+ * the draw keyed by this t.  obs [E][P][S][S]: plane P - 1 - k shows the state k steps ago — the ball cell (255, only on rows
+ * < V = visible_rows) and the paddle cell (128) — or zeros when the episode is younger than k steps.  `state` is
+ * [2][E] 16-byte records {ball_col, ball_row, paddle now | 1 | 2 | 3 steps ago as bytes 0..3, 0} and `clock` the pair of step
+ * words: the launch reads half `slot` of both and writes half slot ^ 1.  reset_all = 1: every env starts an episode keyed by
+ * t = clock[slot], which is not advanced; rewards 0, dones 1; actions may be NULL.  state, clock and obs 16-byte aligned.     */
+int mirl_catch_env_step(int32_t E, int32_t P, int32_t S, int32_t G, int32_t V, int32_t A, const int32_t* actions, void* state,
+                        uint64_t* clock, int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards,
+                        uint8_t* dones, void* stream);
+/* mirl_catch_env_step and mirl_actor_pre as ONE launch (arguments: those of the two calls, the pre-step's from H on).        */
+int mirl_catch_env_step_pre(int32_t E, int32_t P, int32_t S, int32_t G, int32_t V, int32_t A, const int32_t* actions, void* state,
+                            uint64_t* clock, int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards,
+                            uint8_t* dones, int32_t H, int32_t A_pre, const int32_t* actions_pre, const float* h, const float* c,
+                            float* xh_tail, int64_t xh_pitch, float* c_in, float* state_pack, float* initials,
+                            float* rewards_out, uint8_t* dones_out, int32_t clip_rewards, float* ep_reward, int32_t* ep_len,
+                            float* out_reward, int32_t* out_len, int32_t* action_counts, uint64_t* rng_step, uint64_t step,
+                            void* stream);
 int mirl_episode_track(int32_t E, int32_t A, const float* rewards, const uint8_t* dones,
                        const int32_t* actions, float* ep_reward, int32_t* ep_len,
                        float* out_reward, int32_t* out_len, int32_t* action_counts, void* stream);

@@ -235,7 +235,9 @@ class FastActingStep:
         # that the rollout graph and the per-step path see the same env stream
         env = actor._vec_env
         self.env_into = bool(getattr(env, "supports_step_into", lambda: False)())
-        self.env_pre = self.env_into and hasattr(env, "step_into_args")
+        self.env_pre = self.env_into and (hasattr(env, "step_pre") or hasattr(env, "step_into_args"))
+        if hasattr(env, "bind_actions"):
+            env.bind_actions(self.actions)       # an env that needs the actions reads them from the head's static buffer
         if self.env_into:
             self.obs_buf = torch.empty_like(obs0)
             self.env_rewards = torch.zeros(E, **f32)
@@ -306,13 +308,17 @@ class FastActingStep:
         check(lib.mirl_actor_pre(self.E, a[0], a[1], ptr(rewards), ptr(dones_u8), *a[2:]), "mirl_actor_pre")
 
     def env_step_pre(self, clip=False, row=None):
-        """env.step and the pre-step as ONE launch (csrc/acting.hip k_synth_env_step<true>): the workgroup that draws an
-        env's reward / done applies them to that env's recurrent carry, stored state and episode statistics."""
+        """env.step and the pre-step as ONE launch (csrc/acting.hip k_synth_env_step<true>, or the env's own fused launch:
+        env.step_pre): the workgroup that decides an env's reward / done applies them to that env's recurrent carry, stored
+        state and episode statistics."""
         env = self.actor._vec_env
         tr = self.tracker
         if tr is not None and row is None:
             row = tr.begin_step()
         self.step_no += 1
+        if hasattr(env, "step_pre"):
+            env.step_pre(self.obs_buf, self.env_rewards, self.env_dones, self._pre_args(tr, row, clip))
+            return self.obs_buf
         check(lib.mirl_synth_env_step_pre(*env.step_into_args(self.obs_buf, self.env_rewards, self.env_dones), *self._pre_args(tr, row, clip)),
               "mirl_synth_env_step_pre")
         env.advance_host()

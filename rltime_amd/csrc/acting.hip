@@ -193,6 +193,86 @@ k_synth_env_step(int row_q, const uint4* __restrict__ pool, int pool_n, int64_t 
   }
 }
 
+// One step of Catch as a device-native vector env (acting/catch_env.py): a ball falls one cell row per step down a G x G
+// grid, the paddle on the bottom row moves by -1 (action 1), +1 (action 2) or stays (anything else), and after G - 1 steps the
+// episode ends with +1 (ball column == paddle column) or -1 and the next one starts in the same step.  The env's whole
+// state is ONE 16-byte record {ball_col, ball_row, paddle columns now .. three steps ago as four bytes, 0}, kept like the
+// clock as a pair of blocks read / written alternately: every workgroup of an env reads the old record and the action and
+// recomputes the transition (no exchange, no atomics), workgroup 0 writes the new record, reward, done and the clock.
+// The P history planes are rebuilt from the record — the previous observation is never read — with cached 16-byte
+// stores (the input conv reads the block next).  reset_all: every env starts an episode keyed by t = clock (not advanced).
+struct CatchArgs {
+  int P, S, G, V, cell, plane_q, reset_all;
+  const int32_t* actions; const uint4* state_in; uint4* state_out;
+  const uint64_t* clock_in; uint64_t* clock_out; uint64_t seed;
+  uint4* obs; float* rewards; uint8_t* dones;
+};
+
+template <bool PRE>
+__global__ void __launch_bounds__(256)
+k_catch_env_step(CatchArgs a, ActorPreArgs pre) {
+  const int e = blockIdx.y;
+  const int G = a.G;
+  const uint64_t t = *a.clock_in + (a.reset_all ? 0ull : 1ull);   // every workgroup reads the word nobody writes in this launch
+  int bc = 0, br = 0, dn = 1;
+  uint32_t pad = 0;
+  float rr = 0.0f;
+  if (!a.reset_all) {
+    const uint4 s = a.state_in[e];
+    const int act = a.actions[e];
+    int p0 = (int)(s.z & 0xFFu) + (act == 2 ? 1 : (act == 1 ? -1 : 0));
+    p0 = p0 < 0 ? 0 : (p0 > G - 1 ? G - 1 : p0);
+    pad = (s.z << 8) | (uint32_t)p0;
+    bc = (int)s.x;
+    br = (int)s.y + 1;
+    dn = br == G - 1 ? 1 : 0;
+    if (dn) rr = bc == p0 ? 1.0f : -1.0f;
+  }
+  if (dn) {                                             // a new episode starts in the same step
+    uint32_t r[4];
+    philox_4x32(a.seed ^ 0xCA7Cull, t, (uint32_t)e, r);
+    bc = (int)(((uint64_t)r[0] * (uint64_t)G) >> 32);
+    br = 0;
+    pad = (uint32_t)(G / 2) * 0x01010101u;
+  }
+  // frames: plane P-1-k shows the state k steps ago; planes from before the episode began are zero
+  const int S = a.S, cell = a.cell, plane_q = a.plane_q;
+  const int px_ball = bc * cell, py_pad = (G - 1) * cell;
+  uint4* dst = a.obs + (int64_t)e * a.P * plane_q;
+  for (int c = blockIdx.x * 256 + threadIdx.x; c < a.P * plane_q; c += gridDim.x * 256) {
+    const int p = c / plane_q, k = a.P - 1 - p;
+    const int by = br - k;                              // the ball's cell row in this plane
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (by >= 0) {
+      const int o = (c - p * plane_q) * 16;             // first pixel of the chunk in its plane
+      int y = o / S, x = o - y * S;
+      const int y_last = (o + 15) / S;
+      const int py_ball = by < a.V ? by * cell : -cell;   // hidden: a row range no pixel is in
+      if (y_last >= py_pad || (y_last >= py_ball && y < py_ball + cell)) {
+        const int px_pad = (int)((pad >> (8 * k)) & 0xFFu) * cell;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          uint32_t v = 0u;
+          if (y >= py_pad) { if (x >= px_pad && x < px_pad + cell) v = 128u; }
+          else if (y >= py_ball && y < py_ball + cell && x >= px_ball && x < px_ball + cell) v = 255u;
+          w[j >> 2] |= v << (8 * (j & 3));
+          if (++x == S) { x = 0; ++y; }
+        }
+      }
+    }
+    dst[c] = uint4{w[0], w[1], w[2], w[3]};
+  }
+  if (blockIdx.x == 0) {
+    if (threadIdx.x == 0) {
+      a.state_out[e] = uint4{(uint32_t)bc, (uint32_t)br, pad, 0u};
+      a.rewards[e] = rr;
+      a.dones[e] = (uint8_t)dn;
+      if (e == 0) *a.clock_out = t;                     // the OTHER word of the pair: the next launch reads it
+    }
+    if (PRE) actor_pre_env(pre, e, rr, dn);
+  }
+}
+
 }  // namespace mirl
 
 extern "C" int mirl_synth_env_step(int32_t E, int64_t frame_bytes, const uint8_t* pool, int32_t pool_n, uint64_t* clock, int32_t slot,
@@ -248,6 +328,58 @@ extern "C" int mirl_synth_env_step_pre(int32_t E, int64_t frame_bytes, const uin
   hipLaunchKernelGGL(mirl::k_synth_env_step<true>, dim3(gx, E), dim3(256), 0, (hipStream_t)stream, row_q, (const uint4*)pool, (int)pool_n,
                      (int64_t)E * row_q, (const uint64_t*)(clock + slot), clock + (slot ^ 1), seed, p_neg, p_nonpos, p_done,
                      (uint4*)obs, rewards, dones, p);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
+static int fill_catch(mirl::CatchArgs& a, int32_t E, int32_t P, int32_t S, int32_t G, int32_t V, int32_t A, const int32_t* actions,
+                      void* state, uint64_t* clock, int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards,
+                      uint8_t* dones) {
+  // (E is a grid dimension; S <= 8192 keeps every pixel index of an env's P planes in 32 bits)
+  if (E <= 0 || E > 65535 || P < 1 || P > 4 || G < 2 || G > 128 || S < G || S > 8192 || (S % G) || (((int64_t)S * S) % 16) || A < 3 ||
+      V < 1 || V > G || (slot != 0 && slot != 1) || (reset_all != 0 && reset_all != 1) || (!reset_all && !actions) || !state ||
+      !clock || !obs || !rewards || !dones || !mirl::aligned16(state, clock, obs))
+    return mirl::fail(MIRL_ERR_ARG, "bad catch_env_step arguments (1 <= P <= 4, 2 <= G <= 128, S % G == 0, S * S % 16 == 0, A >= 3, "
+                                    "1 <= V <= G, 16-byte aligned state / clock / obs, slot 0 | 1)");
+  a.P = P; a.S = S; a.G = G; a.V = V; a.cell = S / G; a.plane_q = S * S / 16; a.reset_all = reset_all;
+  a.actions = actions; a.state_in = (const uint4*)state + (int64_t)slot * E; a.state_out = (uint4*)state + (int64_t)(slot ^ 1) * E;
+  a.clock_in = clock + slot; a.clock_out = clock + (slot ^ 1); a.seed = seed;
+  a.obs = (uint4*)obs; a.rewards = rewards; a.dones = dones;
+  return MIRL_OK;
+}
+
+extern "C" int mirl_catch_env_step(int32_t E, int32_t P, int32_t S, int32_t G, int32_t V, int32_t A, const int32_t* actions, void* state,
+                                   uint64_t* clock, int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards,
+                                   uint8_t* dones, void* stream) {
+  mirl::CatchArgs a;
+  int rc = fill_catch(a, E, P, S, G, V, A, actions, state, clock, slot, seed, reset_all, obs, rewards, dones);
+  if (rc) return rc;
+  const int row_q = a.P * a.plane_q;
+  int gx = (row_q + 255) / 256; if (gx > 8) gx = 8;
+  mirl::ProfScope ps("k_catch_env_step", (double)E * (double)row_q * 16.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_catch_env_step<false>, dim3(gx, E), dim3(256), 0, (hipStream_t)stream, a, mirl::ActorPreArgs{});
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
+extern "C" int mirl_catch_env_step_pre(int32_t E, int32_t P, int32_t S, int32_t G, int32_t V, int32_t A, const int32_t* actions, void* state,
+                                       uint64_t* clock, int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards,
+                                       uint8_t* dones, int32_t H, int32_t A_pre, const int32_t* actions_pre, const float* h, const float* c,
+                                       float* xh_tail, int64_t xh_pitch, float* c_in, float* state_pack, float* initials,
+                                       float* rewards_out, uint8_t* dones_out, int32_t clip_rewards, float* ep_reward, int32_t* ep_len,
+                                       float* out_reward, int32_t* out_len, int32_t* action_counts, uint64_t* rng_step, uint64_t step,
+                                       void* stream) {
+  mirl::CatchArgs a;
+  int rc = fill_catch(a, E, P, S, G, V, A, actions, state, clock, slot, seed, reset_all, obs, rewards, dones);
+  if (rc) return rc;
+  mirl::ActorPreArgs p;
+  rc = fill_pre(p, E, H, A_pre, actions_pre, h, c, xh_tail, xh_pitch, c_in, state_pack, initials, rewards_out, dones_out, clip_rewards,
+                ep_reward, ep_len, out_reward, out_len, action_counts, rng_step, step);
+  if (rc) return rc;
+  const int row_q = a.P * a.plane_q;
+  int gx = (row_q + 255) / 256; if (gx > 8) gx = 8;
+  mirl::ProfScope ps("k_catch_env_step_pre", (double)E * (double)row_q * 16.0 + (double)E * H * 4.0 * 6.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_catch_env_step<true>, dim3(gx, E), dim3(256), 0, (hipStream_t)stream, a, p);
   MIRL_LAUNCH_CHECK();
   return MIRL_OK;
 }

@@ -29,10 +29,20 @@ def make_vec_env(env, env_args, num_envs, device, seed=0):
         from rltime_amd.acting.cartpole_env import CartPoleVecEnv
         limit = (env_args or {}).get("max_episode_steps", 500 if env.endswith("v1") else 200)
         return CartPoleVecEnv(num_envs, max_episode_steps=limit, seed=seed)
+    if env == "catch":
+        # the one device-native game (acting/catch_env.py: a single HIP kernel per vector step)
+        from rltime_amd.acting.catch_env import CatchVecEnv
+        args = dict(env_args or {})
+        unknown = set(args) - {"frame_shape", "grid", "n_actions", "visible_rows"}
+        if unknown:
+            raise ValueError("catch: unknown env_args %s" % sorted(unknown))
+        if "frame_shape" in args:
+            args["frame_shape"] = tuple(args["frame_shape"])
+        return CatchVecEnv(num_envs, device=device, seed=seed, **args)
     if env != "synthetic-atari":
         raise ValueError(
-            "rltime_amd ships the synthetic vector env ('synthetic-atari') and its own CartPole ('CartPole-v0/-v1'): "
-            "real emulators are CPU code outside the scope of this backend (DESIGN.md)")
+            "rltime_amd ships the synthetic vector env ('synthetic-atari'), the device-native game 'catch' and its own "
+            "CartPole ('CartPole-v0/-v1'): real emulators are CPU code outside the scope of this backend (DESIGN.md)")
     from rltime_amd.acting.synthetic_env import SyntheticAtariVecEnv
     args = dict(env_args or {})
     args["frame_shape"] = tuple(args.get("frame_shape", (4, 84, 84)))
