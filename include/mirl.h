@@ -832,6 +832,17 @@ int mirl_catch_env_step_pre(int32_t E, int32_t P, int32_t S, int32_t G, int32_t 
 int mirl_episode_track(int32_t E, int32_t A, const float* rewards, const uint8_t* dones,
                        const int32_t* actions, float* ep_reward, int32_t* ep_len,
                        float* out_reward, int32_t* out_len, int32_t* action_counts, void* stream);
+/* The reference evaluation's counting rule on the device (csrc/acting.hip k_eval_count; rltime/eval.py:59-72, :113-149): of E
+ * envs stepping in parallel the first N = episode_count episodes that STARTED are counted, in the host loop's order (step
+ * by step, env by env).  State: acc double [E], len int32 [E], open uint8 [E], counters int32 [4] = {started, counted, steps,
+ * 0}; lists ep_reward double [N], ep_len int32 [N].  reset = 1: acc = 0, len = 0, open = 1, counters = {E, 0, 0, 0}
+ * (rewards / dones may be NULL).  reset = 0, one vector step on rewards (float32 [E], raw) and dones (uint8 [E]): nothing is
+ * written when counted == N at entry; else steps += 1, acc += (double)reward, len += 1, an env with done & open stores
+ * (acc, len) at list position counted + (number of such envs before it), an env with done closes when started + (number of
+ * dones up to and including it) > N, then counted / started advance and acc, len restart at 0 where done.  One workgroup,
+ * no atomics, no host state: capturable.  1 <= E <= 65535 and E <= N (eval.py:74), else MIRL_ERR_ARG before any launch.    */
+int mirl_eval_count(int32_t E, int32_t N, int32_t reset, const float* rewards, const uint8_t* dones, double* acc, int32_t* len,
+                    uint8_t* open, int32_t* counters, double* ep_reward, int32_t* ep_len, void* stream);
 
 /* ---- device copy micro-benchmark used by bench.py for the measured HBM peak */
 int mirl_copy_bytes(void* dst, const void* src, int64_t bytes, void* stream);

@@ -168,6 +168,8 @@ class FastActingStep:
         self.rng_step = torch.zeros(1, dtype=torch.int64, device=dev)
         self.step_no = 0
         self.rng_seed = (int(torch.initial_seed()) ^ (int(actor._base_env_id) << 32) ^ 0xAC7) & 0x7FFFFFFFFFFFFFFF
+        if getattr(actor, "_rng_seed", None) is not None:        # an actor with a Philox key of its own (acting/evaluator.py)
+            self.rng_seed = int(actor._rng_seed) & 0x7FFFFFFFFFFFFFFF
         if self.lstm is not None:
             self.bias_sum = torch.empty(4 * H, **f32)
             self.wcat = torch.empty((4 * H, F + H), **f32)
@@ -488,6 +490,7 @@ class FastActingStep:
     # -- a whole get_samples call as one graph launch --------------------------------------------------
     @staticmethod
     def _sink_key(sink):
+        # (a sink without a replay handle — acting/evaluator.EvalSink — is keyed by the object itself)
         h = getattr(sink, "_h", None)
         return ("replay", int(getattr(h, "value", None) or id(sink)))
 

@@ -273,6 +273,65 @@ k_catch_env_step(CatchArgs a, ActorPreArgs pre) {
   }
 }
 
+// The reference evaluation's counting rule (rltime/eval.py:59-72, loop :113-149) as ONE launch per vector step: of E
+// envs in parallel, the first N episodes that STARTED are counted, in the order the host loop meets them — step by
+// step, env by env — and an env's mask closes when the running count of started episodes passes N.  The sequential
+// loop is restated as two prefix sums over the envs: with c_i = done_i & open_i an episode goes to list position
+// counted + exclusive_scan(c)_i, and env i closes when started + inclusive_scan(done)_i > N.  Episode rewards
+// accumulate in float64 over the float32 step rewards like the reference's EpisodeTracker wrapper
+// (env_wrappers/common.py:25-28).  ONE workgroup walks the envs in env order in chunks of 256 and carries the two
+// running sums; a chunk's scan is wave shuffles plus one LDS hop across the four waves.  No atomics, nothing on the
+// host: the launch captures.  counters = {started, counted, steps, 0}; with counted == N at entry nothing is written.
+__global__ void __launch_bounds__(256)
+k_eval_count(int E, int N, int reset, const float* __restrict__ rewards, const uint8_t* __restrict__ dones,
+             double* __restrict__ acc, int32_t* __restrict__ len, uint8_t* __restrict__ open, int32_t* __restrict__ counters,
+             double* __restrict__ ep_reward, int32_t* __restrict__ ep_len) {
+  __shared__ int wave_sum[2][4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (reset) {
+    for (int e = tid; e < E; e += 256) { acc[e] = 0.0; len[e] = 0; open[e] = 1; }
+    if (tid < 4) counters[tid] = tid == 0 ? E : 0;
+    return;
+  }
+  const int started = counters[0], counted = counters[1], steps = counters[2];
+  if (counted >= N) return;                              // uniform: the quota is full, an over-run replay writes nothing
+  int carry_d = 0, carry_c = 0;                          // sums of done / of c over the chunks walked so far
+  for (int base = 0, it = 0; base < E; base += 256, ++it) {
+    const int e = base + tid;
+    const bool in = e < E;
+    const int d = in && dones[e] ? 1 : 0;
+    const int c = d && open[e] ? 1 : 0;
+    int v = d | (c << 16);                               // both scans in one word: a chunk's sums are <= 256
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(v, o);
+      if (lane >= o) v += t;
+    }
+    int* ws = wave_sum[it & 1];                          // alternate rows: one barrier per chunk is enough
+    if (lane == 63) ws[wave] = v;
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int w = 0; w < 4; ++w) { const int s = ws[w]; total += s; if (w < wave) before += s; }
+    v += before;
+    const int incl_d = carry_d + (v & 0xFFFF), excl_c = carry_c + (v >> 16) - c;
+    if (in) {
+      double a = acc[e] + (double)rewards[e];
+      int l = len[e] + 1;
+      if (c) {
+        const int pos = counted + excl_c;
+        if (pos < N) { ep_reward[pos] = a; ep_len[pos] = l; }
+      }
+      if (d) {
+        if (started + incl_d > N) open[e] = 0;
+        a = 0.0; l = 0;
+      }
+      acc[e] = a; len[e] = l;
+    }
+    carry_d += total & 0xFFFF; carry_c += total >> 16;
+  }
+  // every thread read the counters before the first barrier; E >= 1, so at least one barrier lies behind
+  if (tid == 0) { counters[0] = started + carry_d; counters[1] = counted + carry_c; counters[2] = steps + 1; }
+}
+
 }  // namespace mirl
 
 extern "C" int mirl_synth_env_step(int32_t E, int64_t frame_bytes, const uint8_t* pool, int32_t pool_n, uint64_t* clock, int32_t slot,
@@ -444,6 +503,19 @@ extern "C" int mirl_episode_track(int32_t E, int32_t A, const float* rewards, co
   mirl::ProfScope ps("k_episode_track", 0.0, (hipStream_t)stream);
   hipLaunchKernelGGL(mirl::k_episode_track, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, (int)E, (int)A, rewards, dones,
                      actions, ep_reward, ep_len, out_reward, out_len, action_counts);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
+extern "C" int mirl_eval_count(int32_t E, int32_t N, int32_t reset, const float* rewards, const uint8_t* dones, double* acc,
+                               int32_t* len, uint8_t* open, int32_t* counters, double* ep_reward, int32_t* ep_len, void* stream) {
+  // (E <= N: the reference's assertion, eval.py:74 — the E episodes under way at the reset all count)
+  if (E <= 0 || E > 65535 || N < E || (reset != 0 && reset != 1) || (!reset && (!rewards || !dones)) || !acc || !len || !open ||
+      !counters || !ep_reward || !ep_len)
+    return mirl::fail(MIRL_ERR_ARG, "bad eval_count arguments (1 <= E <= 65535, E <= N = episode_count, reset 0 | 1, no null operands)");
+  mirl::ProfScope ps("k_eval_count", 0.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_eval_count, dim3(1), dim3(256), 0, (hipStream_t)stream, (int)E, (int)N, (int)reset, rewards, dones, acc, len,
+                     open, counters, ep_reward, ep_len);
   MIRL_LAUNCH_CHECK();
   return MIRL_OK;
 }

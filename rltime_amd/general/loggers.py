@@ -25,6 +25,9 @@ class NullLogger:
     def save_checkpoint(self, data, step):
         pass
 
+    def get_checkpoint(self):
+        raise RuntimeError("this logger keeps no checkpoint: only a DirectoryLogger can read one back")
+
 
 class DirectoryLogger(NullLogger):
     def __init__(self, path, echo=True):
@@ -46,6 +49,11 @@ class DirectoryLogger(NullLogger):
         with open(os.path.join(self.path, "config.json"), "w") as f:
             json.dump(config, f, indent=2, default=str)
 
+    def get_config(self):
+        """loggers.py:157-158: the run's config.json, through the config loader."""
+        from rltime_amd.general.config import load_config
+        return load_config(os.path.join(self.path, "config.json"))
+
     def log_result(self, name, data, step):
         super().log_result(name, data, step)
         with open(os.path.join(self.path, name + ".json"), "a") as f:
@@ -54,3 +62,9 @@ class DirectoryLogger(NullLogger):
     def save_checkpoint(self, data, step):
         with open(os.path.join(self.path, "checkpoint.p"), "wb") as f:
             pickle.dump({"step": step, "data": data}, f)
+
+    def get_checkpoint(self):
+        """loggers.py:186-192: (global step, data) of the last checkpoint."""
+        with open(os.path.join(self.path, "checkpoint.p"), "rb") as f:
+            cp = pickle.load(f)
+        return cp["step"], cp["data"]

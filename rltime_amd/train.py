@@ -78,6 +78,8 @@ def train(config, logger=None, device="cuda", device_acting=True, data_parallel=
     trainer = trainer_cls(logger=logger, actors=actors, model_config=config["model"],
                           policy_args=config.get("policy_args", {}))
     trainer.data_parallel = data_parallel
+    # the periodic evaluation (training args eval_episodes) steps envs of its own, keyed apart from the acting envs
+    trainer.eval_env_factory = lambda n: make_vec_env(config.get("env"), config.get("env_args"), n, device, seed=1)
     if resume:
         trainer.resume_from = resume
     if on_trainer is not None:

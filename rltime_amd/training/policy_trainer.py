@@ -29,6 +29,8 @@ class PolicyTrainer:
         self.resume_from = None         # directory of a run written with full_checkpoints=True (training/resume.py)
         self.full_checkpoints = False
         self._full_checkpoint_due = False
+        self.eval_env_factory = None    # num_envs -> a fresh device vector env for the periodic evaluation (train.train sets it)
+        self.eval_episodes = 0
 
     # -- hooks for subclasses ------------------------------------------------
     @staticmethod
@@ -188,6 +190,23 @@ class PolicyTrainer:
         self.logger.log_result("train", row, self.steps)
         self.logger.save_checkpoint(
             {"policy_state": self.policy.get_state(), "train_state": self._get_train_state()}, self.steps)
+        if self.eval_episodes > 0:
+            self._evaluate()
+
+    def _evaluate(self):
+        """The current policy on an env, actor and carry of the evaluation's own (acting/evaluator.py): nothing of the
+        training run is touched and no global generator is drawn from, so the run's weights do not depend on it."""
+        import time
+        from rltime_amd.acting.evaluator import Evaluator
+        from rltime_amd.eval import make_record
+        env = self.eval_env_factory(self.eval_envs)
+        try:
+            t0 = time.time()
+            got = Evaluator(self.policy, env, self.eval_episodes, eps=self.eval_eps).run()
+            row = make_record(self.steps, got, time.time() - t0)
+        finally:
+            env.close()
+        self.logger.log_result("eval", row, self.steps)
 
     # -- entry point -----------------------------------------------------------------
     def save_full_checkpoint(self):
@@ -209,10 +228,24 @@ class PolicyTrainer:
         self._full_checkpoint_due = False
 
     def train(self, total_steps, log_freq=10000, target_update_freq=0, clip_rewards=False,
-              early_stop_steps=None, episode_history_windows=[10, 100], full_checkpoints=False, **kwargs):
+              early_stop_steps=None, episode_history_windows=[10, 100], full_checkpoints=False,
+              eval_episodes=0, eval_envs=None, eval_eps=0.0, **kwargs):
         """policy_trainer.py:284-325.  full_checkpoints (not in the reference): also write
         a resumable checkpoint (replay shard, optimizer, RNG streams, counters) at every
-        log interval; `python -m rltime_amd.train ... --resume <log dir>` continues it."""
+        log interval; `python -m rltime_amd.train ... --resume <log dir>` continues it.
+        eval_episodes > 0 (not in the reference): every log row is followed by an evaluation of the current policy over
+        that many episodes on `eval_envs` envs (default: the acting env count) with epsilon `eval_eps`, logged as an
+        `eval` row (rltime_amd/eval.py has the record's keys)."""
+        self.eval_episodes, self.eval_eps = int(eval_episodes or 0), float(eval_eps)
+        if self.eval_episodes > 0:
+            if self.data_parallel is not None:
+                raise ValueError("eval_episodes: periodic evaluation is not built for a process group (evaluate the run "
+                                 "directory with python -m rltime_amd.eval)")
+            if self.eval_env_factory is None:
+                raise ValueError("eval_episodes needs trainer.eval_env_factory (rltime_amd.train.train sets it)")
+            self.eval_envs = int(eval_envs) if eval_envs else min(self.actors.get_env_count(), self.eval_episodes)
+            if self.eval_envs > self.eval_episodes:
+                raise ValueError("eval_envs can't be higher than eval_episodes")
         self.full_checkpoints = full_checkpoints
         self.total_steps, self.early_stop_steps = total_steps, early_stop_steps
         self.log_freq, self.target_update_freq = log_freq, target_update_freq
@@ -221,6 +254,8 @@ class PolicyTrainer:
         self.clock = IntervalClock()
         self.steps = 0
         self.init_policies()
+        if self.eval_episodes > 0 and not getattr(self.policy, "is_cuda", lambda: False)():
+            raise ValueError("eval_episodes: periodic evaluation runs the device actor; this policy is on the CPU")
         self.update_actors()
         logging.getLogger().info("training starts with %d acting envs", self.actors.get_env_count())
         self._train(**kwargs)
