@@ -843,6 +843,22 @@ int mirl_episode_track(int32_t E, int32_t A, const float* rewards, const uint8_t
  * no atomics, no host state: capturable.  1 <= E <= 65535 and E <= N (eval.py:74), else MIRL_ERR_ARG before any launch.    */
 int mirl_eval_count(int32_t E, int32_t N, int32_t reset, const float* rewards, const uint8_t* dones, double* acc, int32_t* len,
                     uint8_t* open, int32_t* counters, double* ep_reward, int32_t* ep_len, void* stream);
+/* The reference's ExtraFeaturesEnvWrapper on the device (csrc/acting.hip k_extra_features; rltime/env_wrappers/common.py:221-332
+ * under an auto-resetting vector env, vec_env/simple.py:25-29).  X = (include_action ? A : 0) + include_timestep + include_reward
+ * floats per env, laid out [one-hot action | timestep | reward]; mirl_extra_features_size returns X, MIRL_ERR_ARG for X == 0,
+ * A outside [1, 4096] or a flag that is not 0 | 1.                                                                           */
+int mirl_extra_features_size(int32_t A, int32_t include_action, int32_t include_reward, int32_t include_timestep, int32_t* X);
+/* One vector step: reads the action just executed (int32 [E]), the raw reward (float32 [E]), done (uint8 [E]) and the env's
+ * timesteps-since-reset counter (int32 [E], updated) and writes the feature row of the observation that follows.  done: the
+ * reset row (one-hot of action 0, timestep 0, reward 0), counter = 0.  Else counter += 1, one-hot of the action (an action
+ * outside [0, A) sets no element), timestep = (float)((double)counter * timestep_scale), reward = sign(r) with clip_reward
+ * else r.  The row goes to compact + e * X (float32 [E, X]) and to pitched + e * pitch + col0 (pitch in floats); either may
+ * be NULL; nothing else is written.  One thread per env, no atomics, no host state or synchronisation: capturable.
+ * MIRL_ERR_ARG before any launch for bad arguments (as for _size; E < 1; a NULL input; col0 < 0 or col0 + X > pitch).        */
+int mirl_extra_features_step(int32_t E, int32_t A, int32_t include_action, int32_t include_reward, int32_t include_timestep,
+                             int32_t clip_reward, double timestep_scale, const int32_t* actions, const float* rewards,
+                             const uint8_t* dones, int32_t* counters, float* compact, float* pitched, int64_t pitch,
+                             int64_t col0, void* stream);
 
 /* ---- device copy micro-benchmark used by bench.py for the measured HBM peak */
 int mirl_copy_bytes(void* dst, const void* src, int64_t bytes, void* stream);

@@ -235,6 +235,8 @@ _SIGNATURES = {
                        _vp, _vp, _u64, _vp],
     "mirl_episode_track": [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mirl_eval_count": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mirl_extra_features_size": [_i32, _i32, _i32, _i32, _P(_i32)],
+    "mirl_extra_features_step": [_i32, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp],
     "mirl_copy_bytes": [_vp, _vp, _i64, _vp],
     "mirl_copy_bytes_ex": [_vp, _vp, _i64, _i32, _vp],
     "mirl_book_create": [_P(ReplayConfig), _P(_vp)],

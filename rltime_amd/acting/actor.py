@@ -33,7 +33,8 @@ class GraphedStep:
     def __init__(self, actor, obs, dones):
         pol, self.actor = actor._policy, actor
         dev = pol.device()
-        self.obs, self.dones = obs.clone(), dones.clone()
+        # (a tuple observation — frames + extra feature rows, acting/extra_features.py — keeps a static copy per part)
+        self.obs, self.dones = deep_apply(obs, lambda x: x.clone()), dones.clone()
         self.eps = torch.zeros((), dtype=torch.float64, device=dev)
         self.rec = [layer for layer in pol.model.layers if layer.is_recurrent()]
         self.carry = [tuple(t.clone() for t in layer.last_state) for layer in self.rec]
@@ -75,12 +76,17 @@ class GraphedStep:
             self.b_actions, self.b_q = tail(self.states)
 
     def after_env_step(self, obs, dones, eps):
-        self.obs.copy_(obs)
+        if isinstance(obs, (tuple, list)):
+            for dst, src in zip(self.obs, obs):
+                dst.copy_(src)
+        else:
+            self.obs.copy_(obs)
         self.dones.copy_(dones)
         self.eps.fill_(eps)
         self.graph_a.replay()
         fields = {k: v.clone() for k, v in self.fields.items() if k != "frames"}
-        fields["frames"] = obs                    # the env's own tensor; the static copy is overwritten next step
+        # the env's own tensor; the static copy is overwritten next step
+        fields["frames"] = obs[0] if isinstance(obs, (tuple, list)) else obs
         return fields, self.next_actions.clone(), self.next_q.clone()
 
     def reselect(self, eps):
@@ -300,7 +306,7 @@ class Actor(ActingInterface):
                 pf = self._action_space.n if sink._keep_policy else 0
                 sink.configure(fs.example, self._num_envs, self._base_env_id, policy_f32=pf)
                 if getattr(sink, "_dedup", False) and fs.trusted_stack and not getattr(sink, "_acting_priority_init", False):
-                    sink.prime_stack(self._reset_obs)
+                    sink.prime_stack(self._reset_obs[0] if isinstance(self._reset_obs, (tuple, list)) else self._reset_obs)
             keep_policy = bool(sink._policy_f32)
         out = None
         if fs.can_rollout(iters, sink) and fs.rollout(iters, sink, keep_policy=keep_policy, clip=self.clip_rewards):

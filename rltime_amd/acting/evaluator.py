@@ -73,7 +73,7 @@ class EvalSink:
     def plan_ingest(self, iters, num_envs):
         pass                                   # nothing is decided on the host
 
-    def ingest_planned(self, k, obs, actions, rewards, dones, state=None, initials=None, policy=None):
+    def ingest_planned(self, k, obs, actions, rewards, dones, extra=None, state=None, initials=None, policy=None):
         self.count(rewards, dones)
 
     def update_batch(self, obs, actions, rewards, dones, **kwargs):
@@ -130,6 +130,10 @@ class Evaluator:
         self._started = True
         rec = self._recurrent()
         keep = [layer.last_state for layer in rec]           # the eager training actor's carry lives here
+        for layer in rec:
+            # the evaluation's first input state is all-initial on ITS env count: a carry left by a learner forward has the
+            # training batch's rows (restored below)
+            layer.last_state = None
         devices = [self.device] if self.device.type == "cuda" else []
         try:
             with torch.random.fork_rng(devices=devices), torch.no_grad():

@@ -82,7 +82,10 @@ class FastActingStep:
             (cnn, fc), lstm = layers, None
         else:
             return None
-        if not (isinstance(cnn, CNN) and isinstance(fc, FC)) or model.extra_input_layer is not None:
+        if not (isinstance(cnn, CNN) and isinstance(fc, FC)):
+            return None
+        # extras (a tuple observation's second part, acting/extra_features.py) are taken into the recurrent layer only
+        if model.extra_input_layer is not None and not (lstm is not None and model.extra_input_layer == 1):
             return None
         dueling = getattr(pol, "value_layer", None) is not None
         if dueling:
@@ -118,6 +121,15 @@ class FastActingStep:
             if expl is not None and not hasattr(expl, "_device_exponents"):
                 return False
             space = actor._vec_env.observation_space
+            if pol.model.extra_input_layer is not None:
+                # the env writes the extras rows itself, into the step's static buffers (ExtraFeaturesVecEnv.write_extras)
+                env = actor._vec_env
+                if not (hasattr(space, "spaces") and len(space.spaces) == 2 and hasattr(env, "write_extras")
+                        and int(env.extra_size) == int(pol.model.extra_input_shape[0])):
+                    return False
+                space = space.spaces[0]
+            elif hasattr(space, "spaces"):
+                return False
             probe = torch.empty((1,) + tuple(space.shape), dtype=torch.uint8, device=pol.device())
             return bool(conv_u8_supported(probe, cnn.layers[0])) and hasattr(actor._vec_env, "step_device")
         except Exception:
@@ -135,6 +147,11 @@ class FastActingStep:
         self.Z = pol.num_atoms if self.c51 else 1
         self.need_q = bool(need_q) or self.c51
         self.cnn, self.lstm, self.fc, self.dueling = self._parts(pol)
+        if isinstance(obs0, (tuple, list)):                       # (frames, extras): the extras rows are written below
+            obs0 = obs0[0]
+        # extras into the recurrent layer: X floats per env, padded to Xp in the LSTM product's input rows (K % 16 holds)
+        X = self.X = int(pol.model.extra_input_shape[0]) if pol.model.extra_input_layer is not None else 0
+        Xp = self.Xp = (X + 15) // 16 * 16
         self.fc_layer = pol.model.layers[-1]
         self.iqn = hasattr(pol, "num_sampling_quantiles")
         self.N = pol.num_sampling_quantiles if self.iqn else 1
@@ -142,7 +159,8 @@ class FastActingStep:
         E = self.E = actor._num_envs
         # without a recurrent layer (H = 0) the head reads the conv features themselves
         H = self.H = self.lstm.num_units if self.lstm is not None else 0
-        F = self.F = self.lstm.inp_size if self.lstm is not None else self.fc.in_features
+        F = self.F = self.lstm.inp_size - X if self.lstm is not None else self.fc.in_features
+        K = self.K = F + Xp + H                                   # the LSTM product's row: [features | extras, padded | masked h]
         W = self.W = H if self.lstm is not None else F            # width of the head's input rows
         A = self.A = actor._action_space.n
         f32 = dict(dtype=torch.float32, device=dev)
@@ -153,7 +171,8 @@ class FastActingStep:
         need = C.c_int64()
         check(lib.mirl_conv1_u8_wpk_floats(C.byref(need)))
         self.wpk = torch.empty(need.value, **f32)
-        self.xh = torch.zeros((E, F + H), **f32)                 # [conv features (NCHW order) | masked h]
+        self.xh = torch.zeros((E, K), **f32)                     # [conv features (NCHW order) | extras | zeros | masked h]
+        self.extra = torch.zeros((E, X), **f32) if X else None   # the compact rows the replay ingests as `extra`
         self.c_in = torch.zeros((E, H), **f32)
         self.h = torch.zeros((E, H), **f32)                      # raw carry (outputs of the last cell)
         self.c = torch.zeros((E, H), **f32)
@@ -172,7 +191,7 @@ class FastActingStep:
             self.rng_seed = int(actor._rng_seed) & 0x7FFFFFFFFFFFFFFF
         if self.lstm is not None:
             self.bias_sum = torch.empty(4 * H, **f32)
-            self.wcat = torch.empty((4 * H, F + H), **f32)
+            self.wcat = torch.empty((4 * H, K), **f32) if not X else torch.zeros((4 * H, K), **f32)   # (padding columns stay 0)
         h1, hv = self.fc.out_features, (pol.value_hidden_layer.out_features if self.dueling else 0)
         self.h1 = h1
         self.fc_w = torch.empty((h1 + hv, self.fc.in_features), **f32)
@@ -207,7 +226,7 @@ class FastActingStep:
                 self.w2p = torch.empty((64, k2 * k2 * c2.in_channels), **f32)
                 self.w3p = torch.empty((64, k3 * k3 * c3.in_channels), **f32)
                 self.conv_dims = (h1o, w1o, h2o, w2o, h3o, w3o)
-        self.f_lstm = self.lstm is not None and bool(lib.mirl_act_lstm_supported(E, H, F + H))
+        self.f_lstm = self.lstm is not None and bool(lib.mirl_act_lstm_supported(E, H, K))
         D = int(self.freq.shape[0]) if self.iqn else 0
         # (the output layer in the hidden layer's epilogue selects on scalar Q values: not for C51's distributions)
         self.f_head = not self.c51 and E * self.N <= 2048 and self.fc.in_features == W and self.dueling \
@@ -221,7 +240,7 @@ class FastActingStep:
             self.part = torch.zeros(parts.value * E * self.N * pitch.value, **f32)
         if self.f_lstm:
             need = C.c_int64()
-            check(lib.mirl_act_lstm_workspace_bytes(E, H, F + H, C.byref(need)))
+            check(lib.mirl_act_lstm_workspace_bytes(E, H, K, C.byref(need)))
             self.lstm_ws = torch.zeros((need.value + 3) // 4, dtype=torch.int32, device=dev)   # zero once: the kernel restores it
         self.in_kernel_taus = self.iqn and getattr(pol, "tau_source", None) is None
         expl = actor._exploration
@@ -247,12 +266,15 @@ class FastActingStep:
         self._rollouts = {}              # (iters, keep_policy, clip, sink id) -> [calls so far, CUDAGraph or None]
         self.rollout_graphs = os.environ.get("MIRL_ROLLOUT_GRAPH", "1") != "0"
         self.rollout_eager_calls = int(os.environ.get("MIRL_ROLLOUT_EAGER_CALLS", "0"))
-        assert self.lstm is None or self.lstm.lstm_cell.weight_ih.shape == (4 * H, F)
+        assert self.lstm is None or self.lstm.lstm_cell.weight_ih.shape == (4 * H, F + X)
         # the reference's first input state: every env starts an episode (actor.py:78-89)
         self.refresh()
         self._pre(torch.zeros(E, **f32), torch.ones(E, dtype=torch.uint8, device=dev), track=False)
+        if X:
+            env.reset_extras(self.extra, self.xh, K, F)           # the reset rows (the same launch with dones all 1)
         if self.lstm is not None:
-            self.example = {"x": obs0[0].cpu().numpy(), "layer0_state": {},
+            x0 = obs0[0].cpu().numpy()
+            self.example = {"x": (x0, np.zeros(X, np.float32)) if X else x0, "layer0_state": {},
                             "layer1_state": {"hx": np.zeros(H, np.float32), "cx": np.zeros(H, np.float32), "initials": np.float32(1.0)},
                             "layer2_state": {}}
         else:
@@ -261,21 +283,24 @@ class FastActingStep:
 
     # -- weight-only quantities, once per get_samples call -------------------------------
     def refresh(self):
-        pol, F = self.pol, self.F
+        pol, F, X = self.pol, self.F, self.X
         with torch.no_grad():
             if self.lstm is not None:
                 cell = self.lstm.lstm_cell
+                w_ih = cell.weight_ih if not X else cell.weight_ih[:, :F]
                 torch.add(cell.bias_ih, cell.bias_hh, out=self.bias_sum)
                 if self.f_conv:
                     # layer 3 writes its NHWC rows straight into xh: W_ih's columns follow (same products, modules.LSTM._flat_input)
                     c2, c3 = self.cnn.layers[1], self.cnn.layers[2]
                     h3o, w3o = self.conv_dims[4], self.conv_dims[5]
-                    self.wcat[:, :F].view(-1, h3o, w3o, 64).copy_(cell.weight_ih.view(-1, 64, h3o, w3o).permute(0, 2, 3, 1))
+                    self.wcat[:, :F].view(-1, h3o, w3o, 64).copy_(w_ih.view(-1, 64, h3o, w3o).permute(0, 2, 3, 1))
                     self.w2p.view(64, c2.kernel_size[0], c2.kernel_size[1], c2.in_channels).copy_(c2.weight.permute(0, 2, 3, 1))
                     self.w3p.view(64, c3.kernel_size[0], c3.kernel_size[1], c3.in_channels).copy_(c3.weight.permute(0, 2, 3, 1))
                 else:
-                    self.wcat[:, :F].copy_(cell.weight_ih)
-                self.wcat[:, F:].copy_(cell.weight_hh)
+                    self.wcat[:, :F].copy_(w_ih)
+                if X:
+                    self.wcat[:, F:F + X].copy_(cell.weight_ih[:, F:])
+                self.wcat[:, F + self.Xp:].copy_(cell.weight_hh)
             na = self.na
             # one multi-tensor copy for the head's buffers instead of a launch each (the T = 1 configs refresh every learner step)
             dst = [self.fc_w[:self.h1], self.fc_b[:self.h1], self.out_w[:na, :self.h1], self.adv_w, self.out_b[:na]]
@@ -292,7 +317,7 @@ class FastActingStep:
     def _pre_args(self, tr, row, clip):
         rec = self.H > 0
         return (self.H, self.A, ptr(self.actions), ptr(self.h) if rec else None, ptr(self.c) if rec else None,
-                C.c_void_p(self.xh.data_ptr() + 4 * self.F) if rec else None, self.F + self.H,
+                C.c_void_p(self.xh.data_ptr() + 4 * (self.F + self.Xp)) if rec else None, self.K,
                 ptr(self.c_in) if rec else None, ptr(self.state_pack) if rec else None, ptr(self.initials),
                 ptr(self.rewards), ptr(self.dones), 1 if clip else 0,
                 ptr(tr.ep_reward) if tr is not None else None, ptr(tr.ep_len) if tr is not None else None,
@@ -326,6 +351,13 @@ class FastActingStep:
         env.advance_host()
         return self.obs_buf
 
+    def _extras(self, rewards, dones_u8):
+        """The extras rows of the observation that follows this step (csrc/acting.hip k_extra_features, issued by the env
+        wrapper that owns the timestep counters): reads the env's RAW rewards / dones and self.actions — still the actions
+        just executed, the head overwrites them later in the step — and writes the compact block the ingest takes and
+        the extras columns of xh."""
+        self.actor._vec_env.write_extras(self.actions, rewards, dones_u8, self.extra, self.xh, self.K, self.F)
+
     def _conv1(self, obs, packed=False):
         """packed=True: self.wpk still holds the current weights (packed by the call's re-selection)."""
         c1 = self.cnn.layers[0]
@@ -342,16 +374,16 @@ class FastActingStep:
             h1o, w1o, h2o, w2o, h3o, w3o = self.conv_dims
             check(lib.mirl_act_conv_fwd(2, E, h1o, w1o, ptr(self.y1), ptr(self.w2p), ptr(c2.bias), ptr(self.y2), h2o * w2o * 64, stream()),
                   "mirl_act_conv_fwd")
-            check(lib.mirl_act_conv_fwd(3, E, h2o, w2o, ptr(self.y2), ptr(self.w3p), ptr(c3.bias), ptr(self.xh), F + H, stream()),
+            check(lib.mirl_act_conv_fwd(3, E, h2o, w2o, ptr(self.y2), ptr(self.w3p), ptr(c3.bias), ptr(self.xh), self.K, stream()),
                   "mirl_act_conv_fwd")
         else:
             x = self.y1
             for layer in self.cnn.layers[1:]:
                 x = conv_bias_relu(x, layer)
             ch, hh, ww = x.shape[1:]
-            torch.as_strided(self.xh, (E, ch, hh, ww), (F + H, hh * ww, ww, 1)).copy_(x)   # NHWC -> the reference's (C, H, W) flatten
+            torch.as_strided(self.xh, (E, ch, hh, ww), (self.K, hh * ww, ww, 1)).copy_(x)   # NHWC -> the reference's (C, H, W) flatten
         if self.f_lstm:
-            check(lib.mirl_act_lstm_fwd(E, H, F + H, ptr(self.xh), F + H, ptr(self.wcat), ptr(self.bias_sum), ptr(self.c_in), ptr(self.h),
+            check(lib.mirl_act_lstm_fwd(E, H, self.K, ptr(self.xh), self.K, ptr(self.wcat), ptr(self.bias_sum), ptr(self.c_in), ptr(self.h),
                                         ptr(self.c), ptr(self.lstm_ws), stream()), "mirl_act_lstm_fwd")
         elif self.lstm is not None:
             torch.addmm(self.bias_sum, self.xh, self.wcat.t(), out=self.gates)
@@ -460,11 +492,23 @@ class FastActingStep:
         with the env step (env_step_pre)."""
         if not pre_done:
             dones_u8 = dones.view(torch.uint8) if dones.dtype == torch.bool else dones.to(torch.uint8)
-            self._pre(rewards if rewards.dtype == torch.float32 else rewards.float(), dones_u8, clip=clip)
+            rewards = rewards if rewards.dtype == torch.float32 else rewards.float()
+            self._pre(rewards, dones_u8, clip=clip)
+        if self.X:
+            if isinstance(obs, (tuple, list)):
+                # an env stepped through step_device has written its rows (and advanced its counters) already
+                obs, rows = obs
+                self.extra.copy_(rows)
+                self.xh[:, self.F:self.F + self.X].copy_(rows)
+            elif pre_done:
+                self._extras(self.env_rewards, self.env_dones)
+            else:
+                self._extras(rewards, dones_u8)
         fields = None
         if sink is not None:
             rec = self.H > 0
             sink.update_batch(obs, self.actions, self.rewards, self.dones, state=self.state_pack if rec else None,
+                              **({"extra": self.extra} if self.X else {}),
                               initials=self.initials if rec else None,
                               policy=self.qvalues if keep_policy else None, transient=True,
                               # acting-time priority init reads whole stored stacks through the verifying ingest
@@ -477,6 +521,8 @@ class FastActingStep:
                           policy=self.qvalues.clone(), rewards=self.rewards.clone(), dones=self.dones.clone(), episode_stats=None)
             if self.H > 0:
                 fields.update(state=self.state_pack.clone(), initials=self.initials.clone())
+            if self.X:
+                fields.update(extra=self.extra.clone())
         self.last_obs = obs
         self._conv1(obs, packed=True)
         self.graph.replay()
@@ -512,7 +558,10 @@ class FastActingStep:
                 obs, rewards, dones = self.env_step()
                 self._pre(rewards, dones, clip=clip, row=k)
             rec = self.H > 0
+            if self.X:
+                self._extras(self.env_rewards, self.env_dones)
             sink.ingest_planned(k, obs, self.actions, self.rewards, self.dones, state=self.state_pack if rec else None,
+                                **({"extra": self.extra} if self.X else {}),
                                 initials=self.initials if rec else None, policy=self.qvalues if keep_policy else None)
             self._conv1(obs, packed=True)
             self._body()
@@ -572,12 +621,17 @@ class FastActingStep:
         st = {k: getattr(self, k).detach().clone().cpu() for k in keys}
         st["xh"] = self.xh[:, self.F:].detach().clone().cpu()
         st.update(step_no=self.step_no, last_obs=self.last_obs.detach().clone().cpu())
+        if self.X:                               # (xh[:, F:] above holds the extras columns; the counters live in the env wrapper)
+            st.update(extra=self.extra.detach().clone().cpu(), extra_counters=self.actor._vec_env._counters.detach().clone().cpu())
         return st
 
     def set_state(self, st):
         for k in ("h", "c", "c_in", "state_pack", "initials", "actions", "qvalues", "rewards", "dones"):
             getattr(self, k).copy_(st[k].to(self.dev))
         self.xh[:, self.F:].copy_(st["xh"].to(self.dev))
+        if self.X:
+            self.extra.copy_(st["extra"].to(self.dev))
+            self.actor._vec_env._counters.copy_(st["extra_counters"].to(self.dev))
         self.step_no = st["step_no"]
         self.rng_step.fill_(self.step_no)
         self.last_obs = st["last_obs"].to(self.dev)

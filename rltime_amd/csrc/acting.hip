@@ -332,7 +332,73 @@ k_eval_count(int E, int N, int reset, const float* __restrict__ rewards, const u
   if (tid == 0) { counters[0] = started + carry_d; counters[1] = counted + carry_c; counters[2] = steps + 1; }
 }
 
+// The extra-features observation of the reference's ExtraFeaturesEnvWrapper (env_wrappers/common.py:221-332) under an
+// auto-resetting vector env (vec_env/simple.py:25-29), for the observation that FOLLOWS the step whose action, raw reward
+// and done are read here: row = [one-hot last action (A) | timesteps since reset * scale | last reward], each part only
+// when included.  done: the reset row (one-hot of action 0 — the wrapper's reset sets _last_action = 0 —, timestep 0,
+// reward 0) and the counter restarts at 0; else the counter advances by one first (common.py:331) and the timestep is the
+// Python product int * float in double, cast to float32 (_make_features' astype).  One thread per env reads and writes
+// the env's counter and writes its X floats to both destinations: no exchange, no atomics.
+__global__ void __launch_bounds__(256)
+k_extra_features(int E, int A, int inc_action, int inc_reward, int inc_timestep, int clip, double scale,
+                 const int32_t* __restrict__ actions, const float* __restrict__ rewards, const uint8_t* __restrict__ dones,
+                 int32_t* __restrict__ counters, float* __restrict__ compact, int X, float* __restrict__ pitched, int64_t pitch) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= E) return;
+  const bool dn = dones[e] != 0;
+  const int t = dn ? 0 : counters[e] + 1;
+  counters[e] = t;
+  const int a = dn ? 0 : actions[e];
+  float r = dn ? 0.f : rewards[e];
+  if (clip) r = r > 0.f ? 1.f : (r < 0.f ? -1.f : (r == 0.f ? 0.f : r));      // np.sign (a NaN stays a NaN)
+  const float ts = (float)((double)t * scale);
+  float* c = compact ? compact + (int64_t)e * X : nullptr;
+  float* p = pitched ? pitched + (int64_t)e * pitch : nullptr;
+  int j = 0;
+  if (inc_action) {
+    for (int k = 0; k < A; ++k, ++j) {                    // an action outside [0, A) matches no k
+      const float v = k == a ? 1.f : 0.f;
+      if (c) c[j] = v;
+      if (p) p[j] = v;
+    }
+  }
+  if (inc_timestep) { if (c) c[j] = ts; if (p) p[j] = ts; ++j; }
+  if (inc_reward) { if (c) c[j] = r; if (p) p[j] = r; ++j; }
+}
+
 }  // namespace mirl
+
+static int extra_size(int32_t A, int32_t inc_action, int32_t inc_reward, int32_t inc_timestep) {
+  // the wrapper's _calc_size; -1 for arguments outside the domain (flags 0 | 1, 1 <= A <= 4096)
+  if (A < 1 || A > 4096 || (inc_action | inc_reward | inc_timestep) & ~1) return -1;
+  return (inc_action ? A : 0) + inc_reward + inc_timestep;
+}
+
+extern "C" int mirl_extra_features_size(int32_t A, int32_t include_action, int32_t include_reward, int32_t include_timestep,
+                                        int32_t* X) {
+  const int x = extra_size(A, include_action, include_reward, include_timestep);
+  if (!X || x <= 0)
+    return mirl::fail(MIRL_ERR_ARG, "bad extra_features_size arguments (1 <= A <= 4096, flags 0 | 1, at least one feature included)");
+  *X = x;
+  return MIRL_OK;
+}
+
+extern "C" int mirl_extra_features_step(int32_t E, int32_t A, int32_t include_action, int32_t include_reward, int32_t include_timestep,
+                                        int32_t clip_reward, double timestep_scale, const int32_t* actions, const float* rewards,
+                                        const uint8_t* dones, int32_t* counters, float* compact, float* pitched, int64_t pitch,
+                                        int64_t col0, void* stream) {
+  const int x = extra_size(A, include_action, include_reward, include_timestep);
+  if (E <= 0 || x <= 0 || (clip_reward != 0 && clip_reward != 1) || !actions || !rewards || !dones || !counters ||
+      (pitched && (col0 < 0 || pitch < col0 + x)))
+    return mirl::fail(MIRL_ERR_ARG, "bad extra_features_step arguments (1 <= A <= 4096, flags 0 | 1, at least one feature included, "
+                                    "no null inputs, 0 <= col0 and col0 + X <= pitch)");
+  mirl::ProfScope ps("k_extra_features", 0.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_extra_features, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, (int)E, (int)A, (int)include_action,
+                     (int)include_reward, (int)include_timestep, (int)clip_reward, timestep_scale, actions, rewards, dones, counters,
+                     compact, x, pitched ? pitched + col0 : nullptr, pitch);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
 
 extern "C" int mirl_synth_env_step(int32_t E, int64_t frame_bytes, const uint8_t* pool, int32_t pool_n, uint64_t* clock, int32_t slot,
                                    uint64_t seed, float p_neg, float p_nonpos, float p_done, uint8_t* obs, float* rewards,

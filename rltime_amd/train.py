@@ -23,7 +23,33 @@ from rltime_amd.general.type_registry import get_registered_type
 from rltime_amd.general.utils import deep_dictionary_update
 
 
+_EXTRA_FEATURES_KEYS = ("include_action", "include_reward", "include_timestep", "clip_reward", "timestep_scale", "use_real_done")
+
+
 def make_vec_env(env, env_args, num_envs, device, seed=0):
+    """env_args["extra_features"] (true: the defaults; a dict: the wrapper's arguments) wraps 'catch' / 'synthetic-atari'
+    in acting/extra_features.ExtraFeaturesVecEnv — the reference's env_args.wrappers entry of ExtraFeaturesEnvWrapper."""
+    env_args = dict(env_args or {})
+    extra = env_args.pop("extra_features", None)
+    if extra is None or extra is False:
+        return _make_base_vec_env(env, env_args, num_envs, device, seed)
+    # (refused before any env is built)
+    if isinstance(env, str) and env.startswith("CartPole-"):
+        raise ValueError("extra_features: the CartPole envs step on the CPU; the extra-features wrapper is a device kernel "
+                         "and wraps 'catch' and 'synthetic-atari' only")
+    if extra is not True and not isinstance(extra, dict):
+        raise ValueError("extra_features: true (the wrapper's defaults) or a dict of its arguments %s" % (_EXTRA_FEATURES_KEYS,))
+    kwargs = {} if extra is True else dict(extra)
+    unknown = set(kwargs) - set(_EXTRA_FEATURES_KEYS)
+    if unknown:
+        raise ValueError("extra_features: unknown arguments %s (known: %s)" % (sorted(unknown), list(_EXTRA_FEATURES_KEYS)))
+    if not any(bool(kwargs.get(k, True)) for k in _EXTRA_FEATURES_KEYS[:3]):
+        raise ValueError("extra_features: at least one of include_action / include_reward / include_timestep")
+    from rltime_amd.acting.extra_features import ExtraFeaturesVecEnv
+    return ExtraFeaturesVecEnv(_make_base_vec_env(env, env_args, num_envs, device, seed), **kwargs)
+
+
+def _make_base_vec_env(env, env_args, num_envs, device, seed=0):
     if isinstance(env, str) and env.startswith("CartPole-"):
         # the CPU plumbing config (BASELINE configs[0]): the build's own cart-pole, v0 = 200-step episodes, v1 = 500
         from rltime_amd.acting.cartpole_env import CartPoleVecEnv
