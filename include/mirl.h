@@ -512,6 +512,42 @@ int mirl_conv1_u8_wrw_masked(int64_t N, int32_t H, int32_t W, const uint8_t* x, 
                              float* scratch, float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w,
                              float* db, void* stream);
 
+/* ---- the same input layer from ONE-plane frames (csrc/conv_in1p.hip): the reference's recurrent set-up
+ * (configs/atari_iqn_lstm.json with env_wrappers/atari_lstm.json, "stack": 1) feeds Conv2d(1 -> 32, kernel 8,
+ * stride 4) with unstacked (1, H, W) uint8 observations.  A second kernel family, because the 4-plane one gives an
+ * MFMA k-group to a plane; here a k-group is a kernel row.  bf16 matrix pipe with an f32 result: pixels are exact in
+ * bf16, weight * scale (forward) or the gradient (backward) is split exactly into three bf16 parts.
+ *   x       uint8 [N][1][H][W] (the replay's gathered rows, as stored)
+ *   weight  float, logical [32][1][8][8] with element strides ws_o, ws_h, ws_w (contiguous or channels_last memory)
+ *   y       float [N][OH][OW][32] = relu(conv(x * scale, weight) + bias), NHWC; OH = (H-8)/4+1, OW likewise
+ *   wpk     scratch, *out of mirl_conv1p_u8_wpk_floats() floats (the weight parts in MFMA operand order)
+ *   flags   bit 3 = wpk already holds these weights packed by an earlier call of this entry point (acting steps
+ *           between updates); on a block this entry point did not pack: MIRL_ERR_STATE.  Any other bit is
+ *           MIRL_ERR_ARG, with neither y nor wpk touched.
+ * An output's summation order does not depend on N or on the launch shape.
+ * mirl_conv1p_u8_supported() (host logic only): F = 32, K = 8, S = 4, H >= 8, W >= 8, W % 4 == 0, H*W % 16 == 0 and
+ * one frame staged as bf16 within 64 KiB of LDS.  Anything else, a null or misaligned (16 B) pointer and N <= 0
+ * return MIRL_ERR_ARG before anything is launched.                                                              */
+int mirl_conv1p_u8_supported(int32_t H, int32_t W, int32_t F, int32_t K, int32_t S);
+int mirl_conv1p_u8_wpk_floats(int64_t* out);
+int mirl_conv1p_u8_fwd(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* weight,
+                       int64_t ws_o, int64_t ws_h, int64_t ws_w, const float* bias, float scale,
+                       float* wpk, float* y, int32_t flags, void* stream);
+/* Weight gradient of that layer from the same uint8 frames:
+ *   dw[f][0][kh][kw] = scale * sum over (n, oh, ow) of g[n][oh][ow][f] * float(x[n][0][4 oh + kh][4 ow + kw])
+ *   g        float [N][OH][OW][32], the gradient w.r.t. the conv output AFTER the ReLU mask, NHWC like y
+ *   dw       float, logical [32][1][8][8] written with element strides ws_o, ws_h, ws_w
+ *   scratch  *out of mirl_conv1p_u8_wrw_scratch_floats() floats (per-workgroup partial slabs, summed in a fixed
+ *            order by a second kernel: fixed partition, no float atomics, bit-identical reruns)
+ * The masked form takes dy, the gradient w.r.t. the layer's OUTPUT, applies y > 0 while it is loaded and writes the
+ * bias gradient db[32] (the masked gradient's column sums) from the same pass.                                   */
+int mirl_conv1p_u8_wrw_scratch_floats(int64_t* out);
+int mirl_conv1p_u8_wrw(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* g, float scale,
+                       float* scratch, float* dw, int64_t ws_o, int64_t ws_h, int64_t ws_w, void* stream);
+int mirl_conv1p_u8_wrw_masked(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* dy, const float* y,
+                              float scale, float* scratch, float* dw, int64_t ws_o, int64_t ws_h, int64_t ws_w,
+                              float* db, void* stream);
+
 /* ---- data gradient of the second conv layer (csrc/conv_mid.hip).  For the backward
  * autograd derives for `F.relu(conv(x))` (rltime/models/torch/modules/cnn.py:47-49) at
  * Conv2d(32 -> 64, kernel 4, stride 2) (configs/models/cnn_*.json), input IH x IW =

@@ -13,7 +13,8 @@ weight concatenations, rand / randint, fills).  Here one step is
                                                episode statistics, RNG step
     mirl_replay_ingest        1 copy + 1 launch  frames + state + scalars + plan + tree, straight
                                                from the static buffers (no clones)
-    mirl_conv1_u8_fwd         2 launches       input layer from the env's uint8 frames
+    mirl_conv1_u8_fwd         2 launches       input layer from the env's uint8 frames (mirl_conv1p_u8_fwd for
+                                               one-plane observations)
     network                   6 launches       csrc/actnet.hip: conv 2, conv 3 (bias + ReLU in the epilogue, layer 3
                                                writes the LSTM product's input rows), [features | h] x [W_ih | W_hh]^T
                                                with the cell in the same launch, quantile embedding x features, hidden
@@ -169,7 +170,7 @@ class FastActingStep:
         k, s = c1.kernel_size[0], c1.stride[0]
         self.y1 = torch.empty((E, c1.out_channels, (hh - k) // s + 1, (ww - k) // s + 1), memory_format=torch.channels_last, **f32)
         need = C.c_int64()
-        check(lib.mirl_conv1_u8_wpk_floats(C.byref(need)))
+        check((lib.mirl_conv1p_u8_wpk_floats if obs0.shape[1] == 1 else lib.mirl_conv1_u8_wpk_floats)(C.byref(need)))
         self.wpk = torch.empty(need.value, **f32)
         self.xh = torch.zeros((E, K), **f32)                     # [conv features (NCHW order) | extras | zeros | masked h]
         self.extra = torch.zeros((E, X), **f32) if X else None   # the compact rows the replay ingests as `extra`
@@ -362,6 +363,11 @@ class FastActingStep:
         """packed=True: self.wpk still holds the current weights (packed by the call's re-selection)."""
         c1 = self.cnn.layers[0]
         so, sc, sh, sw = c1.weight.stride()
+        if obs.shape[1] == 1:                                     # one-plane frames: csrc/conv_in1p.hip
+            check(lib.mirl_conv1p_u8_fwd(obs.shape[0], obs.shape[2], obs.shape[3], ptr(obs), ptr(c1.weight), so, sh, sw, ptr(c1.bias),
+                                         float(self.cnn.scale), ptr(self.wpk), ptr(self.y1), 8 if packed else 0, stream()),
+                  "mirl_conv1p_u8_fwd")
+            return
         check(lib.mirl_conv1_u8_fwd_ex(obs.shape[0], obs.shape[2], obs.shape[3], ptr(obs), ptr(c1.weight), so, sc, sh, sw, ptr(c1.bias),
                                        float(self.cnn.scale), ptr(self.wpk), ptr(self.y1), 8 if packed else 0, stream()),
               "mirl_conv1_u8_fwd")

@@ -15,7 +15,8 @@ expressions; parity tests in tests/test_fused_gpu.py compare against those):
                      straight from the replay's uint8 frames on the f32 MFMA pipe
                      (csrc/conv_in.hip): no converted copy of the frames, no separate
                      bias / ReLU pass; backward = the weight gradient from the same uint8
-                     frames, ReLU mask and bias gradient in that kernel
+                     frames, ReLU mask and bias gradient in that kernel.  One-plane frames
+                     (N, 1, H, W) take the second kernel family, csrc/conv_in1p.hip
   cos_embed          IQN cosine features (iqn.py:78-81) in one kernel
   quantile_product   x[m] * relu(phi @ Wq^T + bq)[m, n] (iqn.py:82-102) with a
                      backward that never materialises g*x / g*emb / the mask
@@ -333,6 +334,8 @@ def conv_u8_supported(x, conv):
             and conv.kernel_size[0] == conv.kernel_size[1] and conv.stride[0] == conv.stride[1]
             and conv.in_channels == x.shape[1] and not torch.is_autocast_enabled()):
         return False
+    if x.shape[1] == 1:                       # one-plane frames: the second kernel family (csrc/conv_in1p.hip)
+        return bool(_lib().lib.mirl_conv1p_u8_supported(x.shape[2], x.shape[3], conv.out_channels, conv.kernel_size[0], conv.stride[0]))
     return bool(_lib().lib.mirl_conv1_u8_supported(x.shape[1], x.shape[2], x.shape[3], conv.out_channels,
                                                    conv.kernel_size[0], conv.stride[0]))
 
@@ -383,8 +386,56 @@ class _ConvU8BiasReLU(torch.autograd.Function):
         return None, dw, (db if ctx.needs_input_grad[2] else None), None, None
 
 
+class _ConvU8P1BiasReLU(torch.autograd.Function):
+    """_ConvU8BiasReLU for one-plane frames (csrc/conv_in1p.hip): a (F, 1, k, k) weight has no channel stride to pass."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, scale, stride):
+        L = _lib()
+        n, _, h, w = x.shape
+        f, k = weight.shape[0], weight.shape[2]
+        oh, ow = (h - k) // stride + 1, (w - k) // stride + 1
+        y = torch.empty((n, f, oh, ow), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        if n:
+            wpk = torch.empty(_scratch_floats("mirl_conv1p_u8_wpk_floats"), dtype=torch.float32, device=x.device)
+            so, _, sh, sw = weight.stride()
+            b = bias if bias.data_ptr() % 16 == 0 else bias.clone()
+            L.check(L.lib.mirl_conv1p_u8_fwd(n, h, w, L.ptr(x), L.ptr(weight), so, sh, sw, L.ptr(b), float(scale), L.ptr(wpk), L.ptr(y), 0,
+                                             L.stream()), "mirl_conv1p_u8_fwd")
+        ctx.scale = scale
+        ctx.save_for_backward(x, weight, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, weight, y = ctx.saved_tensors
+        grad = grad.contiguous(memory_format=torch.channels_last)
+        if not (ctx.needs_input_grad[1] and x.shape[0]):
+            _, db = relu_bwd_bias_rows(grad, y, y.shape[1])
+            dw = torch.zeros_like(weight) if ctx.needs_input_grad[1] else None
+            return None, dw, (db if ctx.needs_input_grad[2] else None), None, None
+        L = _lib()
+        n, _, h, w = x.shape
+        scratch = torch.empty(_scratch_floats("mirl_conv1p_u8_wrw_scratch_floats"), dtype=torch.float32, device=x.device)
+        dw = torch.empty_like(weight)
+        so, _, sh, sw = dw.stride()
+        if grad.data_ptr() % 16 == 0:
+            # ReLU mask and bias gradient inside the weight-gradient kernel: one pass over dy, y and the uint8 frames
+            db = torch.empty(weight.shape[0], dtype=torch.float32, device=x.device)
+            L.check(L.lib.mirl_conv1p_u8_wrw_masked(n, h, w, L.ptr(x), L.ptr(grad), L.ptr(y), float(ctx.scale), L.ptr(scratch), L.ptr(dw), so, sh, sw,
+                                                    L.ptr(db), L.stream()), "mirl_conv1p_u8_wrw_masked")
+        else:
+            # an upstream gradient off the 16-byte grid: the mask + bias-gradient pass leaves an aligned masked gradient
+            g, db = relu_bwd_bias_rows(grad, y, y.shape[1])
+            L.check(L.lib.mirl_conv1p_u8_wrw(n, h, w, L.ptr(x), L.ptr(g), float(ctx.scale), L.ptr(scratch), L.ptr(dw), so, sh, sw,
+                                             L.stream()), "mirl_conv1p_u8_wrw")
+        return None, dw, (db if ctx.needs_input_grad[2] else None), None, None
+
+
 def conv_u8_bias_relu(x, conv, scale):
     """relu(conv(x * scale)) for uint8 NCHW x; the caller checked conv_u8_supported(x, conv)."""
+    if x.shape[1] == 1:
+        return _ConvU8P1BiasReLU.apply(x, conv.weight, conv.bias, float(scale), int(conv.stride[0]))
     return _ConvU8BiasReLU.apply(x, conv.weight, conv.bias, float(scale), int(conv.stride[0]))
 
 
