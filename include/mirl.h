@@ -428,6 +428,31 @@ int mirl_lstm_cell_bwd(int32_t B, int32_t H, float* gates, const float* c_t, con
                        const float* d_out, const float* dh_rec, float* dc_rec, const float* keep_next,
                        int32_t first, void* stream);
 
+/* ---- the extra-feature columns of the LSTM's input projection (csrc/lstm_extras.hip).
+ * The reference concatenates X extra floats per row (last action one-hot, timestep, last reward)
+ * to the conv features in front of the LSTM (rltime/models/torch/sequential.py:155-166); here
+ *   [f | e] W_ih^T = f W_ih[:, :F]^T + e W_ih[:, F:]^T
+ * and the second term is added to the K = F product by a store-bound pass:
+ *   dst[r][n] = src[r][n] + sum_{x < X} e[r][x] * wx[n][x]        r < M, n < N
+ * in f32, the accumulator starting at src[r][n] and x ascending, every product and every sum
+ * rounded (no fused multiply-add).  dst == src (in place) is allowed; otherwise src is only read.
+ * src / dst: 16-byte aligned, leading dimensions (floats) >= N and multiples of 4.  e [M][lde],
+ * lde >= X, and wx [N][ldwx] (the view W_ih[:, F:], ldwx = F + X) need no alignment.
+ * mirl_lstm_extras_supported: M >= 1, N >= 4, N % 4 == 0, 1 <= X <= 32 (host logic); the
+ * launchers answer MIRL_ERR_ARG for everything else.                                           */
+int mirl_lstm_extras_supported(int64_t M, int64_t N, int32_t X);
+int mirl_lstm_extras_add(int64_t M, int64_t N, int32_t X, const float* src, int64_t ldsrc, const float* e, int64_t lde,
+                         const float* wx, int64_t ldwx, float* dst, int64_t lddst, void* stream);
+/* The gradient of those weight columns: dwx[n][x] = sum_{r < M} g[r][n] * e[r][x] into a
+ * contiguous [N][X] block, from ONE read of g [M][ldg] (16-byte aligned, ldg % 4 == 0).  Rows are
+ * summed in chunks of 256 (four runs of 64 ascending rows, joined in a fixed order); with more
+ * than one chunk the per-chunk partials go to the workspace (mirl_lstm_extras_wgrad_workspace_bytes,
+ * 0 for M <= 256) and a second launch adds them in ascending order: no atomics, two calls on the
+ * same operands give the same bits.                                                             */
+int mirl_lstm_extras_wgrad_workspace_bytes(int64_t M, int64_t N, int32_t X, int64_t* bytes);
+int mirl_lstm_extras_wgrad(int64_t M, int64_t N, int32_t X, const float* g, int64_t ldg, const float* e, int64_t lde,
+                           float* dwx, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* The CNN's input conversion (rltime/models/torch/modules/cnn.py:44-45,
  * `x.float() * scale`) fused with the NCHW -> NHWC layout change: src uint8
  * [N][C][HW] -> dst float32 [N][HW][C] = src * scale, one pass.                  */

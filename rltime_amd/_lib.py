@@ -165,6 +165,10 @@ _SIGNATURES = {
     "mirl_lstm_seq_bwd_workspace_bytes": [_i32, _i32, _P(_i64)],
     "mirl_lstm_seq_bwd": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mirl_lstm_cell_bwd": [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
+    "mirl_lstm_extras_supported": [_i64, _i64, _i32],
+    "mirl_lstm_extras_add": [_i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
+    "mirl_lstm_extras_wgrad_workspace_bytes": [_i64, _i64, _i32, _P(_i64)],
+    "mirl_lstm_extras_wgrad": [_i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp],
     "mirl_frames_to_f32_nhwc": [_i64, _i32, _i32, _vp, C.c_float, _vp, _vp],
     "mirl_frames_to_f32_nhwc_ex": [_i64, _i32, _i32, _vp, C.c_float, _vp, _i32, _i32, _vp],
     "mirl_conv1_u8_supported": [_i32, _i32, _i32, _i32, _i32, _i32],

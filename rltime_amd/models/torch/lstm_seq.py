@@ -139,9 +139,79 @@ def _backward_sweep(gates, c_all, cm, d_out, keep, w):
             torch.mm(gates[t], w, out=dh_rec)
 
 
+def extras_supported(M, N, X):
+    """Does csrc/lstm_extras.hip take an (M, N) gates block with X extra features per row?"""
+    return bool(lib.mirl_lstm_extras_supported(M, N, X))
+
+
+def _row_view(t):
+    """(M, N) float32 -> itself when the extras kernels take its rows as stored (16-byte aligned, row stride a multiple
+    of 4), else a contiguous copy."""
+    t = t.float()
+    if t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0:
+        return t
+    return t.contiguous()
+
+
+def _compact(extra):
+    extra = extra.float()
+    return extra if extra.stride(1) == 1 and extra.stride(0) >= extra.shape[1] else extra.contiguous()
+
+
+def extras_add(src, extra, w_x, out=None):
+    """src (M, N) + extra (M, X) @ w_x (N, X)^T  (csrc/lstm_extras.hip: the extra-feature columns of the input
+    projection, f32 in a fixed order).  out=None: a fresh buffer, src untouched; out=src: in place.  w_x is the
+    strided view W_ih[:, F:] as stored."""
+    M, N = src.shape
+    X = extra.shape[1]
+    extra = _compact(extra)
+    w_x = w_x.float()
+    if w_x.stride(1) != 1:
+        w_x = w_x.contiguous()
+    if out is None:
+        src = _row_view(src)
+        out = torch.empty((M, N), dtype=torch.float32, device=src.device)
+    check(lib.mirl_lstm_extras_add(M, N, X, ptr(src), src.stride(0), ptr(extra), extra.stride(0), ptr(w_x), w_x.stride(0),
+                                   ptr(out), out.stride(0), stream()), "mirl_lstm_extras_add")
+    return out
+
+
+def extras_wgrad(g, extra):
+    """g (M, N)^T @ extra (M, X) -> (N, X): the gradient of W_ih[:, F:], deterministic (no atomics)."""
+    g = _row_view(g)
+    extra = _compact(extra)
+    M, N = g.shape
+    X = extra.shape[1]
+    need = C.c_int64()
+    check(lib.mirl_lstm_extras_wgrad_workspace_bytes(M, N, X, C.byref(need)), "mirl_lstm_extras_wgrad_workspace_bytes")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=g.device) if need.value else None
+    out = torch.empty((N, X), dtype=torch.float32, device=g.device)
+    check(lib.mirl_lstm_extras_wgrad(M, N, X, ptr(g), g.stride(0), ptr(extra), extra.stride(0), ptr(out), ptr(ws), need.value,
+                                     stream()), "mirl_lstm_extras_wgrad")
+    return out
+
+
+class _ExtrasAdd(torch.autograd.Function):
+    """proj + extra @ w_x^T out of place, for a projection formed outside the sequence op (LSTM.project_input)."""
+
+    @staticmethod
+    def forward(ctx, proj, extra, w_x):
+        ctx.save_for_backward(extra)
+        return extras_add(proj, extra, w_x)
+
+    @staticmethod
+    def backward(ctx, g):
+        extra, = ctx.saved_tensors
+        return g, None, (extras_wgrad(g, extra) if ctx.needs_input_grad[2] else None)
+
+
+def add_extras(proj, extra, w_x):
+    return _ExtrasAdd.apply(proj, extra, w_x)
+
+
 class _LSTMSequence(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w_ih, w_hh, bias, h0, c0, keep, track=True):
+    def forward(ctx, x, w_ih, w_hh, bias, h0, c0, keep, track=True, extra=None, w_x=None):
         # x (T*B, I); bias = b_ih + b_hh (4H); keep (T, B).  The input projection of
         # ALL timesteps is one GEMM into `gates`; every step then accumulates the
         # recurrent GEMM onto its slice IN PLACE (no per-step copy of the projection)
@@ -153,19 +223,25 @@ class _LSTMSequence(torch.autograd.Function):
         keep = keep.float().contiguous()
         # `track`: decided by the caller from torch.is_grad_enabled() — inside forward() grad mode is
         # always off and ctx.needs_input_grad mirrors requires_grad even in a no_grad pass
-        need_grad = track and any(ctx.needs_input_grad[:4])
+        need_grad = track and (any(ctx.needs_input_grad[:4]) or ctx.needs_input_grad[9])
         dev = x.device
-        gates = gemm3.linear_fwd(x, w_ih.float(), bias.float().contiguous()).view(T, B, 4 * H)
+        # with extras: x holds the F feature columns only and w_ih = W_ih[:, :F]; the X extra columns are added to the
+        # K = F product in place (csrc/lstm_extras.hip) — the (T*B, F + X) block is never formed
+        gates = gemm3.linear_fwd(x, w_ih.float(), bias.float().contiguous())
+        if extra is not None:
+            extra = _compact(extra)
+            extras_add(gates, extra, w_x, out=gates)
+        gates = gates.view(T, B, 4 * H)
         out, hm, cm, c_all, h_last, c_last = _forward_sweep(
             gates, w, h0.float().contiguous(), c0.float().contiguous(), keep, need_grad)
         if need_grad:
-            ctx.save_for_backward(x, w_ih, gates, c_all, cm, hm, keep, w)
+            ctx.save_for_backward(x, w_ih, gates, c_all, cm, hm, keep, w, extra)
         ctx.mark_non_differentiable(h_last, c_last)
         return out, h_last, c_last
 
     @staticmethod
     def backward(ctx, d_out, _dh, _dc):
-        x, w_ih, gates, c_all, cm, hm, keep, w = ctx.saved_tensors
+        x, w_ih, gates, c_all, cm, hm, keep, w, extra = ctx.saved_tensors
         T, B, G = gates.shape
         H = G // 4
         d_out = d_out.float().contiguous()
@@ -175,49 +251,57 @@ class _LSTMSequence(torch.autograd.Function):
         d_wih = gemm3.grad_weight(dg, x) if ctx.needs_input_grad[1] else None
         d_whh = gemm3.grad_weight(dg, hm[:T].reshape(T * B, H)) if ctx.needs_input_grad[2] else None
         d_b = dg.sum(0) if ctx.needs_input_grad[3] else None
-        return d_x, d_wih, d_whh, d_b, None, None, None, None
+        d_wx = extras_wgrad(dg, extra) if extra is not None and ctx.needs_input_grad[9] else None
+        return d_x, d_wih, d_whh, d_b, None, None, None, None, None, d_wx
 
 
 class _LSTMSequenceFromProjection(torch.autograd.Function):
     """The same recurrence on an input projection computed elsewhere (gx (T, B, 4H) =
     x W_ih^T + b_ih + b_hh, possibly a slice of a larger shared block): gx is left
-    untouched (it may have other consumers), so the gates buffer is a copy of it."""
+    untouched (it may have other consumers), so the gates buffer is a copy of it.  With extras (extra (T*B, X),
+    w_x = W_ih[:, F:]) gx is the projection of the feature columns alone and the copy is gx + extra w_x^T, made by
+    one out-of-place pass (csrc/lstm_extras.hip) that takes the place of the clone."""
 
     @staticmethod
-    def forward(ctx, gx, w_hh, h0, c0, keep, track=True):
+    def forward(ctx, gx, w_hh, h0, c0, keep, track=True, extra=None, w_x=None):
         T, B, G = gx.shape
         H = G // 4
         w = w_hh.float().contiguous()
         keep = keep.float().contiguous()
-        need_grad = track and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        need_grad = track and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[7])
         dev = gx.device
-        if need_grad or not (persistent_supported(T, B, H) and w.data_ptr() % 16 == 0):
+        if extra is not None:
+            extra = _compact(extra)
+            gates = extras_add(gx.reshape(T * B, G), extra, w_x).view(T, B, G)      # a fresh buffer: gx stays as it is
+        elif need_grad or not (persistent_supported(T, B, H) and w.data_ptr() % 16 == 0):
             gates = gx.float().clone(memory_format=torch.contiguous_format)
         else:
             gates = gx.float().contiguous()       # the persistent no-grad sweep only READS the projection: no copy
         out, hm, cm, c_all, h_last, c_last = _forward_sweep(
             gates, w, h0.float().contiguous(), c0.float().contiguous(), keep, need_grad)
         if need_grad:
-            ctx.save_for_backward(gates, c_all, cm, hm, keep, w)
+            ctx.save_for_backward(gates, c_all, cm, hm, keep, w, extra)
         ctx.mark_non_differentiable(h_last, c_last)
         return out, h_last, c_last
 
     @staticmethod
     def backward(ctx, d_out, _dh, _dc):
-        gates, c_all, cm, hm, keep, w = ctx.saved_tensors
+        gates, c_all, cm, hm, keep, w, extra = ctx.saved_tensors
         T, B, G = gates.shape
         H = G // 4
         d_out = d_out.float().contiguous()
         _backward_sweep(gates, c_all, cm, d_out, keep, w)
         d_whh = gemm3.grad_weight(gates.reshape(T * B, G), hm[:T].reshape(T * B, H)) if ctx.needs_input_grad[1] else None
-        return gates, d_whh, None, None, None, None
+        d_wx = extras_wgrad(gates.reshape(T * B, G), extra) if extra is not None and ctx.needs_input_grad[7] else None
+        return gates, d_whh, None, None, None, None, None, d_wx
 
 
-def lstm_sequence_from_projection(gx, w_hh, h0, c0, keep):
-    """gx (T, B, 4H) -> (out (T,B,H), h_T, c_T)."""
-    return _LSTMSequenceFromProjection.apply(gx, w_hh, h0, c0, keep, torch.is_grad_enabled())
+def lstm_sequence_from_projection(gx, w_hh, h0, c0, keep, extra=None, w_x=None):
+    """gx (T, B, 4H) -> (out (T,B,H), h_T, c_T); with extra (T*B, X) and w_x (4H, X): gx + extra w_x^T."""
+    return _LSTMSequenceFromProjection.apply(gx, w_hh, h0, c0, keep, torch.is_grad_enabled(), extra, w_x)
 
 
-def lstm_sequence(x, w_ih, w_hh, bias, h0, c0, keep):
-    """x (T*B, I) -> (out (T,B,H), h_T (B,H), c_T (B,H)); keep (T, B) = 1 - initials."""
-    return _LSTMSequence.apply(x, w_ih, w_hh, bias, h0, c0, keep, torch.is_grad_enabled())
+def lstm_sequence(x, w_ih, w_hh, bias, h0, c0, keep, extra=None, w_x=None):
+    """x (T*B, I) -> (out (T,B,H), h_T (B,H), c_T (B,H)); keep (T, B) = 1 - initials.  With extra (T*B, X) and
+    w_x (4H, X): x and w_ih are the feature columns and the projection is x w_ih^T + extra w_x^T."""
+    return _LSTMSequence.apply(x, w_ih, w_hh, bias, h0, c0, keep, torch.is_grad_enabled(), extra, w_x)

@@ -153,62 +153,103 @@ class LSTM(BaseModule):
         self.fused = True          # use the fused HIP sequence op on the GPU
         # NHWC conv output consumed in memory order with permuted W_ih columns instead of a transposing copy (_flat_input)
         self.nhwc_input = True
+        # extra features handed over beside the feature rows (forward(extra=...)) enter as a rank-X correction of the
+        # K = F projection (csrc/lstm_extras.hip) instead of through a concatenated (rows, F + X) block
+        self.split_extras = True
         self._w_ih_nhwc = None     # (key, permuted W_ih) of the last no-grad pass
         init_weight(self.lstm_cell.weight_hh)
         init_weight(self.lstm_cell.weight_ih)
 
-    def _flat_input(self, x):
+    def takes_extra(self, x, extra):
+        """Will forward(x, ..., extra=extra) add the extras to the K = F projection (csrc/lstm_extras.hip) instead of
+        concatenating them?  x: the F = inp_size - X features of every row, in any shape; extra (rows, X)."""
+        if not (extra is not None and self.fused and self.split_extras and isinstance(x, torch.Tensor) and x.is_cuda
+                and extra.is_cuda and extra.dim() == 2 and x.dim() >= 2 and x.shape[0] == extra.shape[0]
+                and 0 < extra.shape[1] < self.inp_size
+                and int(np.prod(x.shape[1:])) + extra.shape[1] == self.inp_size):
+            return False
+        from .lstm_seq import extras_supported
+        return extras_supported(x.shape[0], 4 * self.num_units, extra.shape[1])
+
+    def _flat_input(self, x, n_extra=0):
         """The layer's input rows and the input weights to multiply them with.  The reference flattens the conv stack's
         (C, H, W) output (lstm.py:60-66: x.view(-1, inp_size)); for an NHWC (channels_last) activation that is a
         transposing copy of the whole block (62 464 x 3136 floats = 0.8 GB per pass at config D).  The rows are taken in
         MEMORY order instead — a view — and the columns of W_ih are permuted to match (a 26 MB copy that autograd undoes
-        for the weight gradient): the same products, summed in another column order."""
+        for the weight gradient): the same products, summed in another column order.
+        n_extra = X > 0: the rows hold the F = inp_size - X feature columns only and are paired with W_ih[:, :F] (the
+        same permutation for NHWC rows, a contiguous copy for flat ones); the X extra columns are added separately."""
         w = self.lstm_cell.weight_ih
+        feat = self.inp_size - n_extra
         if (x.dim() == 4 and x.is_cuda and self.nhwc_input and not x.is_contiguous()
-                and x.is_contiguous(memory_format=torch.channels_last) and x.shape[1] * x.shape[2] * x.shape[3] == self.inp_size):
+                and x.is_contiguous(memory_format=torch.channels_last) and x.shape[1] * x.shape[2] * x.shape[3] == feat):
             n, c, h, wd = x.shape
             rows = x.permute(0, 2, 3, 1).reshape(n, h * wd * c)
             if torch.is_grad_enabled() and w.requires_grad:
                 # the pass the weight gradient flows through: autograd undoes the permutation (once per learner step)
-                return rows, w.view(-1, c, h, wd).permute(0, 2, 3, 1).reshape(-1, h * wd * c)
+                return rows, w[:, :feat].unflatten(1, (c, h, wd)).permute(0, 2, 3, 1).reshape(-1, h * wd * c)
             # no-grad passes (target net, double-Q selection, burn-in, acting): the permuted copy is a pure function of
             # the weights — kept per (storage address, version counter), rebuilt after an optimizer step / weight copy
             key = (w.data_ptr(), w._version, c, h, wd)
             from . import gemm3
             if self._w_ih_nhwc is None or self._w_ih_nhwc[0] != key or gemm3.REFRESH_ALWAYS:
                 with torch.no_grad():
-                    src = w.detach().view(-1, c, h, wd).permute(0, 2, 3, 1)
+                    src = w.detach()[:, :feat].unflatten(1, (c, h, wd)).permute(0, 2, 3, 1)
                     if self._w_ih_nhwc is not None and self._w_ih_nhwc[1].shape == (w.shape[0], h * wd * c):
                         self._w_ih_nhwc[1].view(-1, h, wd, c).copy_(src)          # in place: captured graphs keep reading this buffer
                         self._w_ih_nhwc = (key, self._w_ih_nhwc[1])
                     else:
                         self._w_ih_nhwc = (key, src.reshape(-1, h * wd * c).contiguous())
             return rows, self._w_ih_nhwc[1]
+        if n_extra:
+            return x.reshape(-1, feat), w[:, :feat].contiguous()
         return x.reshape(-1, self.inp_size), w
 
-    def project_input(self, x):
+    def project_input(self, x, extra=None):
         """x W_ih^T + b_ih + b_hh for every row of x: the part of the sequence forward
         that does not depend on the recurrent state.  A caller that runs this layer
         over overlapping row ranges of one block (the online net's training pass and
         its double-Q selection pass, MultiStepTrainer._share_online_features) computes
-        it once and hands each pass its rows through forward(projected=...)."""
+        it once and hands each pass its rows through forward(projected=...).
+        Rows that hold only the F = inp_size - X feature columns give the projection of those columns alone
+        (forward(projected=..., extra=...) adds each pass's own extras); with `extra` they are added here."""
         cell = self.lstm_cell
         from .gemm3 import linear as linear3
-        rows, w_ih = self._flat_input(x)
-        return linear3(rows, w_ih, cell.bias_ih + cell.bias_hh)
+        n_extra = self.inp_size - int(np.prod(x.shape[1:])) if x.dim() >= 2 else 0
+        if extra is not None and not self.takes_extra(x, extra):
+            x, n_extra = torch.cat([x.reshape(x.shape[0], -1), extra], dim=-1), 0
+            extra = None
+        assert 0 <= n_extra < self.inp_size and (extra is None or extra.shape[1] == n_extra)
+        rows, w_ih = self._flat_input(x, n_extra)
+        proj = linear3(rows, w_ih, cell.bias_ih + cell.bias_hh)
+        if extra is not None:
+            from .lstm_seq import add_extras
+            proj = add_extras(proj, extra, cell.weight_ih[:, self.inp_size - n_extra:])
+        return proj
 
-    def forward(self, x, hx, cx, initials, timesteps, projected=None):
+    def forward(self, x, hx, cx, initials, timesteps, projected=None, extra=None):
         if projected is not None and projected.is_cuda and self.fused and projected.shape[0] == hx.shape[0]:
             from .lstm_seq import lstm_sequence_from_projection
             batch = projected.shape[0] // timesteps
             h0 = hx.reshape(timesteps, batch, self.num_units)[0]
             c0 = cx.reshape(timesteps, batch, self.num_units)[0]
+            w_x = None
+            if extra is not None:
+                # `projected` covers the feature columns alone: this pass's own extras are added while the gates buffer is made
+                assert extra.shape[0] == projected.shape[0] and self.split_extras
+                w_x = self.lstm_cell.weight_ih[:, self.inp_size - extra.shape[1]:]
             out, h_last, c_last = lstm_sequence_from_projection(
                 projected.reshape(timesteps, batch, -1), self.lstm_cell.weight_hh, h0, c0,
-                (1 - initials).reshape(timesteps, batch))
+                (1 - initials).reshape(timesteps, batch), extra, w_x)
             self.last_state = (h_last.detach(), c_last.detach())
             return out.reshape(timesteps * batch, self.num_units)
-        x, w_ih = self._flat_input(x)
+        n_extra = 0
+        if extra is not None:
+            if x.shape[0] == hx.shape[0] and self.takes_extra(x, extra):
+                n_extra = extra.shape[1]
+            else:                              # CPU, X > 32, multi-sample batches: the reference's concatenation
+                x, extra = torch.cat([x.reshape(x.shape[0], -1), extra], dim=-1), None
+        x, w_ih = self._flat_input(x, n_extra)
         assert hx.shape[1] == self.num_units and cx.shape[1] == self.num_units
         assert x.shape[0] % hx.shape[0] == 0
         multi = x.shape[0] // hx.shape[0]
@@ -223,10 +264,12 @@ class LSTM(BaseModule):
         if x.is_cuda and multi == 1 and self.fused:
             # MI355X path: one GEMM + one fused HIP kernel per step (lstm_seq.py)
             from .lstm_seq import lstm_sequence
+            w_x = cell.weight_ih[:, self.inp_size - n_extra:] if n_extra else None
             out, h_last, c_last = lstm_sequence(x, w_ih, cell.weight_hh, cell.bias_ih + cell.bias_hh,
-                                                hx, cx, (1 - initials).reshape(timesteps, batch))
+                                                hx, cx, (1 - initials).reshape(timesteps, batch), extra, w_x)
             self.last_state = (h_last.detach(), c_last.detach())
             return out.reshape(timesteps * batch, self.num_units)
+        assert not n_extra
         keep = (1 - initials).reshape(timesteps, batch, 1)
         # one GEMM for the input projection of every timestep
         gx = F.linear(x, w_ih, cell.bias_ih).reshape(timesteps, batch, -1)

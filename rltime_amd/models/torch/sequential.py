@@ -123,11 +123,20 @@ class SequentialModel(nn.Module):
         assert (extra is None) == (self.extra_input_layer is None)
         result = {"layer_inputs": []}
         for i, layer in enumerate(self.layers):
+            layer_extra = {}
             if i == self.extra_input_layer:
-                if x.shape[0] != extra.shape[0]:     # multi-sample batch (sequential.py:155-159)
-                    assert x.shape[0] % extra.shape[0] == 0
-                    extra = extra.repeat_interleave(x.shape[0] // extra.shape[0], dim=0)
-                x = torch.cat([x.reshape(x.shape[0], -1), extra], dim=-1)
+                # A layer that takes the extras beside its rows (LSTM.takes_extra: the X columns are added to its K = F
+                # projection, csrc/lstm_extras.hip) gets them as they are — no (rows, F + X) block is formed.  Not with a
+                # pre-processor on the layer (it works on the concatenated input) and not for the last layer, whose
+                # recorded input is the only "layer_inputs" entry with a consumer (the dueling head, policies/dqn.py).
+                if i not in self.layer_pre_processors and i != len(self.layers) - 1 and hasattr(layer, "takes_extra") \
+                        and layer.takes_extra(x, extra):
+                    layer_extra = {"extra": extra}
+                else:
+                    if x.shape[0] != extra.shape[0]:     # multi-sample batch (sequential.py:155-159)
+                        assert x.shape[0] % extra.shape[0] == 0
+                        extra = extra.repeat_interleave(x.shape[0] // extra.shape[0], dim=0)
+                    x = torch.cat([x.reshape(x.shape[0], -1), extra], dim=-1)
             if i in self.layer_pre_processors:
                 x, more = self.layer_pre_processors[i](x)
                 result.update(more)
@@ -136,13 +145,14 @@ class SequentialModel(nn.Module):
                 break
             if i == 0 and first_out is not None:
                 x = first_out
-            elif i == 1 and projected is not None and first_out is not None and i != self.extra_input_layer \
+            elif i == 1 and projected is not None and first_out is not None and (i != self.extra_input_layer or layer_extra) \
                     and i not in self.layer_pre_processors and hasattr(layer, "project_input"):
-                x = layer(x, timesteps=timesteps, projected=projected, **inp.get("layer%d_state" % i, {}))
+                # with extras at this layer the shared projection covers the feature columns; the pass adds its own extras
+                x = layer(x, timesteps=timesteps, projected=projected, **layer_extra, **inp.get("layer%d_state" % i, {}))
             elif i == 0 and prepared is not None and self.extra_input_layer != 0 and 0 not in self.layer_pre_processors:
                 x = layer(prepared, timesteps=timesteps, prepared=True, **inp.get("layer0_state", {}))
             else:
-                x = layer(x, timesteps=timesteps, **inp.get("layer%d_state" % i, {}))
+                x = layer(x, timesteps=timesteps, **layer_extra, **inp.get("layer%d_state" % i, {}))
             if stop_after is not None and i == stop_after:
                 break
         result["output"] = x

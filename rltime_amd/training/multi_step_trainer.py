@@ -488,8 +488,15 @@ class MultiStepTrainer(PolicyTrainer):
         # (x W_ih^T + b, 40 960 x 3136 x 2048 at config D: a 4 ms GEMM) is also a pure
         # function of these rows — compute it once over the union as well
         layer1 = model.layers[1]
+        hoist = model.extra_input_layer != 1
+        if not hoist and hasattr(layer1, "takes_extra") and len(model.layers) > 2:
+            # extras enter at this layer: the hoisted projection covers the feature columns alone, and each pass adds
+            # its own extras (its own x[1:]) to its slice of it (csrc/lstm_extras.hip) — no union of extras is needed
+            ex = train_data["states"]["x"]
+            hoist = isinstance(ex, (tuple, list)) and layer1.takes_extra(
+                feats[:T * B], torch.cat([v.reshape(T * B, -1) for v in ex[1:]], dim=-1))
         if getattr(self, "share_online_projection", True) and hasattr(layer1, "project_input") \
-                and getattr(layer1, "fused", False) and model.extra_input_layer != 1 and 1 not in model.layer_pre_processors:
+                and getattr(layer1, "fused", False) and hoist and 1 not in model.layer_pre_processors:
             proj = layer1.project_input(feats)
             train_data["states"]["x_projected"] = {id(model): proj[:T * B].reshape(T, B, -1)}
             train_data["target_states"]["x_projected"] = {id(model): proj[shift * B:].detach().reshape(T, B, -1)}
