@@ -42,7 +42,7 @@ import torch
 
 from rltime_amd._lib import lib, check, ptr, stream
 from rltime_amd.general.utils import deep_apply, quiet_gc
-from rltime_amd.models.torch.fused import conv_bias_relu, conv_u8_supported, cos_embed
+from rltime_amd.models.torch.fused import conv_bias_relu, conv_u8_family, conv_u8_supported, cos_embed
 from rltime_amd.models.torch import gemm3
 
 
@@ -169,9 +169,8 @@ class FastActingStep:
         _, hh, ww = obs0.shape[1:]
         k, s = c1.kernel_size[0], c1.stride[0]
         self.y1 = torch.empty((E, c1.out_channels, (hh - k) // s + 1, (ww - k) // s + 1), memory_format=torch.channels_last, **f32)
-        need = C.c_int64()
-        check((lib.mirl_conv1p_u8_wpk_floats if obs0.shape[1] == 1 else lib.mirl_conv1_u8_wpk_floats)(C.byref(need)))
-        self.wpk = torch.empty(need.value, **f32)
+        self.conv1_family = conv_u8_family(obs0.shape[1])        # four-plane or one-plane kernels (csrc/conv_in.hip / conv_in1p.hip)
+        self.wpk = torch.empty(self.conv1_family.wpk_floats(), **f32)
         self.xh = torch.zeros((E, K), **f32)                     # [conv features (NCHW order) | extras | zeros | masked h]
         self.extra = torch.zeros((E, X), **f32) if X else None   # the compact rows the replay ingests as `extra`
         self.c_in = torch.zeros((E, H), **f32)
@@ -361,16 +360,9 @@ class FastActingStep:
 
     def _conv1(self, obs, packed=False):
         """packed=True: self.wpk still holds the current weights (packed by the call's re-selection)."""
-        c1 = self.cnn.layers[0]
-        so, sc, sh, sw = c1.weight.stride()
-        if obs.shape[1] == 1:                                     # one-plane frames: csrc/conv_in1p.hip
-            check(lib.mirl_conv1p_u8_fwd(obs.shape[0], obs.shape[2], obs.shape[3], ptr(obs), ptr(c1.weight), so, sh, sw, ptr(c1.bias),
-                                         float(self.cnn.scale), ptr(self.wpk), ptr(self.y1), 8 if packed else 0, stream()),
-                  "mirl_conv1p_u8_fwd")
-            return
-        check(lib.mirl_conv1_u8_fwd_ex(obs.shape[0], obs.shape[2], obs.shape[3], ptr(obs), ptr(c1.weight), so, sc, sh, sw, ptr(c1.bias),
-                                       float(self.cnn.scale), ptr(self.wpk), ptr(self.y1), 8 if packed else 0, stream()),
-              "mirl_conv1_u8_fwd")
+        c1, fam = self.cnn.layers[0], self.conv1_family
+        fam.call(fam.fwd_packed, obs.shape[0], obs.shape[2], obs.shape[3], ptr(obs), ptr(c1.weight), *fam.strides(c1.weight), ptr(c1.bias),
+                 float(self.cnn.scale), ptr(self.wpk), ptr(self.y1), 8 if packed else 0)
 
     def _body(self):
         """conv 2.. -> LSTM step -> head; reads y1 / xh tail / c_in, writes h, c, actions, qvalues."""

@@ -35,19 +35,16 @@
 //                 16 B stores per lane; a wave writes 2 KiB of contiguous NHWC rows.
 //
 // The layer's input needs no gradient; its weight gradient (k_conv1_u8_wrw, further
-// down in this file) reads the same uint8 frames.  Autograd wiring:
-// rltime_amd/models/torch/fused.py:_ConvU8BiasReLU.
-#include "common.hpp"
-#include "split3.hpp"
+// down in this file) reads the same uint8 frames.  Launch plans and size constants
+// (C1_*): csrc/host_util.hpp; what this family shares with the one-plane one
+// (csrc/conv_in1p.hip) on the device and in the entry points: csrc/conv_u8.hpp.
+// Autograd wiring: rltime_amd/models/torch/fused.py:_ConvU8 through its four-plane family.
+#include "conv_u8.hpp"
 #include <stdlib.h>
-#include <unordered_map>
 
 namespace mirl {
 
-typedef float cv_f4 __attribute__((ext_vector_type(4)));
-
-constexpr int C1_PLANES = 4, C1_K = 8, C1_S = 4, C1_F = 32, C1_TAPS = C1_K * C1_K;
-constexpr int C1_WPK = 2 * C1_TAPS * 64;      // packed weight image: [half][tap][lane]
+constexpr int C1_WPK = 2 * C1_TAPS * 64;      // packed weight image of the f32-pipe kernel: [half][tap][lane]
 constexpr int C1_LD = 7;                      // staging loads in flight per lane (one 84x84 frame = 6.9 x 256 vectors)
 
 // wpk[(m*64 + tap)*64 + lane] = w[f][c][kh][kw] with the MFMA A-operand lane map
@@ -63,8 +60,6 @@ k_conv1_pack_w(const float* __restrict__ w, int64_t so, int64_t sc, int64_t sh, 
   const int f = (i >> 2) * 8 + m * 4 + (i & 3);
   wpk[t] = w[f * so + c * sc + kh * sh + kw * sw] * scale;   // x*scale*w summed as x*(scale*w): one rounding moved
 }
-
-__device__ __forceinline__ float c1_byte(uint32_t v, int b) { return (float)((v >> (8 * b)) & 0xffu); }
 
 // LDS fill of the forward and f32-pipe weight-gradient kernels: `frames` frames x 4 planes from frame n0 on are one
 // contiguous run of 16 B vectors in HBM; only the LDS side has the padded plane pitch.  C1_LD loads in flight per lane.
@@ -136,7 +131,7 @@ __device__ __forceinline__ float c1_byte(uint32_t v, int b) { return (float)((v 
 // one tile: 128 MFMAs on two accumulator chains, then + bias, ReLU, two 16 B stores
 #define C1_TILE_COMPUTE(px_, f_, p_)                                                            \
   {                                                                                             \
-    cv_f4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};                                 \
+    g3_f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};                              \
     float vv_[C1_TAPS];                                                                         \
     /* tap s = kh*8 + kw: word kh*2 + (kw>>2), byte kw&3 */                                     \
     _Pragma("unroll") for (int s = 0; s < C1_TAPS; ++s)                                         \
@@ -147,10 +142,9 @@ __device__ __forceinline__ float c1_byte(uint32_t v, int b) { return (float)((v 
       a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wr1[s], vv_[s], a1, 0, 0, 0);                   \
     }                                                                                           \
     if (p_ < OHW) {                                                                             \
-      cv_f4 o0 = a0 + b0, o1 = a1 + b1;                                                         \
-      o0.x = o0.x > 0.f ? o0.x : 0.f; o0.y = o0.y > 0.f ? o0.y : 0.f; o0.z = o0.z > 0.f ? o0.z : 0.f; o0.w = o0.w > 0.f ? o0.w : 0.f; \
-      o1.x = o1.x > 0.f ? o1.x : 0.f; o1.y = o1.y > 0.f ? o1.y : 0.f; o1.z = o1.z > 0.f ? o1.z : 0.f; o1.w = o1.w > 0.f ? o1.w : 0.f; \
-      cv_f4* dst = reinterpret_cast<cv_f4*>(y + ((n0 + f_) * (int64_t)OHW + p_) * C1_F + kq * 8); \
+      g3_f32x4 o0 = a0 + b0, o1 = a1 + b1;                                                      \
+      o0 = c1_relu(o0); o1 = c1_relu(o1);                                                       \
+      g3_f32x4* dst = reinterpret_cast<g3_f32x4*>(y + ((n0 + f_) * (int64_t)OHW + p_) * C1_F + kq * 8); \
       if (NTS) { __builtin_nontemporal_store(o0, dst); __builtin_nontemporal_store(o1, dst + 1); } \
       else { dst[0] = o0; dst[1] = o1; }                                                        \
     }                                                                                           \
@@ -166,7 +160,7 @@ k_conv1_u8_fwd(int N, int H, int W, int OH, int OW, unsigned ow_magic, int pitch
   float wr0[C1_TAPS], wr1[C1_TAPS];
 #pragma unroll
   for (int s = 0; s < C1_TAPS; ++s) { wr0[s] = wpk[s * 64 + lane]; wr1[s] = wpk[(C1_TAPS + s) * 64 + lane]; }
-  const cv_f4 b0 = *reinterpret_cast<const cv_f4*>(bias + kq * 8), b1 = *reinterpret_cast<const cv_f4*>(bias + kq * 8 + 4);
+  const g3_f32x4 b0 = *reinterpret_cast<const g3_f32x4*>(bias + kq * 8), b1 = *reinterpret_cast<const g3_f32x4*>(bias + kq * 8 + 4);
   const int HW = H * W, OHW = OH * OW, tiles = (OHW + 15) >> 4, hw16 = HW >> 4;
   const int groups = (N + FPI - 1) / FPI, units = groups * split, step = 4 * split;
   bool first = true;
@@ -218,20 +212,11 @@ k_conv1_pack_w3(const float* __restrict__ w, int64_t so, int64_t sc, int64_t sh,
   wpk3[32 * 64 + o] = make_uint4(l0.x, l0.y, l1.x, l1.y);
 }
 
-__device__ __forceinline__ g3_bf16x8 c1_as_bf8(uint4 v) { return __builtin_bit_cast(g3_bf16x8, v); }
-
-// bytes (2e, 2e+1) of v -> two bf16 in one dword
-__device__ __forceinline__ unsigned c1_bytes_bf(uint32_t v, int e) {
-  const float a = (float)((v >> (16 * e)) & 0xffu), b = (float)((v >> (16 * e + 8)) & 0xffu);
-  return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
-}
-
 #define C1B_TILE_COMPUTE(px_, f_, p_)                                                           \
   {                                                                                             \
-    cv_f4 h0 = {0.f, 0.f, 0.f, 0.f}, m0 = h0, l0 = h0, h1 = h0, m1 = h0, l1 = h0;               \
+    g3_f32x4 h0 = {0.f, 0.f, 0.f, 0.f}, m0 = h0, l0 = h0, h1 = h0, m1 = h0, l1 = h0;            \
     _Pragma("unroll") for (int kh = 0; kh < C1_K; ++kh) {                                       \
-      const g3_bf16x8 b_ = c1_as_bf8(make_uint4(c1_bytes_bf(px_[2 * kh], 0), c1_bytes_bf(px_[2 * kh], 1),       \
-                                             c1_bytes_bf(px_[2 * kh + 1], 0), c1_bytes_bf(px_[2 * kh + 1], 1))); \
+      const g3_bf16x8 b_ = c1_row_bf(px_[2 * kh], px_[2 * kh + 1]);                             \
       l0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c1_as_bf8(wlo[kh * 64 + lane]), b_, l0, 0, 0, 0);          \
       l1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c1_as_bf8(wlo[(C1_K + kh) * 64 + lane]), b_, l1, 0, 0, 0); \
       m0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm0[kh], b_, m0, 0, 0, 0);                   \
@@ -240,10 +225,9 @@ __device__ __forceinline__ unsigned c1_bytes_bf(uint32_t v, int e) {
       h1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh1[kh], b_, h1, 0, 0, 0);                   \
     }                                                                                           \
     if (p_ < OHW) {                                                                             \
-      cv_f4 o0 = ((l0 + m0) + h0) + b0, o1 = ((l1 + m1) + h1) + b1;                             \
-      o0.x = o0.x > 0.f ? o0.x : 0.f; o0.y = o0.y > 0.f ? o0.y : 0.f; o0.z = o0.z > 0.f ? o0.z : 0.f; o0.w = o0.w > 0.f ? o0.w : 0.f; \
-      o1.x = o1.x > 0.f ? o1.x : 0.f; o1.y = o1.y > 0.f ? o1.y : 0.f; o1.z = o1.z > 0.f ? o1.z : 0.f; o1.w = o1.w > 0.f ? o1.w : 0.f; \
-      cv_f4* dst = reinterpret_cast<cv_f4*>(y + ((n0 + f_) * (int64_t)OHW + p_) * C1_F + kq * 8); \
+      g3_f32x4 o0 = ((l0 + m0) + h0) + b0, o1 = ((l1 + m1) + h1) + b1;                          \
+      o0 = c1_relu(o0); o1 = c1_relu(o1);                                                       \
+      g3_f32x4* dst = reinterpret_cast<g3_f32x4*>(y + ((n0 + f_) * (int64_t)OHW + p_) * C1_F + kq * 8); \
       if (NTS) { __builtin_nontemporal_store(o0, dst); __builtin_nontemporal_store(o1, dst + 1); } \
       else { dst[0] = o0; dst[1] = o1; }                                                        \
     }                                                                                           \
@@ -265,7 +249,7 @@ k_conv1_u8_fwd_bf(int N, int H, int W, int OH, int OW, unsigned ow_magic, int pi
   // lo parts: 16 KB behind the frame area
   uint4* wlo = reinterpret_cast<uint4*>(c1_lds + FPI * C1_PLANES * pitch);
   for (int o = tid; o < 16 * 64; o += 256) wlo[o] = wpk3[32 * 64 + o];
-  const cv_f4 b0 = *reinterpret_cast<const cv_f4*>(bias + kq * 8), b1 = *reinterpret_cast<const cv_f4*>(bias + kq * 8 + 4);
+  const g3_f32x4 b0 = *reinterpret_cast<const g3_f32x4*>(bias + kq * 8), b1 = *reinterpret_cast<const g3_f32x4*>(bias + kq * 8 + 4);
   const int HW = H * W, OHW = OH * OW, tiles = (OHW + 15) >> 4, hw16 = HW >> 4;
   const int groups = (N + FPI - 1) / FPI, units = groups * split, step = 4 * split;
   bool first = true;
@@ -312,7 +296,6 @@ k_conv1_u8_fwd_bf(int N, int H, int W, int OH, int OW, unsigned ow_magic, int pi
 // Algorithmic bytes: 28 224 B of pixels + 51 200 B of g per frame (as the forward);
 // 6.55 MFLOP per frame on the f32 MFMA pipe.
 constexpr int C1_WU = 4;                      // k-steps (4 positions each) per block
-constexpr int C1_DW = C1_F * C1_PLANES * C1_TAPS;   // 8192 weight-gradient elements
 
 #define C1_WRW_LOAD(bb_, gv_, po_, f_)                                                          \
   {                                                                                             \
@@ -366,9 +349,9 @@ k_conv1_u8_wrw(int N, int H, int W, int OH, int OW, unsigned ow_magic, int pitch
   const int HW = H * Wd, OHW = OH * OW, hw16 = HW >> 4;
   const int ksteps = (OHW + 3) >> 2, blocks = (ksteps + C1_WU - 1) / C1_WU;
   const int tap_off = (j >> 3) * Wd + (j & 7);
-  cv_f4 acc0[16], acc1[16];
+  g3_f32x4 acc0[16], acc1[16];
 #pragma unroll
-  for (int t = 0; t < 16; ++t) { acc0[t] = cv_f4{0.f, 0.f, 0.f, 0.f}; acc1[t] = cv_f4{0.f, 0.f, 0.f, 0.f}; }
+  for (int t = 0; t < 16; ++t) { acc0[t] = g3_f32x4{0.f, 0.f, 0.f, 0.f}; acc1[t] = g3_f32x4{0.f, 0.f, 0.f, 0.f}; }
   const int units = (N + FPI - 1) / FPI;
   bool first = true;
   for (int u = blockIdx.x; u < units; u += gridDim.x) {
@@ -463,6 +446,7 @@ k_conv1_u8_wrw_b3(int N, int H, int W, int OH, int OW, int Pd, const uint8_t* __
   const int no = (OW + 7) >> 3, octets = OH * no, ksteps = (octets + 3) >> 2;
   const int tap_off = (j >> 3) * W + (j & 7);
   float dbs[2] = {0.f, 0.f};
+  C1WrwG<MASK> gs;
   g3_f32x4 acc0[16], acc1[16];
 #pragma unroll
   for (int t = 0; t < 16; ++t) { acc0[t] = g3_f32x4{0.f, 0.f, 0.f, 0.f}; acc1[t] = g3_f32x4{0.f, 0.f, 0.f, 0.f}; }
@@ -485,75 +469,21 @@ k_conv1_u8_wrw_b3(int N, int H, int W, int OH, int OW, int Pd, const uint8_t* __
           const int o = o0 + k * 256;
           if (o < vecs) {
             const int pl = o / hw16;
-            const uint32_t wv[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
-            uint32_t h[8];
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-              // float(byte) has at most 8 significant bits: its top 16 bits ARE the bf16 value
-              const uint32_t f0 = __float_as_uint(c1_byte(wv[d], 0)), f1 = __float_as_uint(c1_byte(wv[d], 1));
-              const uint32_t f2 = __float_as_uint(c1_byte(wv[d], 2)), f3 = __float_as_uint(c1_byte(wv[d], 3));
-              h[2 * d] = (f0 >> 16) | (f1 & 0xffff0000u);
-              h[2 * d + 1] = (f2 >> 16) | (f3 & 0xffff0000u);
-            }
-            uint4* d4 = reinterpret_cast<uint4*>(px + pl * Pd + (o - pl * hw16) * 16);
-            d4[0] = make_uint4(h[0], h[1], h[2], h[3]);
-            d4[1] = make_uint4(h[4], h[5], h[6], h[7]);
+            c1_stage16_bf(v[k], px + pl * Pd + (o - pl * hw16) * 16);
           }
         }
       }
     }
     __syncthreads();
     const float* gf = g + (int64_t)n * OHW * C1_F + j;
-    // the NEXT K-step's g (and y) values are requested before this K-step's split and MFMAs: with two waves per SIMD
-    // nothing else covers a global load's latency
-    float gn[2][8], yn[2][8];
-    auto request = [&](int ks) {
-      const int o = ks * 4 + kq;
-      const int ohr = o / no, ow0 = (o - ohr * no) * 8;
-      const int oh = ohr < OH ? ohr : OH - 1;
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int ow = ow0 + e;
-          const int64_t off = (int64_t)(oh * OW + (ow < OW ? ow : OW - 1)) * C1_F + 16 * m;
-          gn[m][e] = gf[off];
-          if (MASK) yn[m][e] = yv[(gf - g) + off];
-        }
-    };
-    if (wave < ksteps) request(wave);
+    const float* yf = MASK ? yv + (gf - g) : nullptr;
+    if (wave < ksteps) gs.request(gf, yf, wave, kq, no, OH, OW);
     for (int ks = wave; ks < ksteps; ks += 4) {
-      // this lane's octet: 8 consecutive ow of output row oh
-      const int o = ks * 4 + kq;
-      const int ohr = o / no, ow0 = (o - ohr * no) * 8;
-      const bool row_ok = ohr < OH;
-      const int oh = row_ok ? ohr : OH - 1;
-      float gc[2][8];
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float t = gn[m][e];
-          if (MASK) t = yn[m][e] > 0.f ? t : 0.f;                 // the layer's ReLU
-          gc[m][e] = (row_ok && ow0 + e < OW) ? t : 0.f;
-        }
-      if (ks + 4 < ksteps) request(ks + 4);
+      int oh, ow0;                                  // this lane's octet: 8 consecutive ow of output row oh
       uint4 ap[2][3];                               // [filter half][part] = 8 bf16 along k
-#pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        float gv[2][4];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          gv[e >> 2][e & 3] = gc[m][e];
-          if (MASK) dbs[m] += gc[m][e];
-        }
-        uint2 h0, m0, l0, h1, m1, l1;
-        g3_split4(gv[0], h0, m0, l0);
-        g3_split4(gv[1], h1, m1, l1);
-        ap[m][0] = make_uint4(h0.x, h0.y, h1.x, h1.y);
-        ap[m][1] = make_uint4(m0.x, m0.y, m1.x, m1.y);
-        ap[m][2] = make_uint4(l0.x, l0.y, l1.x, l1.y);
-      }
+      gs.take(ks, kq, no, OH, OW, oh, ow0);
+      if (ks + 4 < ksteps) gs.request(gf, yf, ks + 4, kq, no, OH, OW);
+      gs.split(ap, dbs);
       const uint16_t* pb = px + (oh * C1_S) * W + ow0 * C1_S + tap_off;
       // tap group t: plane t >> 2, rows kh = 2 (t & 3) + (j >> 3) (in tap_off), 8 positions 4 pixels apart.  The NEXT
       // group's eight halfwords are requested before this group's six MFMAs (left alone the compiler reads, waits,
@@ -570,55 +500,18 @@ k_conv1_u8_wrw_b3(int N, int H, int W, int OH, int OW, int Pd, const uint8_t* __
         }
         __builtin_amdgcn_sched_barrier(0);
         const uint32_t* rw = raw[t & 1];
-        const g3_bf16x8 bv = __builtin_bit_cast(g3_bf16x8, make_uint4(rw[0] | (rw[1] << 16), rw[2] | (rw[3] << 16),
-                                                                     rw[4] | (rw[5] << 16), rw[6] | (rw[7] << 16)));
+        const g3_bf16x8 bv = c1_as_bf8(make_uint4(rw[0] | (rw[1] << 16), rw[2] | (rw[3] << 16), rw[4] | (rw[5] << 16), rw[6] | (rw[7] << 16)));
 #pragma unroll
         for (int p = 2; p >= 0; --p) {              // smallest part of g first
-          acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(g3_bf16x8, ap[0][p]), bv, acc0[t], 0, 0, 0);
-          acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(g3_bf16x8, ap[1][p]), bv, acc1[t], 0, 0, 0);
+          acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c1_as_bf8(ap[0][p]), bv, acc0[t], 0, 0, 0);
+          acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c1_as_bf8(ap[1][p]), bv, acc1[t], 0, 0, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
     }
   }
-  // workgroup partial: waves add up in LDS in wave order.  Accumulator tile (half m, tap group t): row 4 kq + r <-> filter
-  // 16 m + 4 kq + r, column j <-> tap t * 16 + j
-  __syncthreads();
-  float* red = reinterpret_cast<float*>(c1_lds);
-  for (int w = 0; w < 4; ++w) {
-    if (wave == w) {
-#pragma unroll
-      for (int t = 0; t < 16; ++t) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int i0 = (4 * kq + r) * (C1_PLANES * C1_TAPS) + t * 16 + j, i1 = i0 + 16 * C1_PLANES * C1_TAPS;
-          red[i0] = (w ? red[i0] : 0.f) + acc0[t][r];
-          red[i1] = (w ? red[i1] : 0.f) + acc1[t][r];
-        }
-      }
-    }
-    __syncthreads();
-  }
-  if (MASK) {
-    // bias gradient: lane (j, kq) summed filters j and 16 + j over its octets; the four kq in a fixed butterfly, the four
-    // waves in wave order behind the slab's 8192 weight-gradient sums
-#pragma unroll
-    for (int m = 0; m < 2; ++m) { dbs[m] += __shfl_xor(dbs[m], 16); dbs[m] += __shfl_xor(dbs[m], 32); }
-    for (int w = 0; w < 4; ++w) {
-      if (wave == w && kq == 0) {
-        red[C1_DW + j] = (w ? red[C1_DW + j] : 0.f) + dbs[0];
-        red[C1_DW + 16 + j] = (w ? red[C1_DW + 16 + j] : 0.f) + dbs[1];
-      }
-      __syncthreads();
-    }
-  }
-  float* out = partial + (int64_t)blockIdx.x * slab;
-  for (int k = tid; k < (MASK ? C1_DW + C1_F : C1_DW); k += 256) out[k] = red[k];
+  c1_wrw_epilogue<16, MASK>(reinterpret_cast<float*>(c1_lds), acc0, acc1, dbs, partial + (int64_t)blockIdx.x * slab, tid, wave, j, kq);
 }
-
-// LDS halfwords per plane of the bf16 frame: the frame, the over-read of a row's tail octet (its positions beyond OW carry
-// g = 0 but are still read), rounded to 16 bytes
-static int c1b_pitch(int HW, int OW) { return (HW + 4 * (8 * ((OW + 7) / 8) - OW) + 8 + 7) / 8 * 8; }
 
 // dw[f][c][kh][kw] (element strides so, sc, sh, sw) = scale * sum of the slabs in slab order
 __global__ void __launch_bounds__(256)
@@ -638,13 +531,6 @@ k_conv1_wrw_reduce(const float* __restrict__ partial, int parts, float scale, fl
   dw[f * so + (tap >> 6) * sc + ((tap >> 3) & 7) * sh + (tap & 7) * sw] = ((s0 + s1) + (s2 + s3)) * scale;
 }
 
-// LDS plane pitch in bytes: >= HW, a multiple of 16 B, and 16 (mod 64) in dwords
-static int c1_pitch(int HW) {
-  int dw = (HW + 3) / 4;
-  dw += ((16 - dw % 64) + 64) % 64;
-  return dw * 4;
-}
-
 }  // namespace mirl
 
 static int g_conv1_wrw_bf16 = 1;   // mirl_conv1_wrw_bf16_set (in-process A/B tests): 0 = off, anything else (-1 = default) = on
@@ -654,27 +540,6 @@ extern "C" int mirl_conv1_wrw_bf16_set(int32_t mode) {
 }
 
 namespace mirl {
-// the weight gradient on the bf16 pipe (k_conv1_u8_wrw_b3) when the bf16 frame fits the LDS, else / when switched off: false
-template <bool MASK>
-static int c1_wrw_b3(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* g, const float* y, float* scratch, int slab,
-                     unsigned* grid_out, hipStream_t st, bool* ran) {
-  *ran = false;
-  if (!g_conv1_wrw_bf16) return MIRL_OK;
-  const int OH = (H - C1_K) / C1_S + 1, OW = (W - C1_K) / C1_S + 1, HW = H * W, Pd = c1b_pitch(HW, OW);
-  size_t lds = (size_t)C1_PLANES * Pd * 2;
-  if (lds > 80 * 1024) return MIRL_OK;                             // two workgroups per CU or the f32-pipe kernel
-  if (lds < (size_t)slab * 4) lds = (size_t)slab * 4;              // the workgroup's partial is reduced there
-  const unsigned grid = capped_grid(N, 512);
-  if (int rc = raise_lds_limit(k_conv1_u8_wrw_b3<MASK>, 80 * 1024)) return rc;
-  ProfScope ps("k_conv1_u8_wrw_b3", (double)N * (C1_PLANES * HW + (MASK ? 2.0 : 1.0) * OH * OW * C1_F * 4), st,
-               (double)N * OH * OW * 2.0 * C1_PLANES * C1_K * C1_K * C1_F);
-  hipLaunchKernelGGL((k_conv1_u8_wrw_b3<MASK>), dim3(grid), dim3(256), lds, st, (int)N, H, W, OH, OW, Pd, x, g, scratch, y, slab);
-  MIRL_LAUNCH_CHECK();
-  *grid_out = grid;
-  *ran = true;
-  return MIRL_OK;
-}
-
 // Launcher behind mirl_conv1_u8_wrw_ex and mirl_conv1_u8_wrw_masked, which check the arguments.  MASK: g is the gradient
 // w.r.t. the layer's output, masked by y > 0 while it is loaded, and db receives its column sums; a slab then carries C1_F
 // more floats.  f32_pipe / interleaved: flag bits 1 / 0 of mirl_conv1_u8_wrw_ex.
@@ -682,18 +547,19 @@ template <bool MASK>
 static int c1_wrw(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* g, const float* y, float scale, float* scratch,
                   float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w, float* db, bool f32_pipe, bool interleaved,
                   hipStream_t st) {
-  const int OH = (H - C1_K) / C1_S + 1, OW = (W - C1_K) / C1_S + 1, HW = H * W, pitch = c1_pitch(HW);
-  const int slab = C1_DW + (MASK ? C1_F : 0);
-  bool b3 = false;
-  unsigned grid = 0;
-  if (!f32_pipe) {
-    if (int rc = c1_wrw_b3<MASK>(N, H, W, x, g, y, scratch, slab, &grid, st, &b3)) return rc;
-  }
-  if (!b3) {
-    const int fpi = (N >= 1024 && 2 * C1_PLANES * pitch <= 64 * 1024) ? 2 : 1;
-    grid = capped_grid((N + fpi - 1) / fpi, 512);
-    size_t lds = (size_t)fpi * C1_PLANES * pitch;
-    if (lds < (size_t)slab * 4) lds = (size_t)slab * 4;            // the workgroup's partial slab is reduced there
+  const int OH = c1_out(H), OW = c1_out(W), HW = H * W;
+  const C1WrwPlan pl = c1_wrw_plan(N, H, W, MASK, !f32_pipe && g_conv1_wrw_bf16);
+  const int pitch = pl.pitch, slab = pl.slab;
+  const unsigned grid = pl.grid;
+  const size_t lds = pl.lds;
+  if (pl.bf16) {
+    if (int rc = raise_lds_limit(k_conv1_u8_wrw_b3<MASK>, C1_LDS_WRW_B3)) return rc;
+    ProfScope ps("k_conv1_u8_wrw_b3", (double)N * (C1_PLANES * HW + (MASK ? 2.0 : 1.0) * OH * OW * C1_F * 4), st,
+                 (double)N * OH * OW * 2.0 * C1_PLANES * C1_K * C1_K * C1_F);
+    hipLaunchKernelGGL((k_conv1_u8_wrw_b3<MASK>), dim3(grid), dim3(256), lds, st, (int)N, H, W, OH, OW, pitch, x, g, scratch, y, slab);
+    MIRL_LAUNCH_CHECK();
+  } else {
+    const int fpi = pl.fpi;
     ProfScope ps("k_conv1_u8_wrw", (double)N * (C1_PLANES * HW + (MASK ? 2.0 : 1.0) * OH * OW * C1_F * 4), st,
                  (double)N * OH * OW * 2.0 * C1_PLANES * C1_K * C1_K * C1_F);
 #define C1_WLAUNCH(FPI_, WC_, PC_, BULK_) \
@@ -722,9 +588,7 @@ extern "C" int mirl_conv1_bf16_set(int32_t mode) {
 
 extern "C" int mirl_conv1_u8_supported(int32_t C, int32_t H, int32_t W, int32_t F, int32_t K, int32_t S) {
   using namespace mirl;
-  if (C != C1_PLANES || F != C1_F || K != C1_K || S != C1_S) return 0;
-  if (H < C1_K || W < C1_K || (W % 4) != 0 || ((H * W) % 16) != 0) return 0;
-  return C1_PLANES * c1_pitch(H * W) <= 64 * 1024 ? 1 : 0;
+  return C == C1_PLANES && F == C1_F && K == C1_K && S == C1_S && c1_shape_ok(H, W) ? 1 : 0;
 }
 
 // flags: bit 0 = plain (cached) output stores instead of non-temporal ones; bit 2 = byte->float conversions interleaved
@@ -735,55 +599,40 @@ extern "C" int mirl_conv1_u8_fwd_ex(int64_t N, int32_t H, int32_t W, const uint8
                                     int64_t ws_c, int64_t ws_h, int64_t ws_w, const float* bias, float scale, float* wpk,
                                     float* y, int32_t flags, void* stream) {
   using namespace mirl;
-  if (N <= 0 || N >= (1LL << 30) || !x || !weight || !bias || !wpk || !y) return fail(MIRL_ERR_ARG, "bad conv1_u8_fwd arguments");
-  if (!mirl_conv1_u8_supported(C1_PLANES, H, W, C1_F, C1_K, C1_S)) return fail(MIRL_ERR_ARG, "conv1_u8_fwd: unsupported frame shape");
-  if (!aligned16(x, y, bias, wpk)) return fail(MIRL_ERR_ARG, "conv1_u8_fwd: pointers must be 16-byte aligned");
+  if (int rc = c1_check_args("conv1_u8_fwd", N, x && weight && bias && wpk && y, c1_shape_ok(H, W), aligned16(x, y, bias, wpk)))
+    return rc;
   if (flags & ~(1 | 4 | 8 | 32 | 0xffff00)) return fail(MIRL_ERR_ARG, "conv1_u8_fwd: unknown flag bits");
   const bool nts = !(flags & 1), interleaved = flags & 4, packed = flags & 8, f32_pipe = flags & 32;
-  int fpi = (flags >> 8) & 0xff, split = (flags >> 16) & 0xff;
   hipStream_t st = (hipStream_t)stream;
-  const int OH = (H - C1_K) / C1_S + 1, OW = (W - C1_K) / C1_S + 1, HW = H * W, pitch = c1_pitch(HW);
-  const int tiles = (OH * OW + 15) / 16;
+  const int OH = c1_out(H), OW = c1_out(W), HW = H * W, pitch = c1_pitch(HW);
   static const int bf_env0 = getenv("MIRL_CONV1_BF16") ? atoi(getenv("MIRL_CONV1_BF16")) : 1;
   const int bf_env = g_conv1_bf16 >= 0 ? g_conv1_bf16 : bf_env0;
   const bool bf = bf_env && !f32_pipe && !interleaved;
-  // which kernel's operand order a scratch block holds is remembered per pointer (host side, one caller thread per the
-  // library's contract): a `packed` call whose kernel choice differs from the packing call's is refused instead of
-  // reading a mismatched layout
-  static std::unordered_map<const void*, int> packed_as;
-  if (packed) {                                           // wpk already holds these weights packed (acting steps between updates)
-    auto it = packed_as.find((const void*)wpk);
-    if (it == packed_as.end() || it->second != (bf ? 2 : 1))
-      return fail(MIRL_ERR_STATE, "conv1_u8_fwd: flags bit 3 (weights already packed) but this scratch block was not packed by the same kernel variant");
-  } else {
-    packed_as[(const void*)wpk] = bf ? 2 : 1;
+  // a `packed` call (acting steps between updates) whose kernel choice differs from the packing call's is refused instead
+  // of reading a mismatched layout
+  if (!c1_wpk_holds(wpk, bf ? C1_WPK_BF16 : C1_WPK_F32, packed))
+    return fail(MIRL_ERR_STATE, "conv1_u8_fwd: flags bit 3 (weights already packed) but this scratch block was not packed by the same kernel variant");
+  if (!packed) {
     ProfScope ps("k_conv1_pack_w", 2.0 * C1_WPK * 4, st);
     if (bf) hipLaunchKernelGGL(k_conv1_pack_w3, dim3(4), dim3(256), 0, st, weight, ws_o, ws_c, ws_h, ws_w, scale, (uint4*)wpk);
     else hipLaunchKernelGGL(k_conv1_pack_w, dim3((C1_WPK + 255) / 256), dim3(256), 0, st, weight, ws_o, ws_c, ws_h, ws_w, scale, wpk);
     MIRL_LAUNCH_CHECK();
   }
-  if (fpi != 1 && fpi != 2) fpi = (N >= 1024 && 2 * C1_PLANES * pitch <= 64 * 1024) ? 2 : 1;
-  if (fpi == 2 && 2 * C1_PLANES * pitch > 64 * 1024) fpi = 1;
-  const int max_split = (tiles + 3) / 4;
-  if (split <= 0) split = N >= 512 ? 1 : (int)((512 + N - 1) / N);
-  if (split > max_split) split = max_split;
-  if (fpi == 2) split = 1;
-  const unsigned grid = capped_grid((N + fpi - 1) / fpi * split, 512);
-  const size_t lds = (size_t)fpi * C1_PLANES * pitch + (bf ? 16 * 1024 : 0);
+  const C1FwdPlan pl = c1_fwd_plan(N, H, W, bf, (flags >> 8) & 0xff, (flags >> 16) & 0xff);
   ProfScope ps("k_conv1_u8_fwd", (double)N * (C1_PLANES * HW + (double)OH * OW * C1_F * 4), st,
                (double)N * OH * OW * 2.0 * C1_PLANES * C1_K * C1_K * C1_F);
 #define C1_LAUNCH(KERNEL_, WPK_) \
-  hipLaunchKernelGGL(KERNEL_, dim3(grid), dim3(256), lds, st, (int)N, H, W, OH, OW, magic_u32(OW), pitch, split, x, WPK_, bias, y)
+  hipLaunchKernelGGL(KERNEL_, dim3(pl.grid), dim3(256), pl.lds, st, (int)N, H, W, OH, OW, magic_u32(OW), pitch, pl.split, x, WPK_, bias, y)
   if (bf) {
-    const auto k = fpi == 2 ? (nts ? k_conv1_u8_fwd_bf<2, 1> : k_conv1_u8_fwd_bf<2, 0>) : (nts ? k_conv1_u8_fwd_bf<1, 1> : k_conv1_u8_fwd_bf<1, 0>);
-    if (int rc = raise_lds_limit(k, 96 * 1024)) return rc;      // 2 frames + 16 KB of weight parts = 74 KB of dynamic LDS
+    const auto k = pl.fpi == 2 ? (nts ? k_conv1_u8_fwd_bf<2, 1> : k_conv1_u8_fwd_bf<2, 0>) : (nts ? k_conv1_u8_fwd_bf<1, 1> : k_conv1_u8_fwd_bf<1, 0>);
+    if (int rc = raise_lds_limit(k, C1_LDS_FWD_BF)) return rc;      // 2 frames + 16 KB of weight parts = 74 KB of dynamic LDS
     C1_LAUNCH(k, (const uint4*)wpk);
   } else {
     // fpi 2 with nt stores: all 64 byte->float conversions of a tile in front of its MFMA chain (BULK): 2.20 vs 2.41 ms
     // per 41 472 frames (conversions interleaved with the chain delay MFMA issue; 250 VGPRs, still 2 waves per SIMD).
     // Bit 2 of flags keeps the interleaved variant for the probe.
-    const auto k = fpi == 2 ? (nts ? (interleaved ? k_conv1_u8_fwd<2, 1> : k_conv1_u8_fwd<2, 1, 1>) : k_conv1_u8_fwd<2, 0>)
-                            : (nts ? k_conv1_u8_fwd<1, 1> : k_conv1_u8_fwd<1, 0>);
+    const auto k = pl.fpi == 2 ? (nts ? (interleaved ? k_conv1_u8_fwd<2, 1> : k_conv1_u8_fwd<2, 1, 1>) : k_conv1_u8_fwd<2, 0>)
+                               : (nts ? k_conv1_u8_fwd<1, 1> : k_conv1_u8_fwd<1, 0>);
     C1_LAUNCH(k, (const float*)wpk);
   }
 #undef C1_LAUNCH
@@ -801,13 +650,13 @@ extern "C" int mirl_conv1_u8_fwd(int64_t N, int32_t H, int32_t W, const uint8_t*
 // f32 kernel's 8192 floats of rounds 2 — callers size the block from this query, not from a constant)
 extern "C" int mirl_conv1_u8_wpk_floats(int64_t* out) {
   if (!out) return mirl::fail(MIRL_ERR_ARG, "null out");
-  *out = 12288;
+  *out = mirl::C1_WPK_FLOATS;
   return MIRL_OK;
 }
 
 extern "C" int mirl_conv1_u8_wrw_scratch_floats(int64_t* out) {
   if (!out) return mirl::fail(MIRL_ERR_ARG, "null out");
-  *out = (int64_t)512 * (mirl::C1_DW + mirl::C1_F);      // per-workgroup slabs: 8192 weight-gradient sums (+ 32 bias-gradient sums, masked form)
+  *out = mirl::C1_SCRATCH_FLOATS;      // per-workgroup slabs: 8192 weight-gradient sums (+ 32 bias-gradient sums, masked form)
   return MIRL_OK;
 }
 
@@ -817,9 +666,7 @@ extern "C" int mirl_conv1_u8_wrw_ex(int64_t N, int32_t H, int32_t W, const uint8
                                     float* scratch, float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w,
                                     int32_t flags, void* stream) {
   using namespace mirl;
-  if (N <= 0 || N >= (1LL << 30) || !x || !g || !scratch || !dw) return fail(MIRL_ERR_ARG, "bad conv1_u8_wrw arguments");
-  if (!mirl_conv1_u8_supported(C1_PLANES, H, W, C1_F, C1_K, C1_S)) return fail(MIRL_ERR_ARG, "conv1_u8_wrw: unsupported frame shape");
-  if (!aligned16(x, g, scratch)) return fail(MIRL_ERR_ARG, "conv1_u8_wrw: pointers must be 16-byte aligned");
+  if (int rc = c1_check_args("conv1_u8_wrw", N, x && g && scratch && dw, c1_shape_ok(H, W), aligned16(x, g, scratch))) return rc;
   return c1_wrw<false>(N, H, W, x, g, nullptr, scale, scratch, dw, ws_o, ws_c, ws_h, ws_w, nullptr, flags & 2, flags & 1, (hipStream_t)stream);
 }
 
@@ -829,9 +676,9 @@ extern "C" int mirl_conv1_u8_wrw_masked(int64_t N, int32_t H, int32_t W, const u
                                         float* scratch, float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w,
                                         float* db, void* stream) {
   using namespace mirl;
-  if (N <= 0 || N >= (1LL << 30) || !x || !dy || !y || !scratch || !dw || !db) return fail(MIRL_ERR_ARG, "bad conv1_u8_wrw_masked arguments");
-  if (!mirl_conv1_u8_supported(C1_PLANES, H, W, C1_F, C1_K, C1_S)) return fail(MIRL_ERR_ARG, "conv1_u8_wrw: unsupported frame shape");
-  if (!aligned16(x, dy, y, scratch)) return fail(MIRL_ERR_ARG, "conv1_u8_wrw: pointers must be 16-byte aligned");
+  if (int rc = c1_check_args("conv1_u8_wrw_masked", N, x && dy && y && scratch && dw && db, c1_shape_ok(H, W),
+                             aligned16(x, dy, y, scratch), "conv1_u8_wrw"))
+    return rc;
   return c1_wrw<true>(N, H, W, x, dy, y, scale, scratch, dw, ws_o, ws_c, ws_h, ws_w, db, false, false, (hipStream_t)stream);
 }
 

@@ -1,6 +1,7 @@
 // host_util.hpp — the launchers' pure host arithmetic (no HIP headers: tests/test_host_util_cpu.py builds it with the host
 // compiler alone).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace mirl {
@@ -16,5 +17,93 @@ inline bool aligned16(const P*... p) { return ((((uintptr_t)p % 16) == 0) && ...
 
 // grid of a persistent kernel: one workgroup per work unit up to `cap` resident ones
 inline unsigned capped_grid(int64_t units, int64_t cap) { return (unsigned)(units < cap ? units : cap); }
+
+// ---------------------------------------------------------------------------------------------------------------
+// The input layer from uint8 frames, Conv2d(planes -> 32, kernel 8, stride 4): launch plans of csrc/conv_in.hip (four
+// planes, C1_*) and csrc/conv_in1p.hip (one plane, C1P_*).  The entry points take no buffer sizes, so the size queries
+// and the launchers both read the constants and plans below: what a query reports is what a launcher may write.
+constexpr int C1_PLANES = 4, C1_K = 8, C1_S = 4, C1_F = 32, C1_TAPS = C1_K * C1_K;
+constexpr int C1_DW = C1_F * C1_PLANES * C1_TAPS;   // 8192 weight-gradient elements
+constexpr int C1_WGS = 512;                         // most workgroups of a forward or weight-gradient launch (2 per CU) = most slabs
+constexpr int C1_WPK_FLOATS = 3 * 2 * C1_K * 64 * 4;   // wpk scratch: three 16 KB weight parts (the f32 kernel's image is 8192 floats)
+constexpr int C1_WLO_BYTES = 2 * C1_K * 64 * 16;    // the bf16 forward keeps the lo weight parts in LDS behind the frames
+constexpr size_t C1_LDS = 64 * 1024, C1_LDS_WRW_B3 = 80 * 1024, C1_LDS_FWD_BF = 96 * 1024;   // unasked / raised limits
+constexpr int C1P_DW = C1_F * C1_TAPS;              // 2048 weight-gradient elements
+constexpr int C1P_SLAB = C1P_DW + C1_F;             // floats per workgroup slab: weight sums, then the bias sums (masked form)
+constexpr int C1P_WGS = 1024;                       // weight gradient: most workgroups = slabs (4 per CU)
+constexpr int C1P_FWD_WGS = 1024;                   // forward: most resident workgroups
+constexpr int C1P_FPI = 4;                          // most frames per LDS fill
+constexpr int C1P_WPK = 3 * 2 * 2 * 64 * 4;         // packed weight image in floats: [part][kh half][filter half][lane] x 16 B
+constexpr int64_t C1_SCRATCH_FLOATS = (int64_t)C1_WGS * (C1_DW + C1_F), C1P_SCRATCH_FLOATS = (int64_t)C1P_WGS * C1P_SLAB;
+
+inline int c1_out(int hw) { return (hw - C1_K) / C1_S + 1; }   // output rows / columns of H / W
+
+// LDS plane pitch in bytes of the raw four-plane frame: >= HW, a multiple of 16 B, and 16 (mod 64) in dwords
+inline int c1_pitch(int HW) {
+  int dw = (HW + 3) / 4;
+  dw += ((16 - dw % 64) + 64) % 64;
+  return dw * 4;
+}
+
+// LDS halfwords per plane of the bf16 frame of the bf16 weight-gradient kernels: the frame, the over-read of a row's tail
+// octet (its positions beyond OW carry g = 0 but are still read: the last index is (4 (OH - 1) + 7) W + 32 ceil(OW / 8) + 3),
+// rounded to 16 bytes
+inline int c1_bf_pitch(int HW, int OW) { return (HW + 4 * (8 * ((OW + 7) / 8) - OW) + 8 + 7) / 8 * 8; }
+
+// frame shapes the kernels take: 16 B vectors never straddle planes, and the LDS plan fits what a kernel gets unasked
+inline bool c1_shape_ok(int H, int W) {
+  if (H < C1_K || W < C1_K || (W % 4) != 0 || (int64_t)H * W > (int64_t)C1_LDS || ((H * W) % 16) != 0) return false;
+  return (size_t)C1_PLANES * c1_pitch(H * W) <= C1_LDS;
+}
+// one plane: the weight gradient stages one frame as bf16 (with its tail over-read); the forward's raw bytes are half of that
+inline bool c1p_shape_ok(int H, int W) {
+  if (H < C1_K || W < C1_K || H > 4096 || W > 4096 || (W % 4) != 0 || ((H * W) % 16) != 0) return false;
+  return (size_t)c1_bf_pitch(H * W, c1_out(W)) * 2 <= C1_LDS;
+}
+
+struct C1FwdPlan { int fpi, split; unsigned grid; size_t lds; };   // frames per LDS fill, workgroups per frame, launch
+// four planes; bf: the bf16-pipe kernel; fpi / split: the flags' overrides (anything else = choose)
+inline C1FwdPlan c1_fwd_plan(int64_t N, int H, int W, bool bf, int fpi, int split) {
+  const int pitch = c1_pitch(H * W), tiles = (c1_out(H) * c1_out(W) + 15) / 16;
+  const bool fits2 = (size_t)2 * C1_PLANES * pitch <= C1_LDS;
+  if (fpi != 1 && fpi != 2) fpi = (N >= 1024 && fits2) ? 2 : 1;
+  if (fpi == 2 && !fits2) fpi = 1;
+  // few frames: `split` workgroups share one frame's tiles (at least one tile per wave)
+  const int max_split = (tiles + 3) / 4;
+  if (split <= 0) split = N >= C1_WGS ? 1 : (int)((C1_WGS + N - 1) / N);
+  if (split > max_split) split = max_split;
+  if (fpi == 2) split = 1;
+  return {fpi, split, capped_grid((N + fpi - 1) / fpi * split, C1_WGS), (size_t)fpi * C1_PLANES * pitch + (bf ? C1_WLO_BYTES : 0)};
+}
+inline C1FwdPlan c1p_fwd_plan(int64_t N, int H, int W) {
+  const int HW = H * W, tiles = (c1_out(H) * c1_out(W) + 15) / 16;
+  // frames per LDS fill: more only once every resident workgroup has a group of its own, and within 32 KiB
+  int fpi_max = 32 * 1024 / HW;
+  fpi_max = fpi_max < 1 ? 1 : (fpi_max > C1P_FPI ? C1P_FPI : fpi_max);
+  const int64_t fpi64 = N / C1P_FWD_WGS;
+  const int fpi = fpi64 < 1 ? 1 : (fpi64 > fpi_max ? fpi_max : (int)fpi64);
+  const int max_split = (tiles + 3) / 4;
+  int split = N >= C1P_FWD_WGS ? 1 : (int)((C1P_FWD_WGS + N - 1) / N);
+  if (split > max_split) split = max_split;
+  return {fpi, split, capped_grid((N + fpi - 1) / fpi * split, C1P_FWD_WGS), (size_t)fpi * HW};
+}
+
+// bf16: the bf16-pipe kernel (else the f32-pipe one, four planes only, with fpi frames per fill); pitch: halfwords per
+// plane (bf16) or bytes per plane (f32 pipe); slab: floats a workgroup writes at scratch + blockIdx.x * slab
+struct C1WrwPlan { bool bf16; int fpi, pitch, slab; unsigned grid; size_t lds; };
+inline size_t c1_at_least_slab(size_t lds, int slab) { return lds < (size_t)slab * 4 ? (size_t)slab * 4 : lds; }   // the partial is reduced there
+// four planes; allow_bf16 = false: the f32-pipe kernel (flags / mirl_conv1_wrw_bf16_set), which is also what takes a bf16
+// frame beyond 80 KiB (two workgroups per CU)
+inline C1WrwPlan c1_wrw_plan(int64_t N, int H, int W, bool masked, bool allow_bf16) {
+  const int HW = H * W, slab = C1_DW + (masked ? C1_F : 0), Pd = c1_bf_pitch(HW, c1_out(W)), pitch = c1_pitch(HW);
+  if (allow_bf16 && (size_t)C1_PLANES * Pd * 2 <= C1_LDS_WRW_B3)
+    return {true, 1, Pd, slab, capped_grid(N, C1_WGS), c1_at_least_slab((size_t)C1_PLANES * Pd * 2, slab)};
+  const int fpi = (N >= 1024 && (size_t)2 * C1_PLANES * pitch <= C1_LDS) ? 2 : 1;
+  return {false, fpi, pitch, slab, capped_grid((N + fpi - 1) / fpi, C1_WGS), c1_at_least_slab((size_t)fpi * C1_PLANES * pitch, slab)};
+}
+inline C1WrwPlan c1p_wrw_plan(int64_t N, int H, int W) {
+  const int Pd = c1_bf_pitch(H * W, c1_out(W));
+  return {true, 1, Pd, C1P_SLAB, capped_grid(N, C1P_WGS), c1_at_least_slab((size_t)Pd * 2, C1P_SLAB)};
+}
 
 }  // namespace mirl

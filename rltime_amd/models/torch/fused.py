@@ -12,11 +12,12 @@ expressions; parity tests in tests/test_fused_gpu.py compare against those):
                      one in-place bias+ReLU pass; backward = one mask + bias-gradient
                      pass, MIOpen data / weight gradients
   conv_u8_bias_relu  the INPUT layer, relu(conv2d(x_u8 * scale, W) + b) (cnn.py:44-49),
-                     straight from the replay's uint8 frames on the f32 MFMA pipe
+                     straight from the replay's uint8 frames on the bf16 matrix pipe
                      (csrc/conv_in.hip): no converted copy of the frames, no separate
                      bias / ReLU pass; backward = the weight gradient from the same uint8
                      frames, ReLU mask and bias gradient in that kernel.  One-plane frames
-                     (N, 1, H, W) take the second kernel family, csrc/conv_in1p.hip
+                     (N, 1, H, W) take the second kernel family, csrc/conv_in1p.hip; one
+                     autograd function serves both through a ConvU8Family
   cos_embed          IQN cosine features (iqn.py:78-81) in one kernel
   quantile_product   x[m] * relu(phi @ Wq^T + bq)[m, n] (iqn.py:82-102) with a
                      backward that never materialises g*x / g*emb / the mask
@@ -326,34 +327,69 @@ def frames_to_f32_nhwc(x, scale):
     return out
 
 
+class ConvU8Family:
+    """One kernel family of the input layer from uint8 frames, by plane count: what differs between csrc/conv_in.hip (four
+    planes) and csrc/conv_in1p.hip (one) above the kernels.  `call(name, ...)` runs `<prefix><name>` on the current stream."""
+
+    def __init__(self, planes, prefix, fwd_flags, fwd_packed):
+        self.planes, self.prefix = planes, prefix
+        self.fwd_flags = fwd_flags          # what the autograd forward passes behind `y` to `fwd`
+        self.fwd_packed = fwd_packed        # the forward that takes `flags` (bit 3: wpk already holds the packed weights)
+
+    def strides(self, weight):
+        """A (F, planes, k, k) weight's element strides as the entry points take them: no channel stride for one plane."""
+        so, sc, sh, sw = weight.stride()
+        return (so, sc, sh, sw) if self.planes > 1 else (so, sh, sw)
+
+    def supported(self, h, w, f, k, s):
+        planes = (self.planes,) if self.planes > 1 else ()
+        return bool(getattr(_lib().lib, self.prefix + "supported")(*planes, h, w, f, k, s))
+
+    def wpk_floats(self):
+        return _scratch_floats(self.prefix + "wpk_floats")
+
+    def wrw_scratch_floats(self):
+        return _scratch_floats(self.prefix + "wrw_scratch_floats")
+
+    def call(self, name, *args):
+        L = _lib()
+        L.check(getattr(L.lib, self.prefix + name)(*args, L.stream()), self.prefix + name)
+
+
+_CONV_U8 = {4: ConvU8Family(4, "mirl_conv1_u8_", (), "fwd_ex"), 1: ConvU8Family(1, "mirl_conv1p_u8_", (0,), "fwd")}
+
+
+def conv_u8_family(planes):
+    """The family for frames of `planes` planes, or None."""
+    return _CONV_U8.get(planes)
+
+
 def conv_u8_supported(x, conv):
-    """Does the one-pass input layer (mirl_conv1_u8_fwd) cover this conv on this uint8 block?"""
+    """Does the one-pass input layer (mirl_conv1_u8_fwd / mirl_conv1p_u8_fwd) cover this conv on this uint8 block?"""
     if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.uint8 and x.dim() == 4 and x.is_contiguous()
             and x.data_ptr() % 16 == 0 and conv.bias is not None and conv.weight.dtype == torch.float32
             and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1
             and conv.kernel_size[0] == conv.kernel_size[1] and conv.stride[0] == conv.stride[1]
             and conv.in_channels == x.shape[1] and not torch.is_autocast_enabled()):
         return False
-    if x.shape[1] == 1:                       # one-plane frames: the second kernel family (csrc/conv_in1p.hip)
-        return bool(_lib().lib.mirl_conv1p_u8_supported(x.shape[2], x.shape[3], conv.out_channels, conv.kernel_size[0], conv.stride[0]))
-    return bool(_lib().lib.mirl_conv1_u8_supported(x.shape[1], x.shape[2], x.shape[3], conv.out_channels,
-                                                   conv.kernel_size[0], conv.stride[0]))
+    fam = conv_u8_family(x.shape[1])             # no family for another plane count
+    return fam is not None and fam.supported(x.shape[2], x.shape[3], conv.out_channels, conv.kernel_size[0], conv.stride[0])
 
 
-class _ConvU8BiasReLU(torch.autograd.Function):
+class _ConvU8(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, scale, stride):
         L = _lib()
-        n, _, h, w = x.shape
+        n, c, h, w = x.shape
+        fam = ctx.fam = conv_u8_family(c)
         f, k = weight.shape[0], weight.shape[2]
         oh, ow = (h - k) // stride + 1, (w - k) // stride + 1
         y = torch.empty((n, f, oh, ow), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
         if n:
-            wpk = torch.empty(_scratch_floats("mirl_conv1_u8_wpk_floats"), dtype=torch.float32, device=x.device)
-            so, sc, sh, sw = weight.stride()
+            wpk = torch.empty(fam.wpk_floats(), dtype=torch.float32, device=x.device)
             b = bias if bias.data_ptr() % 16 == 0 else bias.clone()
-            L.check(L.lib.mirl_conv1_u8_fwd(n, h, w, L.ptr(x), L.ptr(weight), so, sc, sh, sw, L.ptr(b), float(scale), L.ptr(wpk), L.ptr(y),
-                                            L.stream()), "mirl_conv1_u8_fwd")
+            fam.call("fwd", n, h, w, L.ptr(x), L.ptr(weight), *fam.strides(weight), L.ptr(b), float(scale), L.ptr(wpk), L.ptr(y),
+                     *fam.fwd_flags)
         ctx.scale = scale
         ctx.save_for_backward(x, weight, y)
         return y
@@ -366,77 +402,27 @@ class _ConvU8BiasReLU(torch.autograd.Function):
             _, db = relu_bwd_bias_rows(grad, y, y.shape[1])
             dw = torch.zeros_like(weight) if ctx.needs_input_grad[1] else None
             return None, dw, (db if ctx.needs_input_grad[2] else None), None, None
-        # weight gradient from the uint8 frames (csrc/conv_in.hip): no float pixels anywhere
-        L = _lib()
+        # weight gradient from the uint8 frames: no float pixels anywhere
+        L, fam = _lib(), ctx.fam
         n, _, h, w = x.shape
-        scratch = torch.empty(_scratch_floats("mirl_conv1_u8_wrw_scratch_floats"), dtype=torch.float32, device=x.device)
+        scratch = torch.empty(fam.wrw_scratch_floats(), dtype=torch.float32, device=x.device)
         dw = torch.empty_like(weight)
-        so, sc, sh, sw = dw.stride()
         if grad.data_ptr() % 16 == 0:
             # ReLU mask and bias gradient inside the weight-gradient kernel (this layer's input takes no gradient, so the
             # masked gradient itself is not needed anywhere else): one pass over dy, y and the uint8 frames
             db = torch.empty(weight.shape[0], dtype=torch.float32, device=x.device)
-            L.check(L.lib.mirl_conv1_u8_wrw_masked(n, h, w, L.ptr(x), L.ptr(grad), L.ptr(y), float(ctx.scale), L.ptr(scratch), L.ptr(dw), so, sc, sh, sw,
-                                                   L.ptr(db), L.stream()), "mirl_conv1_u8_wrw_masked")
+            fam.call("wrw_masked", n, h, w, L.ptr(x), L.ptr(grad), L.ptr(y), float(ctx.scale), L.ptr(scratch), L.ptr(dw), *fam.strides(dw),
+                     L.ptr(db))
         else:
             # an upstream gradient off the 16-byte grid: the mask + bias-gradient pass leaves an aligned masked gradient
             g, db = relu_bwd_bias_rows(grad, y, y.shape[1])
-            L.check(L.lib.mirl_conv1_u8_wrw(n, h, w, L.ptr(x), L.ptr(g), float(ctx.scale), L.ptr(scratch), L.ptr(dw), so, sc, sh, sw,
-                                            L.stream()), "mirl_conv1_u8_wrw")
-        return None, dw, (db if ctx.needs_input_grad[2] else None), None, None
-
-
-class _ConvU8P1BiasReLU(torch.autograd.Function):
-    """_ConvU8BiasReLU for one-plane frames (csrc/conv_in1p.hip): a (F, 1, k, k) weight has no channel stride to pass."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, scale, stride):
-        L = _lib()
-        n, _, h, w = x.shape
-        f, k = weight.shape[0], weight.shape[2]
-        oh, ow = (h - k) // stride + 1, (w - k) // stride + 1
-        y = torch.empty((n, f, oh, ow), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        if n:
-            wpk = torch.empty(_scratch_floats("mirl_conv1p_u8_wpk_floats"), dtype=torch.float32, device=x.device)
-            so, _, sh, sw = weight.stride()
-            b = bias if bias.data_ptr() % 16 == 0 else bias.clone()
-            L.check(L.lib.mirl_conv1p_u8_fwd(n, h, w, L.ptr(x), L.ptr(weight), so, sh, sw, L.ptr(b), float(scale), L.ptr(wpk), L.ptr(y), 0,
-                                             L.stream()), "mirl_conv1p_u8_fwd")
-        ctx.scale = scale
-        ctx.save_for_backward(x, weight, y)
-        return y
-
-    @staticmethod
-    def backward(ctx, grad):
-        x, weight, y = ctx.saved_tensors
-        grad = grad.contiguous(memory_format=torch.channels_last)
-        if not (ctx.needs_input_grad[1] and x.shape[0]):
-            _, db = relu_bwd_bias_rows(grad, y, y.shape[1])
-            dw = torch.zeros_like(weight) if ctx.needs_input_grad[1] else None
-            return None, dw, (db if ctx.needs_input_grad[2] else None), None, None
-        L = _lib()
-        n, _, h, w = x.shape
-        scratch = torch.empty(_scratch_floats("mirl_conv1p_u8_wrw_scratch_floats"), dtype=torch.float32, device=x.device)
-        dw = torch.empty_like(weight)
-        so, _, sh, sw = dw.stride()
-        if grad.data_ptr() % 16 == 0:
-            # ReLU mask and bias gradient inside the weight-gradient kernel: one pass over dy, y and the uint8 frames
-            db = torch.empty(weight.shape[0], dtype=torch.float32, device=x.device)
-            L.check(L.lib.mirl_conv1p_u8_wrw_masked(n, h, w, L.ptr(x), L.ptr(grad), L.ptr(y), float(ctx.scale), L.ptr(scratch), L.ptr(dw), so, sh, sw,
-                                                    L.ptr(db), L.stream()), "mirl_conv1p_u8_wrw_masked")
-        else:
-            # an upstream gradient off the 16-byte grid: the mask + bias-gradient pass leaves an aligned masked gradient
-            g, db = relu_bwd_bias_rows(grad, y, y.shape[1])
-            L.check(L.lib.mirl_conv1p_u8_wrw(n, h, w, L.ptr(x), L.ptr(g), float(ctx.scale), L.ptr(scratch), L.ptr(dw), so, sh, sw,
-                                             L.stream()), "mirl_conv1p_u8_wrw")
+            fam.call("wrw", n, h, w, L.ptr(x), L.ptr(g), float(ctx.scale), L.ptr(scratch), L.ptr(dw), *fam.strides(dw))
         return None, dw, (db if ctx.needs_input_grad[2] else None), None, None
 
 
 def conv_u8_bias_relu(x, conv, scale):
     """relu(conv(x * scale)) for uint8 NCHW x; the caller checked conv_u8_supported(x, conv)."""
-    if x.shape[1] == 1:
-        return _ConvU8P1BiasReLU.apply(x, conv.weight, conv.bias, float(scale), int(conv.stride[0]))
-    return _ConvU8BiasReLU.apply(x, conv.weight, conv.bias, float(scale), int(conv.stride[0]))
+    return _ConvU8.apply(x, conv.weight, conv.bias, float(scale), int(conv.stride[0]))
 
 
 def cos_embed(taus, freq):

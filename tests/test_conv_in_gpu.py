@@ -286,7 +286,7 @@ class _MisalignedGrad(torch.autograd.Function):
 @pytest.mark.parametrize("h,w", [(8, 8), (12, 16)])
 @pytest.mark.parametrize("integer", [True, False], ids=["integer", "real"])
 def test_input_layer_backward_with_a_misaligned_upstream_gradient(h, w, integer):
-    """_ConvU8BiasReLU.backward when the upstream gradient is not 16-byte aligned: the mask + bias-gradient pass
+    """_ConvU8.backward when the upstream gradient is not 16-byte aligned: the mask + bias-gradient pass
     (k_relu_bwd_bias_rows) makes an aligned masked copy and mirl_conv1_u8_wrw follows, instead of the one masked kernel.
     Small-integer frames, weights, bias and gradient make every partial sum exact in f32 in any order: dW and db are then
     BIT-identical to the aligned backward's; real-valued operands are held to the 1e-4 bound."""
