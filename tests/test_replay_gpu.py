@@ -173,13 +173,19 @@ def test_per_sequences_vs_oracle_recurrent():
     print("PER leaves differing from the reference by 1 ulp: %d / %d" % (m["leaf"], m["leaves"]))
 
 
-@pytest.mark.parametrize("T,P,n", [(9, 3, 2), (20, 5, 3), (80, 40, 2), (128, 4, 1)])
+@pytest.mark.parametrize("T,P,n", [(9, 3, 2), (20, 5, 3), (80, 40, 2), (128, 4, 1),
+                                   (2, 1, 1), (7, 2, 2), (129, 3, 2), (136, 8, 1), (200, 5, 2), (264, 4, 1)])
 def test_wave_per_sequence_priorities_vs_oracle(T, P, n):
     """k_recalc_flagged_wave (8 <= T <= 128: one wave per sequence, NumPy's eight
     interleaved accumulators kept in lanes 0..7, shuffle-combined in NumPy's
     association) against the reference restatement: leaf kinds exact, values
     <= 1 ulp, for sequence lengths with and without an n % 8 tail, fresh (Python
-    float 1.0 -> float64 path) and fully-updated (float32 path) sequences."""
+    float 1.0 -> float64 path) and fully-updated (float32 path) sequences.
+    On both sides of that range the lane-per-sequence k_recalc_flagged is held the
+    same way: T = 2 and 7 (7 is the last sequential-sum length), and T > 128, where
+    NumPy's pairwise summation runs on np_pairwise_sum's explicit device-side stack:
+    129 and 136 split at 64 (a multiple of 8 either way), 200 at 96 (rounded down
+    from 100), 264 at 128 (from 132), and its right half of 136 splits again."""
     E = 4
     per_env = T + P + n + 3 * (T - T // 2) + 8
     m = _run_pair(40 + T, E, [("feed", per_env), ("draw", 31, 0.0), ("draw", 32, 0.1), ("feed", T // 2 + 3),
