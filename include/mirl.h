@@ -890,6 +890,25 @@ int mirl_catch_env_step_pre(int32_t E, int32_t P, int32_t S, int32_t G, int32_t 
                             float* rewards_out, uint8_t* dones_out, int32_t clip_rewards, float* ep_reward, int32_t* ep_len,
                             float* out_reward, int32_t* out_len, int32_t* action_counts, uint64_t* rng_step, uint64_t step,
                             void* stream);
+/* One step of CartPole as a device-native vector env (csrc/acting.hip k_cartpole_env_step): one thread per env, float64.
+ * `state` is [E] 48-byte records {double x[4] = cart position, cart velocity, pole angle, pole angular velocity; int64
+ * episodes_started; int32 t; int32 pad} that the launch reads and writes IN PLACE — there is no clock and no pair of halves,
+ * so the same launch replays from a captured graph any number of times.  Transition (gravity 9.8, cart mass 1, pole mass
+ * 0.1, pole half length 0.5, push 10, dt 0.02; every operation IEEE float64 in this order, nothing contracted):
+ *   force = action == 1 ? +10 : -10 (any other action value pushes left);  total = 1.0 + 0.1;  ml = 0.1 * 0.5
+ *   tmp = (force + ml * w * w * sin) / total
+ *   th_acc = (9.8 * sin - cos * tmp) / (0.5 * (4.0 / 3.0 - 0.1 * cos * cos / total));  x_acc = tmp - ml * th_acc * cos / total
+ *   x += 0.02 * v;  v += 0.02 * x_acc;  theta += 0.02 * w;  w += 0.02 * th_acc  (all from the OLD values);  t += 1
+ * with sin = theta * P(theta^2) and cos = Q(theta^2), P / Q the Taylor polynomials through theta^17 / theta^16 evaluated in
+ * Horner form from the highest coefficient down to the constant 1, coefficients +-1/k! as float64 — not libm.  Reward 1.0;
+ * done = |x| > 2.4 || |theta| > 24 * pi / 360 || t >= max_episode_steps.  A finished env starts its next episode in the same
+ * step and returns the NEW episode's first observation with done = 1: x[k] = ((double)w_k + 0.5) * 2^-32 * 0.1 - 0.05 from the
+ * four words of Philox4x32-10 with key seed ^ 0xCA27901E and counter (episodes_started, env), then episodes_started += 1,
+ * t = 0.  reset_all = 1: every env starts an episode that way; rewards 0, dones 1; actions may be NULL.  obs float32 [E][4]
+ * (the state rounded to nearest), rewards float32 [E], dones uint8 [E].  1 <= E <= 2^24, max_episode_steps >= 1, state and obs
+ * 16-byte aligned, else MIRL_ERR_ARG before any launch.                                                                  */
+int mirl_cartpole_env_step(int32_t E, int32_t max_episode_steps, const int32_t* actions, void* state, uint64_t seed,
+                           int32_t reset_all, float* obs, float* rewards, uint8_t* dones, void* stream);
 int mirl_episode_track(int32_t E, int32_t A, const float* rewards, const uint8_t* dones,
                        const int32_t* actions, float* ep_reward, int32_t* ep_len,
                        float* out_reward, int32_t* out_len, int32_t* action_counts, void* stream);

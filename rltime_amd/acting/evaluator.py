@@ -104,6 +104,9 @@ class Evaluator:
         if not hasattr(env, "step_device") or torch.device(getattr(env, "device", "cpu")).type != "cuda":
             raise ValueError("Evaluator: the env steps on the host; evaluation needs an env that steps on the device "
                              "('catch', 'synthetic-atari')")
+        if str(getattr(getattr(env, "observation_space", None), "dtype", "")) == "float32":
+            raise ValueError("Evaluator: float32 vector observations (the device CartPole's MLP policies) are not covered: the "
+                             "evaluation rides on the fused acting step, which takes CNN policies on uint8 frames only")
         if not 1 <= int(steps_per_launch) <= EpisodeTracker.ROWS:
             raise ValueError("steps_per_launch: 1 .. %d" % EpisodeTracker.ROWS)
         self.policy, self.env = policy, env

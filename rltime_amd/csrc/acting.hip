@@ -273,6 +273,84 @@ k_catch_env_step(CatchArgs a, ActorPreArgs pre) {
   }
 }
 
+// One step of CartPole as a device-native vector env (acting/cartpole_device_env.py): the cart-pole of
+// acting/cartpole_env.py (Barto, Sutton & Anderson 1983; Euler steps of 0.02 s) in float64, one thread per env.  The env's
+// whole state is ONE 48-byte record that only its thread reads and writes, in place — no shared clock, no pair of halves,
+// no atomics — so the launch is a fixed one on caller-owned buffers and captures as it is.  sin / cos are fixed Taylor
+// polynomials in Horner form in theta^2 (a step only ever starts from |theta| <= 12 degrees, where they are good to the
+// last bit or so) and the build compiles with -ffp-contract=off, so a NumPy restatement of these lines agrees bit for
+// bit and whole trajectories, dones included, can be pinned (tests/cartpole_device_restate.py).
+struct CartPoleRecord { double x[4]; int64_t episodes_started; int32_t t; int32_t pad; };
+static_assert(sizeof(CartPoleRecord) == 48, "the record is 48 bytes: three 16-byte vectors");
+
+__device__ __forceinline__ double cartpole_sin(double th) {
+  const double z = th * th;
+  double p = 2.8114572543455206e-15;                     // +1/17!
+  p = p * z + -7.647163731819816e-13;                    // -1/15!
+  p = p * z + 1.6059043836821613e-10;                    // +1/13!
+  p = p * z + -2.505210838544172e-08;                    // -1/11!
+  p = p * z + 2.7557319223985893e-06;                    // +1/9!
+  p = p * z + -0.0001984126984126984;                    // -1/7!
+  p = p * z + 0.008333333333333333;                      // +1/5!
+  p = p * z + -0.16666666666666666;                      // -1/3!
+  p = p * z + 1.0;
+  return th * p;
+}
+
+__device__ __forceinline__ double cartpole_cos(double th) {
+  const double z = th * th;
+  double p = 4.779477332387385e-14;                      // +1/16!
+  p = p * z + -1.1470745597729725e-11;                   // -1/14!
+  p = p * z + 2.08767569878681e-09;                      // +1/12!
+  p = p * z + -2.755731922398589e-07;                    // -1/10!
+  p = p * z + 2.48015873015873e-05;                      // +1/8!
+  p = p * z + -0.001388888888888889;                     // -1/6!
+  p = p * z + 0.041666666666666664;                      // +1/4!
+  p = p * z + -0.5;                                      // -1/2!
+  p = p * z + 1.0;
+  return p;
+}
+
+__global__ void __launch_bounds__(64)
+k_cartpole_env_step(int E, int max_steps, int reset_all, const int32_t* __restrict__ actions, CartPoleRecord* __restrict__ state,
+                    uint64_t seed, float4* __restrict__ obs, float* __restrict__ rewards, uint8_t* __restrict__ dones) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= E) return;
+  CartPoleRecord s = state[e];
+  int dn = 1;
+  float rr = 0.0f;
+  if (!reset_all) {
+    const double gravity = 9.8, cart_mass = 1.0, pole_mass = 0.1, half_length = 0.5, push = 10.0, dt = 0.02;
+    const double total = cart_mass + pole_mass, ml = pole_mass * half_length;
+    const double x = s.x[0], v = s.x[1], th = s.x[2], w = s.x[3];
+    const double force = actions[e] == 1 ? push : -push;
+    const double sn = cartpole_sin(th), cs = cartpole_cos(th);
+    const double tmp = (force + ml * w * w * sn) / total;
+    const double th_acc = (gravity * sn - cs * tmp) / (half_length * (4.0 / 3.0 - pole_mass * cs * cs / total));
+    const double x_acc = tmp - ml * th_acc * cs / total;
+    s.x[0] = x + dt * v;
+    s.x[1] = v + dt * x_acc;
+    s.x[2] = th + dt * w;
+    s.x[3] = w + dt * th_acc;
+    s.t += 1;
+    rr = 1.0f;
+    const double angle_limit = 24.0 * 3.141592653589793 / 360.0;
+    dn = (fabs(s.x[0]) > 2.4 || fabs(s.x[2]) > angle_limit || s.t >= max_steps) ? 1 : 0;
+  }
+  if (dn) {                                             // a new episode starts in the same step
+    uint32_t r[4];
+    philox_4x32(seed ^ 0xCA27901Eull, (uint64_t)s.episodes_started, (uint32_t)e, r);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s.x[k] = ((double)r[k] + 0.5) * 2.3283064365386963e-10 * 0.1 - 0.05;     // 2^-32
+    s.episodes_started += 1;
+    s.t = 0;
+  }
+  state[e] = s;
+  obs[e] = float4{(float)s.x[0], (float)s.x[1], (float)s.x[2], (float)s.x[3]};
+  rewards[e] = rr;
+  dones[e] = (uint8_t)dn;
+}
+
 // The reference evaluation's counting rule (rltime/eval.py:59-72, loop :113-149) as ONE launch per vector step: of E
 // envs in parallel, the first N episodes that STARTED are counted, in the order the host loop meets them — step by
 // step, env by env — and an env's mask closes when the running count of started episodes passes N.  The sequential
@@ -505,6 +583,20 @@ extern "C" int mirl_catch_env_step_pre(int32_t E, int32_t P, int32_t S, int32_t 
   int gx = (row_q + 255) / 256; if (gx > 8) gx = 8;
   mirl::ProfScope ps("k_catch_env_step_pre", (double)E * (double)row_q * 16.0 + (double)E * H * 4.0 * 6.0, (hipStream_t)stream);
   hipLaunchKernelGGL(mirl::k_catch_env_step<true>, dim3(gx, E), dim3(256), 0, (hipStream_t)stream, a, p);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
+extern "C" int mirl_cartpole_env_step(int32_t E, int32_t max_episode_steps, const int32_t* actions, void* state, uint64_t seed,
+                                      int32_t reset_all, float* obs, float* rewards, uint8_t* dones, void* stream) {
+  // (E <= 2^24 keeps the grid and every byte offset far inside 32 bits)
+  if (E <= 0 || E > (1 << 24) || max_episode_steps < 1 || (reset_all != 0 && reset_all != 1) || (!reset_all && !actions) || !state ||
+      !obs || !rewards || !dones || !mirl::aligned16(state, obs))
+    return mirl::fail(MIRL_ERR_ARG, "bad cartpole_env_step arguments (1 <= E <= 2^24, max_episode_steps >= 1, reset_all 0 | 1, "
+                                    "16-byte aligned state / obs)");
+  mirl::ProfScope ps("k_cartpole_env_step", (double)E * (2.0 * 48.0 + 16.0 + 4.0 + 1.0 + 4.0), (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_cartpole_env_step, dim3((E + 63) / 64), dim3(64), 0, (hipStream_t)stream, (int)E, (int)max_episode_steps,
+                     (int)reset_all, actions, (mirl::CartPoleRecord*)state, seed, (float4*)obs, rewards, dones);
   MIRL_LAUNCH_CHECK();
   return MIRL_OK;
 }

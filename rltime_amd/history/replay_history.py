@@ -14,8 +14,10 @@ is no CPU fallback, and construction fails loudly without a GPU.
 
 Differences a caller can observe (all documented in DESIGN.md):
   * batches are torch tensors already on the device with the dtypes the trainer
-    would see after ``make_tensor`` (models/torch/utils.py:95-123): uint8 frames,
-    everything else float32, except ``actions`` / ``loss_indices`` (int64);
+    would see after ``make_tensor`` (models/torch/utils.py:95-123): uint8 frames
+    (float32 observations stay float32: stored as their bytes, returned as the
+    float32 view of them), everything else float32, except ``actions`` /
+    ``loss_indices`` (int64);
   * ``update`` wants whole vector steps (one transition per env), which is what
     the synchronous actor emits (acting/actor.py:97-149);
   * ``state_store`` is accepted and ignored: the replay *is* the device store
@@ -70,7 +72,13 @@ class _Layout:
             self.tuple_obs = False
             self.frame_shape = tuple(x.shape)
             self.extra_shapes = []
-        self.frame_bytes = int(np.prod(self.frame_shape))
+        # float32 observations (vector envs: CartPole) are stored as their bytes — the rings move bytes — and handed back
+        # as the float32 view; every other dtype keeps the uint8 contract
+        obs = x[0] if self.tuple_obs else x
+        self.float_obs = str(getattr(obs, "dtype", "")).replace("torch.", "") == "float32"
+        if self.float_obs and not self.frame_shape:
+            raise ValueError("a float32 observation needs at least one axis")
+        self.frame_bytes = int(np.prod(self.frame_shape)) * (4 if self.float_obs else 1)
         self.extra_sizes = [int(np.prod(s)) for s in self.extra_shapes]
         self.extra_f32 = sum(self.extra_sizes)
         self.layer_keys = [k for k in state if k != "x"]
@@ -165,6 +173,8 @@ class ReplayHistoryBuffer(History):
         pass
 
     def _create(self, layout, num_envs, env_base, policy_f32):
+        if layout.float_obs and self._dedup:
+            raise ValueError("frame_stack_dedup stores uint8 frame stacks plane by plane: a float32 observation has none")
         self._layout = layout
         self._example_state = layout.example
         self._num_envs = num_envs
@@ -259,7 +269,15 @@ class ReplayHistoryBuffer(History):
             x = s["next_state"]["x"]
             return x[0] if lay.tuple_obs else x
 
-        fields = {"frames": stack(obs, np.uint8)}
+        if lay.float_obs:
+            # bytes, not values: every sample must already BE float32 (nothing is cast on this path)
+            rows = [np.asarray(obs(s)) for s in chunk]
+            other = {a.dtype for a in rows} - {np.dtype(np.float32)}
+            if other:
+                raise TypeError("the shard stores float32 observations as their bytes: got %s" % sorted(map(str, other)))
+            fields = {"frames": torch.from_numpy(np.ascontiguousarray(np.stack(rows)))}
+        else:
+            fields = {"frames": stack(obs, np.uint8)}
         if lay.extra_f32:
             fields["extra"] = stack(lambda s: np.concatenate(
                 [np.asarray(v, dtype=np.float32).reshape(-1)
@@ -291,6 +309,7 @@ class ReplayHistoryBuffer(History):
             raise _lib.MirlError(
                 "update_batch before the shard exists: call configure() first")
         K = int(frames.shape[0])
+        frames = self._frame_bytes_of(frames)
         keep = [frames, actions, rewards, dones, extra, state, initials, policy]
         plane_ptr, plane_stride = None, 0
         if newest_plane_only:
@@ -323,6 +342,15 @@ class ReplayHistoryBuffer(History):
                 if t is not None:
                     t.record_stream(s)
 
+    def _frame_bytes_of(self, frames):
+        """A float32 observation block of a float32 shard as its bytes (a view: nothing is converted); everything else as
+        it came, for the uint8 assertion of the callers."""
+        if self._layout is not None and self._layout.float_obs and frames.dtype == torch.float32:
+            assert frames.is_contiguous() and frames[0].numel() * 4 == self._layout.frame_bytes
+            return frames.view(torch.uint8)
+        assert self._layout is None or not self._layout.float_obs, "the shard stores float32 observations: got %s" % frames.dtype
+        return frames
+
     # -- a whole acting rollout ahead of its device side (mirl_replay_ingest_plan / _planned) ---------------
     def supports_planned_ingest(self):
         """The fused one-launch ingest covers this shard (no de-duplicated storage, no acting-time priority init)."""
@@ -340,6 +368,7 @@ class ReplayHistoryBuffer(History):
         """Device side of step `step` of the current plan: same payload contract as update_batch; the buffers must stay
         valid (and are re-read) on every replay of a graph this call was captured into."""
         K = int(frames.shape[0])
+        frames = self._frame_bytes_of(frames)
         for t in (frames, actions, rewards, dones, extra, state, initials, policy):
             if t is not None:
                 assert t.is_cuda and t.is_contiguous()
@@ -439,7 +468,8 @@ class ReplayHistoryBuffer(History):
         R = self._rows
         per = self._MODE == _lib.MODE_PER
         new = self._buffer
-        frames = new("frames", (R, B) + tuple(lay.frame_shape), torch.uint8)
+        frames = new("frames", (R, B) + (tuple(lay.frame_shape) if not lay.float_obs else
+                                        tuple(lay.frame_shape[:-1]) + (4 * lay.frame_shape[-1],)), torch.uint8)
         extra = new("extra", (R, B, lay.extra_f32), torch.float32) if lay.extra_f32 else None
         state = new("state", (R, B, lay.state_f32), torch.float32) if lay.state_f32 else None
         initials = new("initials", (R, B), torch.float32) if lay.has_initials else None
@@ -469,6 +499,8 @@ class ReplayHistoryBuffer(History):
 
         def build(cut):
             x = cut(frames)
+            if lay.float_obs:
+                x = x.view(torch.float32)                 # (rows, B) + frame_shape: the bytes as they were stored
             if lay.tuple_obs:
                 parts, at = [x], 0
                 for size, shape in zip(lay.extra_sizes, lay.extra_shapes):

@@ -52,8 +52,12 @@ def make_vec_env(env, env_args, num_envs, device, seed=0):
 def _make_base_vec_env(env, env_args, num_envs, device, seed=0):
     if isinstance(env, str) and env.startswith("CartPole-"):
         # the CPU plumbing config (BASELINE configs[0]): the build's own cart-pole, v0 = 200-step episodes, v1 = 500
-        from rltime_amd.acting.cartpole_env import CartPoleVecEnv
         limit = (env_args or {}).get("max_episode_steps", 500 if env.endswith("v1") else 200)
+        if (env_args or {}).get("device", False):
+            # the same cart-pole as ONE HIP kernel per vector step (acting/cartpole_device_env.py): cartpole_dqn / cartpole_iqn
+            from rltime_amd.acting.cartpole_device_env import CartPoleDeviceVecEnv
+            return CartPoleDeviceVecEnv(num_envs, max_episode_steps=limit, device=device, seed=seed)
+        from rltime_amd.acting.cartpole_env import CartPoleVecEnv
         return CartPoleVecEnv(num_envs, max_episode_steps=limit, seed=seed)
     if env == "catch":
         # the one device-native game (acting/catch_env.py: a single HIP kernel per vector step)
