@@ -171,8 +171,8 @@ int mirl_replay_ingest(mirl_replay* h, const mirl_ingest* in, void* stream);
  *                               into the rings, table / env / leaf ops, tree fix: one launch).  Its arguments do not
  *                               change from rollout to rollout, so the call can sit in a captured graph; `in->count`
  *                               must equal the plan's, env_ids_host / newest_plane_only are ignored / refused.
- * Shards with de-duplicated frame storage or acting_priority_init return MIRL_ERR_ARG (they need the multi-kernel
- * ingest); callers keep mirl_replay_ingest for those.                                                                */
+ * Shards with de-duplicated frame storage or acting_priority_init return MIRL_ERR_ARG (their ingest has launches of
+ * its own around that one); callers keep mirl_replay_ingest for those.                                                */
 int mirl_replay_ingest_plan(mirl_replay* h, int32_t steps, int32_t count, const int32_t* env_ids_host, void* stream);
 int mirl_replay_ingest_planned(mirl_replay* h, int32_t step, const mirl_ingest* in, void* stream);
 
@@ -182,11 +182,6 @@ int mirl_replay_ingest_planned(mirl_replay* h, int32_t step, const mirl_ingest* 
  * newest_planes[e] at `stride` bytes per env — as "transition -1" of every env.  Without it the
  * first stack of an env is taken to be a reset stack (one real plane).                              */
 int mirl_replay_prime_stack(mirl_replay* h, const uint8_t* newest_planes, int64_t stride, void* stream);
-
-/* mirl_replay_ingest issues ONE fused kernel per call (frame / state / q-value rows, scalars,
- * plan, tree fix) unless the shard de-duplicates frame stacks or initialises priorities at
- * acting time; 0 selects the separate kernels of rounds 1-2 for every shard (A/B tests).   */
-int mirl_ingest_fused_set(int32_t on);
 
 /* needed_feed_count (replay_history.py:62-75).  *out = -1 for None.           */
 int mirl_replay_needed_feed_count(mirl_replay* h, int32_t mbatch, int32_t num_envs, int64_t* out);

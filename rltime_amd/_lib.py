@@ -118,7 +118,6 @@ _SIGNATURES = {
     "mirl_replay_ingest": [_vp, _P(Ingest), _vp],
     "mirl_replay_ingest_plan": [_vp, _i32, _i32, _vp, _vp],
     "mirl_replay_ingest_planned": [_vp, _i32, _P(Ingest), _vp],
-    "mirl_ingest_fused_set": [_i32],
     "mirl_replay_prime_stack": [_vp, _vp, _i64, _vp],
     "mirl_replay_needed_feed_count": [_vp, _i32, _i32, _P(_i64)],
     "mirl_replay_sample": [_vp, _i32, _f64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

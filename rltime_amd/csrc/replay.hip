@@ -12,9 +12,9 @@
 // predecessor of the oldest live transition alive and nothing is stored twice.
 //
 // Kernels (all HBM- or latency-bound; no MFMA — there is no contraction here):
-//   k_scatter_rows    ingest: [K][row] dense -> ring slots            (a1, a16)
-//   k_ingest_scalars  ingest: per-transition scalars + PER init       (a1, a2)
-//   k_plan_apply      ingest: host plan -> tables, leaves, dirty list (a2)
+//   k_ingest_fused(_planned) ingest in one launch: rows -> ring slots, scalars + PER init,
+//                     host plan -> tables, leaves, dirty list, tree fix (a1, a2, a3, a16)
+//   k_dedup_depth     verified whole stacks: stack depth + virtual predecessors, ahead of the ingest
 //   k_tree_fix        re-sum ancestors of dirty leaves, level by level (a3)
 //   k_per_sample      LDS-staged stratified descent + IS weights      (a3, a4, a8)
 //   k_uniform_sample  flat choice -> (env, start) (+ episode refine)  (a5)
@@ -62,48 +62,8 @@ __device__ __forceinline__ int64_t slot_of(const Dev& d, int32_t e, int64_t off)
 // ---------------------------------------------------------------------------
 // ingest
 // ---------------------------------------------------------------------------
-// Copy K dense rows into ring slots.  One block column per row, 16 B per lane
-// when the geometry allows, else a byte loop.
-__global__ void __launch_bounds__(256)
-k_scatter_rows(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-               const int32_t* __restrict__ s_env, const int64_t* __restrict__ s_off,
-               int64_t C, int32_t row_bytes, int64_t dst_stride, int vec, int64_t src_stride) {
-  const int k = blockIdx.y;
-  const int64_t slot = (int64_t)s_env[k] * C + s_off[k] % C;
-  const uint8_t* s = src + (int64_t)k * src_stride;
-  uint8_t* t = dst + slot * dst_stride;
-  if (vec) {
-    const int n = row_bytes >> 4;
-    const u32x4* s4 = (const u32x4*)s;
-    u32x4* t4 = (u32x4*)t;
-    for (int c = blockIdx.x * 256 + threadIdx.x; c < n; c += gridDim.x * 256) t4[c] = s4[c];
-  } else {
-    for (int c = blockIdx.x * 256 + threadIdx.x; c < row_bytes; c += gridDim.x * 256) t[c] = s[c];
-  }
-}
-
-__global__ void __launch_bounds__(256)
-k_ingest_scalars(Dev d, int K, const int32_t* __restrict__ s_env, const int64_t* __restrict__ s_off,
-                 const float* __restrict__ initials, const int32_t* __restrict__ actions,
-                 const float* __restrict__ rewards, const uint8_t* __restrict__ dones) {
-  int k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= K) return;
-  int64_t sl = slot_of(d, s_env[k], s_off[k]);
-  if (d.has_init) d.initials[sl] = initials[k];
-  d.actions[sl] = actions[k];
-  d.rewards[sl] = rewards[k];
-  d.dones[sl] = dones[k] ? 1 : 0;
-  if (d.per) {
-    d.loss[sl] = MIRL_LOSS_FRESH;     // sample['loss'] = self._max_loss (python 1.0), prioritized_replay_history.py:141
-    d.prio_index[sl] = -1;
-    d.stamp[sl] = 0ull;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// frame de-duplication (mirl_replay_config.stack_planes)
-// ---------------------------------------------------------------------------
-// One workgroup per ingested transition: how many planes of its stack are real.
+// Frame de-duplication (mirl_replay_config.stack_planes) fed whole stacks: ahead of the ingest launch,
+// one workgroup per ingested transition: how many planes of its stack are real.
 // Plane P-1 is the new one; plane P-1-j must equal the newest plane stored with
 // the env's transition off-j (the wrapper rolled the stack), for j = 1.. until
 // the first mismatch; everything older must then be the zero fill of a reset
@@ -156,31 +116,6 @@ __device__ __forceinline__ TV priority_of(const Dev& d, int32_t e, int64_t base)
   return seq_priority(g, p);
 }
 
-// Apply one ingest plan (book.hpp): table writes, env mirrors, leaf ops.
-__global__ void __launch_bounds__(256)
-k_plan_apply(Dev d, int n_table, const TableOp* __restrict__ tops, int n_env, const EnvOp* __restrict__ eops,
-             int n_leaf, const LeafOp* __restrict__ lops) {
-  int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n_table) d.prio_index[slot_of(d, tops[i].env, tops[i].off)] = tops[i].value;
-  if (i < n_env) { d.first[eops[i].env] = eops[i].first; d.count[eops[i].env] = eops[i].count; }
-  if (i < n_leaf) {
-    LeafOp op = lops[i];
-    int64_t leaf = d.cap + op.slot;
-    if (op.activate) {
-      d.slot_env[op.slot] = op.env; d.slot_base[op.slot] = op.base;
-      TV p = priority_of(d, op.env, op.base);
-      d.tv[leaf] = p.v; d.tk[leaf] = p.k;
-      if (d.tmin) d.tmin[leaf] = p.v;
-    } else {                         // prioritized_replay_history.py:223-227
-      d.slot_env[op.slot] = -1; d.slot_base[op.slot] = -1;
-      d.tv[leaf] = 0.0; d.tk[leaf] = KW;
-      if (d.tmin) d.tmin[leaf] = INFINITY;
-    }
-    int at = atomicAdd(d.dirty_count, 1);
-    d.dirty[at] = op.slot;
-  }
-}
-
 // Re-derive every ancestor of the dirty leaves from its two children, one tree
 // level per barrier (segment_tree.py:91-97; the result depends only on the
 // leaves, so the batch order is irrelevant).  Single workgroup: the tree is
@@ -205,8 +140,7 @@ __global__ void __launch_bounds__(1024)
 k_tree_fix(Dev d) { tree_fix_body(d); }
 
 // The whole device side of one History.update call (history.py:123-176 + the _sample_added /
-// _sample_removed hooks) in ONE launch — rounds 1-2 issued k_scatter_rows x 2-4,
-// k_ingest_scalars, k_plan_apply and k_tree_fix per vector step.  Grid (bx, K + 1):
+// _sample_removed hooks) in ONE launch, whatever the shard's mode.  Grid (bx, K + 1):
 //   y < K   copy workgroups of transition y: frame row, extra / recurrent-state / q-value rows
 //           into their ring slots (16 B per lane when the geometry allows);
 //   y == K  ONE bookkeeping workgroup: per-transition scalars (so that the freshly ingested
@@ -219,6 +153,7 @@ struct IngestSrc {
   int vec_frames, vec_extra, vec_state, vec_policy;
   int64_t frames_stride;      // bytes between the frame rows of consecutive transitions in `frames`
   int32_t row_bytes, slot_bytes;   // bytes copied per transition / ring slot pitch (de-dup: one plane)
+  int32_t depth_verified;     // de-dup fed whole stacks: k_dedup_depth already wrote d.depth from the verified chain
 };
 
 __device__ __forceinline__ void copy_row(const uint8_t* s, uint8_t* t, int row_bytes, int vec, int part, int parts) {
@@ -254,8 +189,9 @@ ingest_fused_body(const Dev& d, int K, const IngestSrc& in, const int32_t* __res
     d.actions[sl] = in.actions[i];
     d.rewards[sl] = in.rewards[i];
     d.dones[sl] = in.dones[i] ? 1 : 0;
+    // sample['loss'] = self._max_loss (python 1.0), prioritized_replay_history.py:141
     if (d.per) { d.loss[sl] = MIRL_LOSS_FRESH; d.prio_index[sl] = -1; d.stamp[sl] = 0ull; }
-    if (d.planes) {
+    if (d.planes && !in.depth_verified) {
       // newest-plane form of de-duplicated storage: the stack of transition `off` has one real
       // plane after a reset (an unprimed env's first transition, or this transition ended an
       // episode: env_wrappers/common.py:175-178 zero-fills the rest), else one more than its predecessor's
@@ -281,7 +217,7 @@ ingest_fused_body(const Dev& d, int K, const IngestSrc& in, const int32_t* __res
       TV p = priority_of(d, op.env, op.base);
       d.tv[leaf] = p.v; d.tk[leaf] = p.k;
       if (d.tmin) d.tmin[leaf] = p.v;
-    } else {
+    } else {                         // prioritized_replay_history.py:223-227
       d.slot_env[op.slot] = -1; d.slot_base[op.slot] = -1;
       d.tv[leaf] = 0.0; d.tk[leaf] = KW;
       if (d.tmin) d.tmin[leaf] = INFINITY;
@@ -970,7 +906,6 @@ struct mirl_replay {
   // rollout plan (mirl_replay_ingest_plan / _planned): ONE device buffer at a fixed address — captured graphs hold it
   char* roll_plan = nullptr; size_t roll_cap = 0; int roll_steps = 0, roll_count = 0, roll_cap_steps = 0, roll_cap_count = 0;
   bool book_broken = false;            // a rollout plan failed after the book had moved: host and device disagree
-  std::vector<char> roll_host;
 };
 
 extern "C" const char* mirl_last_error(void) { return last_error_ref().c_str(); }
@@ -1085,20 +1020,6 @@ extern "C" int mirl_replay_create(const mirl_replay_config* cfg, mirl_replay** o
   return MIRL_OK;
 }
 
-static int scatter(mirl_replay* h, const void* src, void* ring, const int32_t* s_env, const int64_t* s_off,
-                   int K, int32_t row_bytes, int64_t stride, hipStream_t st, int64_t src_stride = 0) {
-  if (!row_bytes || !src) return MIRL_OK;
-  if (!src_stride) src_stride = row_bytes;
-  int vec = (row_bytes % 16 == 0) && (stride % 16 == 0) && (((uintptr_t)src) % 16 == 0) && (src_stride % 16 == 0);
-  int chunks = vec ? row_bytes / 16 : row_bytes;
-  int gx = (chunks + 255) / 256; if (gx > 64) gx = 64; if (gx < 1) gx = 1;
-  ProfScope ps(row_bytes >= 8192 ? "k_scatter_rows(frames)" : "k_scatter_rows(small rows)", 2.0 * K * row_bytes, st);
-  hipLaunchKernelGGL(k_scatter_rows, dim3(gx, K), dim3(256), 0, st, (const uint8_t*)src, (uint8_t*)ring, s_env, s_off,
-                     h->d.C, row_bytes, stride, vec, src_stride);
-  MIRL_LAUNCH_CHECK();
-  return MIRL_OK;
-}
-
 static int update_losses_impl(mirl_replay* h, int64_t count, const int64_t* indices, const float* losses, const int32_t* guard,
                               hipStream_t st);
 
@@ -1127,102 +1048,114 @@ extern "C" int mirl_replay_prime_stack(mirl_replay* h, const uint8_t* newest_pla
 
 static IngestSrc make_ingest_src(const Dev& d, const mirl_ingest* in) {
   const bool planes = d.planes != 0;
-  const int64_t f_stride = in->frames_stride > 0 ? in->frames_stride : (planes ? d.plane_bytes : d.F);
+  // whole stacks handed to a de-duplicated shard (k_dedup_depth has verified them): the newest plane of each is kept
+  const bool verified = planes && !in->newest_plane_only;
+  const uint8_t* frames = verified ? in->frames + (size_t)(d.planes - 1) * d.plane_bytes : in->frames;
+  const int64_t f_stride = verified ? d.F : in->frames_stride > 0 ? in->frames_stride : (planes ? d.plane_bytes : d.F);
   const int32_t f_row = planes ? d.plane_bytes : d.F, f_slot = planes ? d.plane_bytes : d.Fp;
   auto vec_ok = [](const void* src, const void* dst, int64_t row_bytes, int64_t src_stride, int64_t dst_stride) {
     return (int)(row_bytes && row_bytes % 16 == 0 && src_stride % 16 == 0 && dst_stride % 16 == 0 &&
                  ((uintptr_t)src) % 16 == 0 && ((uintptr_t)dst) % 16 == 0);
   };
-  return IngestSrc{in->frames, in->extra, in->state, in->policy, in->initials, in->actions, in->rewards, in->dones,
-                   vec_ok(in->frames, d.frames, f_row, f_stride, f_slot), vec_ok(in->extra, d.extra, d.X * 4, d.X * 4, d.X * 4),
+  return IngestSrc{frames, in->extra, in->state, in->policy, in->initials, in->actions, in->rewards, in->dones,
+                   vec_ok(frames, d.frames, f_row, f_stride, f_slot), vec_ok(in->extra, d.extra, d.X * 4, d.X * 4, d.X * 4),
                    vec_ok(in->state, d.state, d.S * 4, d.S * 4, d.S * 4), vec_ok(in->policy, d.policy, d.A * 4, d.A * 4, d.A * 4),
-                   f_stride, f_row, f_slot};
+                   f_stride, f_row, f_slot, verified ? 1 : 0};
 }
 
-static int g_ingest_fused = 1;      // test hook: mirl_ingest_fused_set
-extern "C" int mirl_ingest_fused_set(int32_t on) { g_ingest_fused = on ? 1 : 0; return MIRL_OK; }
-
-extern "C" int mirl_replay_ingest(mirl_replay* h, const mirl_ingest* in, void* stream) {
+// What mirl_replay_ingest and mirl_replay_ingest_planned both refuse, ahead of everything that moves.
+static int check_ingest_args(mirl_replay* h, const mirl_ingest* in) {
   if (h && h->book_broken) return fail(MIRL_ERR_STATE, "this shard's host bookkeeping ran ahead of its device rows (an ingest_plan failed half-way); the shard is unusable");
   if (!h || !in || in->count <= 0) return fail(MIRL_ERR_ARG, "bad ingest arguments");
+  const Dev& d = h->d;
+  if (!in->frames || !in->actions || !in->rewards || !in->dones) return fail(MIRL_ERR_ARG, "frames/actions/rewards/dones are required");
+  if (in->count > 65535) return fail(MIRL_ERR_ARG, "at most 65535 transitions per ingest call (split the vector step)");
+  if ((d.X && !in->extra) || (d.S && !in->state) || (d.has_init && !in->initials) || (d.A && !in->policy))
+    return fail(MIRL_ERR_ARG, "a configured payload array is NULL");
+  return MIRL_OK;
+}
+
+// The launch of both entry points: `launch(grid, block, src)` enqueues k_ingest_fused or k_ingest_fused_planned.
+template <class Launch>
+static int launch_ingest(mirl_replay* h, const mirl_ingest* in, hipStream_t st, Launch launch) {
+  const Dev& d = h->d;
+  const int K = in->count;
+  const IngestSrc src = make_ingest_src(d, in);
+  // 16 KB per copy workgroup: a (4, 84, 84) frame row takes 2
+  int parts = (int)((src.row_bytes + 16383) / 16384); if (parts < 1) parts = 1; if (parts > 8) parts = 8;
+  {
+    ProfScope ps("k_ingest_fused", 2.0 * K * ((double)src.row_bytes + 4.0 * (d.X + d.S + d.A) + 13 + (d.per ? 16 : 0)), st);
+    launch(dim3(parts, K + 1), dim3(1024), src);
+  }
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
+// One step's five lists behind one another, each 16 B aligned: [sample_env i32][sample_off i64][table][env][leaf] -> the
+// header the kernels find them by.  A sink with cap 0 only measures; bytes past `cap` are counted, not written.
+struct PlanSink {
+  char* dst; size_t cap, size;
+  int64_t put(const void* src, size_t bytes) {
+    const size_t at = size;
+    if (bytes && at + bytes <= cap) memcpy(dst + at, src, bytes);
+    size = align_up(at + bytes, 16);
+    return (int64_t)at;
+  }
+};
+
+static PlanHdr pack_plan(const Plan& p, int K, bool per, PlanSink& to) {
+  PlanHdr hd;
+  hd.n_table = per ? (int32_t)p.table_ops.size() : 0;
+  hd.n_env = (int32_t)p.env_ops.size();
+  hd.n_leaf = per ? (int32_t)p.leaf_ops.size() : 0;
+  hd.pad = 0;
+  hd.o_env = to.put(p.sample_env.data(), sizeof(int32_t) * K);
+  hd.o_off = to.put(p.sample_off.data(), sizeof(int64_t) * K);
+  hd.o_tab = to.put(p.table_ops.data(), sizeof(TableOp) * p.table_ops.size());
+  hd.o_eop = to.put(p.env_ops.data(), sizeof(EnvOp) * p.env_ops.size());
+  hd.o_lop = to.put(p.leaf_ops.data(), sizeof(LeafOp) * p.leaf_ops.size());
+  return hd;
+}
+
+extern "C" int mirl_replay_ingest(mirl_replay* h, const mirl_ingest* in, void* stream) {
+  int rc = check_ingest_args(h, in); if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   Dev& d = h->d;
   const int K = in->count;
-  if (!in->frames || !in->actions || !in->rewards || !in->dones) return fail(MIRL_ERR_ARG, "frames/actions/rewards/dones are required");
-  if (K > 65535) return fail(MIRL_ERR_ARG, "at most 65535 transitions per ingest call (split the vector step)");
-  if ((d.X && !in->extra) || (d.S && !in->state) || (d.has_init && !in->initials) || (d.A && !in->policy))
-    return fail(MIRL_ERR_ARG, "a configured payload array is NULL");
+  const bool acting_td = h->book.cfg.acting_priority_init && d.per;
   // every argument check sits AHEAD of the host bookkeeping: a refused call must leave the book, the staging
   // ring and the device rings exactly where they were
-  if (d.planes && in->newest_plane_only && (h->book.cfg.acting_priority_init && d.per))
+  if (d.planes && in->newest_plane_only && acting_td)
     return fail(MIRL_ERR_ARG, "newest_plane_only ingest cannot be combined with acting_priority_init");
   if (d.planes && !in->newest_plane_only && !aligned16(in->frames))
     return fail(MIRL_ERR_ARG, "stack_planes: the frames array must be 16-byte aligned");
-  int rc = h->book.ingest(K, in->env_ids_host, h->plan);
+  rc = h->book.ingest(K, in->env_ids_host, h->plan);
   if (rc) { last_error_ref() = h->book.err; return rc; }
-  Plan& p = h->plan;
-  // pack the plan: [sample_env i32][sample_off i64][table][env][leaf]
-  size_t o_env = 0, o_off = align_up(o_env + sizeof(int32_t) * K, 16), o_tab = align_up(o_off + sizeof(int64_t) * K, 16);
-  size_t o_eop = align_up(o_tab + sizeof(TableOp) * p.table_ops.size(), 16);
-  size_t o_lop = align_up(o_eop + sizeof(EnvOp) * p.env_ops.size(), 16);
-  size_t total = align_up(o_lop + sizeof(LeafOp) * p.leaf_ops.size(), 16);
+  const Plan& p = h->plan;
+  PlanSink measure{nullptr, 0, 0};
+  pack_plan(p, K, d.per, measure);
   char *hb, *db;
-  rc = h->staging.acquire(total, &hb, &db); if (rc) return rc;
-  memcpy(hb + o_env, p.sample_env.data(), sizeof(int32_t) * K);
-  memcpy(hb + o_off, p.sample_off.data(), sizeof(int64_t) * K);
-  if (!p.table_ops.empty()) memcpy(hb + o_tab, p.table_ops.data(), sizeof(TableOp) * p.table_ops.size());
-  if (!p.env_ops.empty()) memcpy(hb + o_eop, p.env_ops.data(), sizeof(EnvOp) * p.env_ops.size());
-  if (!p.leaf_ops.empty()) memcpy(hb + o_lop, p.leaf_ops.data(), sizeof(LeafOp) * p.leaf_ops.size());
-  rc = h->staging.upload(total, st); if (rc) return rc;
-  const int32_t* s_env = (const int32_t*)(db + o_env);
-  const int64_t* s_off = (const int64_t*)(db + o_off);
-  if ((g_ingest_fused && !d.planes && !(h->book.cfg.acting_priority_init && d.per)) || (d.planes && in->newest_plane_only)) {
-    const IngestSrc src = make_ingest_src(d, in);
-    const int32_t f_row = src.row_bytes;
-    const int nt = d.per ? (int)p.table_ops.size() : 0, ne = (int)p.env_ops.size(), nl = d.per ? (int)p.leaf_ops.size() : 0;
-    // 16 KB per copy workgroup: a (4, 84, 84) frame row takes 2
-    int parts = (int)((f_row + 16383) / 16384); if (parts < 1) parts = 1; if (parts > 8) parts = 8;
-    {
-      ProfScope ps("k_ingest_fused", 2.0 * K * ((double)f_row + 4.0 * (d.X + d.S + d.A) + 13 + (d.per ? 16 : 0)), st);
-      hipLaunchKernelGGL(k_ingest_fused, dim3(parts, K + 1), dim3(1024), 0, st, d, K, src, s_env, s_off, nt, (const TableOp*)(db + o_tab),
-                         ne, (const EnvOp*)(db + o_eop), nl, (const LeafOp*)(db + o_lop));
-    }
-    MIRL_LAUNCH_CHECK();
-    return h->staging.mark(st);
-  }
-  if (d.planes) {
-    // de-dup: verify the stack-shift contract against the stored planes, record the
-    // depth, keep the newest plane only
+  rc = h->staging.acquire(measure.size, &hb, &db); if (rc) return rc;
+  PlanSink block{hb, measure.size, 0};
+  const PlanHdr hd = pack_plan(p, K, d.per, block);
+  rc = h->staging.upload(block.size, st); if (rc) return rc;
+  const int32_t* s_env = (const int32_t*)(db + hd.o_env);
+  const int64_t* s_off = (const int64_t*)(db + hd.o_off);
+  if (d.planes && !in->newest_plane_only) {
+    // de-dup fed whole stacks: verify the stack-shift contract against the stored planes and record the depth;
+    // the ingest launch then keeps the newest plane only
     {
       ProfScope ps("k_dedup_depth", (double)K * (2.0 * d.F - d.plane_bytes), st);
       hipLaunchKernelGGL(k_dedup_depth, dim3(K), dim3(256), 0, st, d, in->frames, s_env, s_off);
     }
     MIRL_LAUNCH_CHECK();
-    rc = scatter(h, in->frames + (size_t)(d.planes - 1) * d.plane_bytes, d.frames, s_env, s_off, K, d.plane_bytes, d.plane_bytes, st, d.F);
-    if (rc) return rc;
-  } else {
-    rc = scatter(h, in->frames, d.frames, s_env, s_off, K, d.F, d.Fp, st); if (rc) return rc;
   }
-  rc = scatter(h, in->extra, d.extra, s_env, s_off, K, d.X * 4, (int64_t)d.X * 4, st); if (rc) return rc;
-  rc = scatter(h, in->state, d.state, s_env, s_off, K, d.S * 4, (int64_t)d.S * 4, st); if (rc) return rc;
-  rc = scatter(h, in->policy, d.policy, s_env, s_off, K, d.A * 4, (int64_t)d.A * 4, st); if (rc) return rc;
-  {
-    ProfScope ps("k_ingest_scalars", 2.0 * K * (13 + (d.per ? 16 : 0)), st);
-    hipLaunchKernelGGL(k_ingest_scalars, dim3((K + 255) / 256), dim3(256), 0, st, d, K, s_env, s_off,
-                       in->initials, in->actions, in->rewards, in->dones);
-  }
-  MIRL_LAUNCH_CHECK();
-  int nt = (int)p.table_ops.size(), ne = (int)p.env_ops.size(), nl = d.per ? (int)p.leaf_ops.size() : 0;
-  if (!d.per) nt = 0;
-  int nmax = nt > ne ? nt : ne; nmax = nl > nmax ? nl : nmax;
-  if (nmax) {
-    ProfScope ps("k_plan_apply", 0.0, st);
-    hipLaunchKernelGGL(k_plan_apply, dim3((nmax + 255) / 256), dim3(256), 0, st, d, nt, (const TableOp*)(db + o_tab),
-                       ne, (const EnvOp*)(db + o_eop), nl, (const LeafOp*)(db + o_lop));
-    MIRL_LAUNCH_CHECK();
-  }
-  if (nl) { ProfScope ps("k_tree_fix(ingest)", 0.0, st); hipLaunchKernelGGL(k_tree_fix, dim3(1), dim3(1024), 0, st, d); MIRL_LAUNCH_CHECK(); }
-  if (h->book.cfg.acting_priority_init && d.per) {
+  rc = launch_ingest(h, in, st, [&](dim3 grid, dim3 block_dim, const IngestSrc& src) {
+    hipLaunchKernelGGL(k_ingest_fused, grid, block_dim, 0, st, d, K, src, s_env, s_off, hd.n_table, (const TableOp*)(db + hd.o_tab),
+                       hd.n_env, (const EnvOp*)(db + hd.o_eop), hd.n_leaf, (const LeafOp*)(db + hd.o_lop));
+  });
+  if (rc) return rc;
+  if (acting_td) {
     // TD errors of the transitions whose n-step target just became available, from
     // stored q-values, through the update_losses path (see mirl_replay_config)
     if (h->td_cap < K) {
@@ -1253,13 +1186,13 @@ extern "C" int mirl_replay_ingest(mirl_replay* h, const mirl_ingest* in, void* s
 // changes; mirl_replay_ingest_planned enqueues the device side of ONE of those steps with no host argument that
 // varies from rollout to rollout — the call a HIP graph of the whole rollout captures (acting/fast_step.py).
 static bool planned_ingest_ok(mirl_replay* h) {
-  return g_ingest_fused && !h->d.planes && !(h->book.cfg.acting_priority_init && h->d.per);
+  return !h->d.planes && !(h->book.cfg.acting_priority_init && h->d.per);    // both put launches of their own around the ingest
 }
 
 extern "C" int mirl_replay_ingest_plan(mirl_replay* h, int32_t steps, int32_t count, const int32_t* env_ids_host, void* stream) {
   if (!h || steps <= 0 || steps > 4096 || count <= 0 || count > 65535) return fail(MIRL_ERR_ARG, "bad ingest_plan arguments");
   if (h->book_broken) return fail(MIRL_ERR_STATE, "this shard's host bookkeeping ran ahead of its device rows (an earlier ingest_plan failed half-way); the shard is unusable");
-  if (!planned_ingest_ok(h)) return fail(MIRL_ERR_ARG, "planned ingest needs the fused ingest kernel (no de-duplicated storage, no acting_priority_init)");
+  if (!planned_ingest_ok(h)) return fail(MIRL_ERR_ARG, "planned ingest covers neither de-duplicated storage nor acting_priority_init");
   hipStream_t st = (hipStream_t)stream;
   const int K = count;
   // Transactional: EVERYTHING that can refuse the call — arguments, buffer sizes, the staging block — is settled before
@@ -1295,36 +1228,19 @@ extern "C" int mirl_replay_ingest_plan(mirl_replay* h, int32_t steps, int32_t co
   const size_t worst = hdr_bytes + per_step_bytes(K) * (size_t)steps;      // <= roll_cap by construction
   char *hb, *db;
   int rc = h->staging.acquire(worst, &hb, &db); if (rc) return rc;
-  std::vector<char>& buf = h->roll_host;
-  buf.assign(hdr_bytes, 0);
-  auto put = [&buf](const void* src, size_t bytes) -> int64_t {
-    const size_t at = align_up(buf.size(), 16);
-    buf.resize(at + bytes);
-    if (bytes) memcpy(buf.data() + at, src, bytes);
-    return (int64_t)at;
-  };
+  memset(hb, 0, hdr_bytes);
+  PlanSink block{hb, worst, hdr_bytes};
   // whatever failed, the caller sees MIRL_ERR_STATE from here on (never MIRL_ERR_ARG, which means "refused before
   // anything moved, fall back to per-step ingest"): the message of the original failure stays in mirl_last_error()
   auto broken = [h](int) -> int { h->book_broken = true; return MIRL_ERR_STATE; };
   for (int s = 0; s < steps; ++s) {
     rc = h->book.ingest(K, env_ids_host, h->plan);
     if (rc) { last_error_ref() = h->book.err; return broken(rc); }     // a reference assert (ring overflow, no free index): fatal anyway
-    const Plan& p = h->plan;
-    PlanHdr hd;
-    hd.n_table = h->d.per ? (int32_t)p.table_ops.size() : 0;
-    hd.n_env = (int32_t)p.env_ops.size();
-    hd.n_leaf = h->d.per ? (int32_t)p.leaf_ops.size() : 0;
-    hd.pad = 0;
-    hd.o_env = put(p.sample_env.data(), sizeof(int32_t) * K);
-    hd.o_off = put(p.sample_off.data(), sizeof(int64_t) * K);
-    hd.o_tab = put(p.table_ops.data(), sizeof(TableOp) * p.table_ops.size());
-    hd.o_eop = put(p.env_ops.data(), sizeof(EnvOp) * p.env_ops.size());
-    hd.o_lop = put(p.leaf_ops.data(), sizeof(LeafOp) * p.leaf_ops.size());
-    memcpy(buf.data() + sizeof(PlanHdr) * (size_t)s, &hd, sizeof(PlanHdr));
+    const PlanHdr hd = pack_plan(h->plan, K, h->d.per, block);
+    memcpy(hb + sizeof(PlanHdr) * (size_t)s, &hd, sizeof(PlanHdr));
   }
-  const size_t total = align_up(buf.size(), 16);
+  const size_t total = block.size;
   if (total > worst || total > h->roll_cap) return broken(fail(MIRL_ERR_STATE, "ingest_plan: the rollout's op lists exceed their worst-case bound (library bug)"));
-  memcpy(hb, buf.data(), buf.size());
   rc = h->staging.upload(total, st); if (rc) return broken(rc);
   if (hipMemcpyAsync(h->roll_plan, db, total, hipMemcpyDeviceToDevice, st) != hipSuccess)     // stream order: after the last rollout that read it
     return broken(fail(MIRL_ERR_HIP, "ingest_plan: copy into the rollout-plan buffer failed"));
@@ -1334,23 +1250,15 @@ extern "C" int mirl_replay_ingest_plan(mirl_replay* h, int32_t steps, int32_t co
 }
 
 extern "C" int mirl_replay_ingest_planned(mirl_replay* h, int32_t step, const mirl_ingest* in, void* stream) {
-  if (h && h->book_broken) return fail(MIRL_ERR_STATE, "this shard's host bookkeeping ran ahead of its device rows (an ingest_plan failed half-way); the shard is unusable");
-  if (!h || !in || in->count <= 0 || step < 0) return fail(MIRL_ERR_ARG, "bad ingest_planned arguments");
+  const int rc = check_ingest_args(h, in); if (rc) return rc;
+  if (step < 0) return fail(MIRL_ERR_ARG, "bad ingest_planned arguments");
   if (!h->roll_plan || step >= h->roll_cap_steps) return fail(MIRL_ERR_STATE, "ingest_planned: no rollout plan covers this step (call mirl_replay_ingest_plan first)");
-  if (!planned_ingest_ok(h) || in->newest_plane_only) return fail(MIRL_ERR_ARG, "planned ingest needs the fused ingest kernel (no de-duplicated storage, no acting_priority_init)");
-  Dev& d = h->d;
-  const int K = in->count;
-  if (K != h->roll_count) return fail(MIRL_ERR_ARG, "ingest_planned: transition count differs from the plan's");
-  if (!in->frames || !in->actions || !in->rewards || !in->dones) return fail(MIRL_ERR_ARG, "frames/actions/rewards/dones are required");
-  if ((d.X && !in->extra) || (d.S && !in->state) || (d.has_init && !in->initials) || (d.A && !in->policy))
-    return fail(MIRL_ERR_ARG, "a configured payload array is NULL");
+  if (!planned_ingest_ok(h) || in->newest_plane_only) return fail(MIRL_ERR_ARG, "planned ingest covers neither de-duplicated storage nor acting_priority_init");
+  if (in->count != h->roll_count) return fail(MIRL_ERR_ARG, "ingest_planned: transition count differs from the plan's");
   hipStream_t st = (hipStream_t)stream;
-  const IngestSrc src = make_ingest_src(d, in);
-  int parts = (int)((src.row_bytes + 16383) / 16384); if (parts < 1) parts = 1; if (parts > 8) parts = 8;
-  ProfScope ps("k_ingest_fused", 2.0 * K * ((double)src.row_bytes + 4.0 * (d.X + d.S + d.A) + 13 + (d.per ? 16 : 0)), st);
-  hipLaunchKernelGGL(k_ingest_fused_planned, dim3(parts, K + 1), dim3(1024), 0, st, d, K, src, (const char*)h->roll_plan, (int)step);
-  MIRL_LAUNCH_CHECK();
-  return MIRL_OK;
+  return launch_ingest(h, in, st, [&](dim3 grid, dim3 block_dim, const IngestSrc& src) {
+    hipLaunchKernelGGL(k_ingest_fused_planned, grid, block_dim, 0, st, h->d, in->count, src, (const char*)h->roll_plan, (int)step);
+  });
 }
 
 extern "C" int mirl_replay_needed_feed_count(mirl_replay* h, int32_t mbatch, int32_t num_envs, int64_t* out) {

@@ -120,34 +120,6 @@ def test_direct_ingest_equals_tensor_hand_over(per):
             assert np.array_equal(x, y)
 
 
-def test_fused_ingest_kernel_equals_the_separate_kernels():
-    """mirl_replay_ingest as ONE launch against the scatter / scalars / plan / tree-fix launches of
-    rounds 1-2 on a ragged prioritized stream with evictions: identical shards."""
-    from rltime_amd._lib import lib, check
-    from rltime_amd.history import PrioritizedReplayHistoryBuffer
-    from tests.golden.streams import StreamSpec, vector_steps, as_reference_samples
-    res = []
-    try:
-        for fused in (1, 0):
-            check(lib.mirl_ingest_fused_set(fused))
-            spec = StreamSpec(seed=12, num_envs=6, frame_shape=(2, 9, 7), lstm_units=4, n_actions=3, done_prob=0.1)
-            buf = PrioritizedReplayHistoryBuffer(size=90, train_frequency=0, nstep_target=2, nstep_train=4, prefix_steps=1,
-                                                 alpha=0.8, beta=0.5, gamma=0.97, device_rng=True)
-            for st in vector_steps(spec, 60):
-                buf.update(as_reference_samples(spec, st))
-            batch = buf.get_train_data(5, train_progress=0.3)
-            res.append((batch, buf.stats(), buf.tree_nodes(), buf.free_slots(), buf.slot_table()))
-            buf.close()
-    finally:
-        check(lib.mirl_ingest_fused_set(1))
-    (ba, sa, ta, fa, la), (bb, sb, tb, fb, lb) = res
-    assert sa == sb and np.array_equal(fa, fb) and all(np.array_equal(x, y) for x, y in zip(la, lb))
-    assert all(np.array_equal(x, y) for x, y in zip(ta, tb))
-    flat = lambda tree: [tree] if isinstance(tree, torch.Tensor) else [x for v in (tree.values() if isinstance(tree, dict) else tree) for x in flat(v)] if tree is not None else []   # noqa: E731
-    for x, y in zip(flat(ba), flat(bb)):
-        assert torch.equal(x, y)
-
-
 def test_in_kernel_quantile_fractions():
     """mirl_cos_embed_rng: tau ~ U[0, 1) drawn in the kernel (Philox keyed by seed, step, row) and the
     cos features of exactly those taus (iqn.py:76-81); a new step draws new fractions."""

@@ -309,6 +309,87 @@ def test_frame_dedup_rejects_frames_that_break_the_stack_contract():
         b2.update(as_reference_samples(s2, next(vector_steps(s2, 1))))
 
 
+# Streams of tests/golden/ingest_separate_kernels.npz (docs/parity.md, "Ingest: the recorded separate kernels"): what the
+# row-scatter / scalars / plan / tree-fix launches of the ingest left behind, recorded before they were retired.  `every`:
+# also record after every `every`-th vector step, not only after the last.
+_ATD = dict(size=6 * 40, train_frequency=0, alpha=0.7, beta=0.5, max_weight_factor=0.9, gamma=0.97, device_rng=True,
+            acting_priority_init=True)
+_ATD_SPEC = dict(num_envs=6, frame_shape=(1, 8, 8), n_actions=5, done_prob=0.08)
+INGEST_STREAMS = {
+    # 126-byte frame rows take the byte-loop copy, the 32-byte state rows the 16 B copy; PER with evictions
+    "a": dict(spec=dict(seed=12, num_envs=6, frame_shape=(2, 9, 7), lstm_units=4, n_actions=3, done_prob=0.1), per=True,
+              hist=dict(size=90, train_frequency=0, nstep_target=2, nstep_train=4, prefix_steps=1, alpha=0.8, beta=0.5,
+                        gamma=0.97, device_rng=True),
+              steps=60, batch=5, progress=0.3, every=0),
+    # 28224-byte frame rows: two copy workgroups per row, 16 B lanes, stored q-values
+    "b": dict(spec=dict(seed=14, num_envs=3, frame_shape=(4, 84, 84), n_actions=6, done_prob=0.1), per=False,
+              hist=dict(size=30, train_frequency=0, nstep_target=2, nstep_train=2, prefix_steps=0, gamma=0.99,
+                        device_rng=True, seed=141, keep_policy_outputs=True),
+              steps=12, batch=2, progress=None, every=0),
+    # verifying de-dup, uniform: resets inside an env's first steps (virtual predecessors)
+    "c": dict(spec=dict(seed=53, num_envs=12, frame_shape=(4, 8, 8), n_actions=4, done_prob=0.35, stacked=True), per=False,
+              hist=dict(size=600, train_frequency=0, nstep_target=2, nstep_train=2, prefix_steps=0, gamma=0.99,
+                        device_rng=True, seed=531, frame_stack_dedup=True),
+              steps=55, batch=24, progress=None, every=0),
+    # verifying de-dup under PER sequence replay with recurrent state, evictions
+    "d": dict(spec=dict(seed=57, num_envs=6, frame_shape=(4, 8, 8), lstm_units=4, n_actions=4, done_prob=0.1, stacked=True),
+              per=True,
+              hist=dict(size=120, train_frequency=0, nstep_target=2, nstep_train=4, prefix_steps=2, alpha=0.8, beta=0.5,
+                        gamma=0.97, device_rng=True, seed=571, frame_stack_dedup=True),
+              steps=60, batch=4, progress=0.3, every=7),
+    # acting_priority_init: the (T, P, n, vf) = (8, 4, 2, 1e-3) and (1, 0, 3, None) cases of the oracle test above
+    "e-T8": dict(spec=dict(seed=70 + 8 + 2, lstm_units=4, **_ATD_SPEC), per=True,
+                 hist=dict(nstep_target=2, nstep_train=8, prefix_steps=4, acting_priority_vf_eps=1e-3, seed=701, **_ATD),
+                 steps=40, batch=4, progress=0.3, every=7),
+    "e-T1": dict(spec=dict(seed=70 + 1 + 3, lstm_units=0, **_ATD_SPEC), per=True,
+                 hist=dict(nstep_target=3, nstep_train=1, prefix_steps=0, acting_priority_vf_eps=None, seed=702, **_ATD),
+                 steps=40, batch=4, progress=0.3, every=7),
+}
+
+
+def run_ingest_stream(name):
+    """One stream of INGEST_STREAMS -> {key: array} of what it leaves: stats(), the PER bookkeeping and every tree node
+    (value, kind, min), and every tensor of one get_train_data batch, at each recording point."""
+    from rltime_amd.history import ReplayHistoryBuffer, PrioritizedReplayHistoryBuffer
+    cfg = INGEST_STREAMS[name]
+    spec = StreamSpec(**cfg["spec"])
+    buf = (PrioritizedReplayHistoryBuffer if cfg["per"] else ReplayHistoryBuffer)(**cfg["hist"])
+    out = {}
+    for i, st in enumerate(vector_steps(spec, cfg["steps"]), start=1):
+        buf.update(as_reference_samples(spec, st))
+        if i != cfg["steps"] and not (cfg["every"] and i % cfg["every"] == 0):
+            continue
+        tag = "%s.s%03d." % (name, i)
+        for k, v in buf.stats().items():
+            out[tag + "stats." + k] = np.int64(v)
+        if cfg["per"]:
+            out[tag + "free_slots"] = buf.free_slots()
+            out[tag + "slot_env"], out[tag + "slot_base"] = buf.slot_table()
+            out[tag + "tree_value"], out[tag + "tree_kind"], out[tag + "tree_min"] = buf.tree_nodes()
+        batch = buf.get_train_data(cfg["batch"], train_progress=cfg["progress"])
+        out[tag + "batch_is_none"] = np.bool_(batch is None)
+        for k, v in scenario.flatten("", batch or {}, {}).items():
+            out[tag + "batch." + k] = scenario.to_numpy(v)
+    buf.close()
+    return out
+
+
+@pytest.mark.parametrize("name", sorted(INGEST_STREAMS))
+def test_ingest_leaves_what_the_separate_kernels_left(name):
+    """The one-launch ingest (k_ingest_fused; behind k_dedup_depth for verified whole stacks, ahead of k_acting_td for
+    acting_priority_init) against the recorded result of the five to seven launches per vector step it replaced (row
+    scatters, scalars, plan, tree fix): bookkeeping, every tree node and every tensor of the sampled batches, bit for bit."""
+    import os
+    gold = np.load(os.path.join(scenario.GOLDEN, "ingest_separate_kernels.npz"))
+    want = {k: gold[k] for k in gold.files if k.startswith(name + ".")}
+    got = run_ingest_stream(name)
+    assert want and set(got) == set(want), sorted(set(got) ^ set(want))
+    assert any(k.endswith("batch.states.x") for k in want)
+    for k, w in want.items():
+        g = np.asarray(got[k])
+        assert g.dtype == w.dtype and np.array_equal(g, w), k
+
+
 def _philox_u53(seed, call, lane):
     """Philox4x32-10 (Salmon et al., SC'11) keyed (seed lo, seed hi), counter
     (lane, call lo, call hi, tag) -> 53-bit uniform: an independent restatement of
