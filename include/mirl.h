@@ -1016,6 +1016,66 @@ int mirl_replay_update_losses_guarded(mirl_replay* h, int64_t count, const int64
  * word is unchanged.                                                                                                */
 int mirl_lstm_seq_status_device(const int32_t** p);
 
+/* ---- actor-critic (A2C / PPO) on the device (csrc/actor_critic.hip) ---------------------------------------------------
+ * Three latency-sized kernels.  No float atomics, every sum in a fixed order: a second call repeats the first bit for
+ * bit.  All take the caller's stream, none synchronises, all can be captured; bad arguments are MIRL_ERR_ARG before
+ * any launch.
+ *
+ * The log-probability of action a of a row z[0..A) is formed by ONE sequence of operations in the head and in the loss:
+ *   zmax = max_j z_j                        float32 comparisons, the first maximum
+ *   d_j  = double(z_j) - double(zmax)       float64 (exact)
+ *   S    = sum_j exp(d_j)                   float64 exp, float64 sum in ascending j
+ *   logp = float32(d_a - log(S))            float64 log and difference, ONE rounding to float32
+ * so a row the loss re-evaluates with unchanged weights gives the head's float32 back, and the PPO ratio
+ * exp(double(logp) - double(old_logp)) is exactly 1.
+ *
+ * The sampling head of one vector step (rltime/policies/torch/actor_critic.py:37-71), one launch: logits [E] rows of A
+ * floats, `pitch` floats apart; values [E]; u [E] float32 uniforms in [0, 1) (NULL allowed with greedy).  The sampled
+ * action is the smallest a with  double(u) * S < sum_{j <= a} exp(d_j)  (float64; the partial sums are formed like S, no
+ * division; the last action is the fallback); with greedy = 1 it is the first maximum of the logits (force_best).
+ * actions [E] int32; the log-probability and a copy of the value of env e go to action_log_probs[e * out_pitch] and
+ * values_out[e * out_pitch], so that both may be columns of one [E][2] block.  1 <= A <= 64, 1 <= E <= 2^24.         */
+int mirl_actor_head_ac(int32_t E, int32_t A, const float* logits, int64_t pitch, const float* values, const float* u,
+                       int32_t greedy, int32_t* actions, float* action_log_probs, float* values_out, int32_t out_pitch,
+                       void* stream);
+/* The (T, B) training window of the on-policy history (rltime/history/online_history.py:81-120 over history.py:71-201,
+ * fixed_target = True) from device rings of whole vector steps.  Ring slot s holds, for each of the E envs, what the
+ * transition of that vector step stored: obs_ring [cap][E][obs_bytes] its next_state (uint8 frames or float32 vectors,
+ * moved as bytes), actions_ring / rewards_ring / dones_ring [cap][E], and the acting-time policy outputs at
+ * logp_ring / values_ring [(s * E + env) * pol_pitch].  plan [B][3] (device int32): the env of sequence b, the ring slot
+ * of its first transition, and 1 when that transition is the env's first ever (it then starts from its own next_state;
+ * every other transition starts from the next_state one slot earlier, which the caller keeps in the ring: cap >= T + 1
+ * slots behind a sequence unless the flag is set).  Transition i = t of sequence b covers n = min(nstep_target, T - t)
+ * steps (the window bounds the horizon; steps covered and the target index advance whatever the dones are):
+ *   returns[t][b]      = float32( r_i + sum_{k=1}^{n-1} [no done among i .. i+k-1]
+ *                                  (gamma^k * lam^(k-1)) * (v_{i+k} + lam * (r_{i+k} - v_{i+k})) )
+ *                        (rltime/training/torch/a2c.py:48-66) — float64 pow, products and sum in ascending k, ONE rounding
+ *   nsteps[t][b] = n,  target_masks[t][b] = 0 when any of i .. i+n-1 is done, else 1     (float32)
+ *   actions / action_log_probs / values [t][b]: the transition's own;  states[t][b]: the next_state one slot before it;
+ *   target_states[t][b]: the next_state of transition i + n - 1.
+ * One workgroup per (t, b); T * B <= 2^24.                                                                             */
+int mirl_online_window(int32_t T, int32_t B, int32_t E, int32_t cap, int32_t nstep_target, double gamma, double lam,
+                       int64_t obs_bytes, const int32_t* plan, const void* obs_ring, const int32_t* actions_ring,
+                       const float* rewards_ring, const uint8_t* dones_ring, const float* logp_ring, const float* values_ring,
+                       int32_t pol_pitch, float* returns, float* nsteps, float* target_masks, int32_t* actions,
+                       float* action_log_probs, float* values, void* states, void* target_states, void* stream);
+/* The A2C / PPO loss with both gradients in ONE launch of one workgroup (rltime/training/torch/a2c.py:101-141,
+ * ppo.py:39-56).  M rows: logits [M][A] (`pitch` floats apart), values, actions (int32 in [0, A); anything else is
+ * clamped into the row), targets, acting_values [M]; old_log_probs [M] or NULL = the A2C gain.
+ *   adv  = targets - acting_values;  with adv_norm: (adv - mean) / (std + 1e-5), the unbiased std (M >= 2)
+ *   gain = mean(logp * adv)   or   mean(min(ratio * adv, clamp(ratio, 1 - clip_value, 1 + clip_value) * adv))
+ *   loss = vf_coef * mean((targets - values)^2) - gain - entropy_factor * mean(entropy)
+ * Everything is float64 on the float32 inputs (logp as above and then used as the float32 it rounds to; entropy =
+ * log S - sum_j exp(d_j) d_j / S), sums per thread in ascending rows and then in a fixed tree, one rounding per output.
+ * dlogits [M][A] (`dpitch` apart) and dvalues [M]: the gradient of the loss.  The PPO gain's gradient follows
+ * autograd: inside [1 - c, 1 + c], bounds included, ratio * adv flows in full; where the clamped term is strictly the
+ * smaller one the row's policy gradient is 0.  log_probs [M] (may be NULL): logp of the rows' actions.
+ * stats [5] = loss, value loss, policy loss (-gain), mean entropy, mean value.  1 <= A <= 64, 1 <= M <= 2^22.       */
+int mirl_ac_loss(int64_t M, int32_t A, const float* logits, int64_t pitch, const float* values, const int32_t* actions,
+                 const float* targets, const float* acting_values, const float* old_log_probs, double vf_coef,
+                 double entropy_factor, double clip_value, int32_t adv_norm, float* dlogits, int64_t dpitch, float* dvalues,
+                 float* log_probs, float* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,7 +133,8 @@ class Actor(ActingInterface):
         self._policy = actor_policy
         obs = self._vec_env.reset()
         self._reset_obs = obs
-        self._fast = None
+        # (actor-critic policies take the generic device path and its GraphedStep, never the fused Q-learning step)
+        self._fast = False if hasattr(actor_policy, "actor_head_ac_raw") else None
         self.last_state = actor_policy.make_input_state(obs, np.array([True] * self._num_envs))
 
     def set_sink(self, history, clip_rewards=False):
@@ -230,6 +231,8 @@ class Actor(ActingInterface):
         (csrc/acting.hip k_actor_head) when the policy exposes its raw head outputs.
         `eps`: 0-dim float64 device tensor holding the base epsilon (None = greedy)."""
         pol = self._policy
+        if hasattr(pol, "actor_head_ac_raw"):
+            return self._select_ac(state)
         expl = self._exploration
         fused = getattr(self, "fused_head", True) and hasattr(pol, "actor_head_raw") and pol.is_cuda() \
             and (expl is None or hasattr(expl, "_device_exponents"))
@@ -267,6 +270,22 @@ class Actor(ActingInterface):
                                   p(eps if expl is not None else None), p(expo), eps_min, p(u), p(rnd),
                                   p(actions), p(qvalues), None, stream()), "mirl_actor_head")
         return actions, qvalues
+
+    def _select_ac(self, state):
+        """The actor-critic vector step (policies/torch/actor_critic.py:37-71): policy forward -> one launch of the
+        sampling head (csrc/actor_critic.hip k_actor_head_ac) -> (actions, block) with block [E][2] = [log-probability |
+        value] where the Q-learning path returns its q-values, so the vector steps carry both policy outputs to the
+        history.  The policy samples for itself: exploration configs are ignored, as in the reference."""
+        from rltime_amd._lib import lib, check, ptr as p, stream
+        logits, values = self._policy.actor_head_ac_raw(state, 1)
+        E, A = logits.shape
+        dev = logits.device
+        u = torch.rand(E, device=dev)
+        actions = torch.empty(E, dtype=torch.int32, device=dev)
+        block = torch.empty((E, 2), dtype=torch.float32, device=dev)
+        check(lib.mirl_actor_head_ac(E, A, p(logits), logits.stride(0), p(values), p(u), 0, p(actions), p(block), p(block[:, 1]), 2,
+                                     stream()), "mirl_actor_head_ac")
+        return actions, block
 
     def _fast_steps(self, iters):
         """The fused vector step (acting/fast_step.py)."""

@@ -1,0 +1,276 @@
+// actor_critic.hip — the actor-critic (A2C / PPO) part of the device path: the sampling head of a vector step, the
+// on-policy rollout window with its lambda-returns, and the loss with its gradients (include/mirl.h has the contracts).
+// All three are latency-sized: a few thousand rows of at most 64 actions.  Plain C++, float64 inside, one rounding to
+// float32 per output; no float atomics, every sum in a fixed order, so a rerun repeats the first run bit for bit.
+#include "common.hpp"
+
+namespace mirl {
+
+// ---- the softmax pieces both the head and the loss use: the SAME sequence of operations in both --------------------
+// zmax = max_j z_j (float32 compare, first maximum), d_j = double(z_j) - double(zmax) (exact), e_j = exp(d_j),
+// S = sum_j e_j in ascending j, log-probability of action a = d_a - log(S), rounded once to float32.
+struct RowSoftmax { float zmax; int first; double S, W; };    // W = sum_j e_j d_j (the loss's entropy needs it)
+
+__device__ inline RowSoftmax row_softmax(const float* __restrict__ z, int A) {
+  RowSoftmax r;
+  r.zmax = z[0]; r.first = 0;
+  for (int j = 1; j < A; ++j) { const float v = z[j]; if (v > r.zmax) { r.zmax = v; r.first = j; } }
+  r.S = 0.0; r.W = 0.0;
+  for (int j = 0; j < A; ++j) {
+    const double d = (double)z[j] - (double)r.zmax;
+    const double e = exp(d);
+    r.S += e;
+    r.W += e * d;
+  }
+  return r;
+}
+
+__device__ inline float row_log_prob(const float* __restrict__ z, int a, const RowSoftmax& r, double logS) {
+  return (float)(((double)z[a] - (double)r.zmax) - logS);
+}
+
+// ---- 1. the sampling head ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_actor_head_ac(int E, int A, const float* __restrict__ logits, long pitch,
+                                                      const float* __restrict__ values, const float* __restrict__ u, int greedy,
+                                                      int* __restrict__ actions, float* __restrict__ logp, float* __restrict__ values_out,
+                                                      int out_pitch) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= E) return;
+  const float* z = logits + (long)e * pitch;
+  const RowSoftmax r = row_softmax(z, A);
+  int a = r.first;
+  if (!greedy) {
+    // inverse CDF without a division: the smallest a with u S < sum_{j <= a} e_j; the partial sums are formed exactly as S was
+    const double want = (double)u[e] * r.S;
+    double cum = 0.0;
+    a = A - 1;
+    for (int j = 0; j < A; ++j) {
+      cum += exp((double)z[j] - (double)r.zmax);
+      if (want < cum) { a = j; break; }
+    }
+  }
+  actions[e] = a;
+  logp[(long)e * out_pitch] = row_log_prob(z, a, r, log(r.S));
+  values_out[(long)e * out_pitch] = values[e];
+}
+
+// ---- 2. the on-policy window ---------------------------------------------------------------------------------------
+// One workgroup per (t, sequence): thread 0 walks the transition's return, all threads move its two observation rows.
+struct WindowArgs {
+  int T, B, E, cap, nstep_target;
+  double gamma, lam;
+  long obs_bytes;
+  const int* plan;                 // [B][3]: env, ring slot of the sequence's first transition, 1 = that transition is the env's first ever
+  const unsigned char* obs_ring;   // [cap][E][obs_bytes]: next_state of the transition
+  const int* actions_ring;         // [cap][E]
+  const float* rewards_ring;
+  const unsigned char* dones_ring;
+  const float* logp_ring;          // [(slot E + env) pol_pitch]
+  const float* values_ring;
+  int pol_pitch;
+  float *returns, *nsteps, *masks;
+  int* actions;
+  float *logp, *values;
+  unsigned char *states, *target_states;
+  int vec16;
+};
+
+__device__ inline void copy_row(unsigned char* __restrict__ dst, const unsigned char* __restrict__ src, long bytes, int vec16) {
+  if (vec16) {
+    const uint4* s = (const uint4*)src;
+    uint4* d = (uint4*)dst;
+    for (long q = threadIdx.x; q < bytes / 16; q += blockDim.x) d[q] = s[q];
+  } else {
+    for (long q = threadIdx.x; q < bytes; q += blockDim.x) dst[q] = src[q];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_online_window(WindowArgs a) {
+  const int b = blockIdx.x % a.B, t = blockIdx.x / a.B;
+  const int env = a.plan[3 * b], first = a.plan[3 * b + 1], own = a.plan[3 * b + 2];
+  // fixed_target: no target looks past the window (history.py:187-190); the steps covered advance whatever the dones are
+  const int want = min(a.nstep_target, a.T - t);
+  const long out = (long)t * a.B + b;
+  auto at = [&](int i) { return (long)((first + i) % a.cap) * a.E + env; };     // ring row of the sequence's transition i
+  if (threadIdx.x == 0) {
+    const long r0 = at(t);
+    double ret = (double)a.rewards_ring[r0];
+    float mask = a.dones_ring[r0] ? 0.f : 1.f;
+    for (int k = 1; k < want; ++k) {
+      const long rj = at(t + k);
+      if (mask != 0.f) {
+        const double v = (double)a.values_ring[rj * a.pol_pitch], r = (double)a.rewards_ring[rj];
+        ret += (pow(a.gamma, (double)k) * pow(a.lam, (double)(k - 1))) * (v + a.lam * (r - v));
+      }
+      if (a.dones_ring[rj]) mask = 0.f;
+    }
+    a.returns[out] = (float)ret;
+    a.nsteps[out] = (float)want;
+    a.masks[out] = mask;
+    a.actions[out] = a.actions_ring[r0];
+    a.logp[out] = a.logp_ring[r0 * a.pol_pitch];
+    a.values[out] = a.values_ring[r0 * a.pol_pitch];
+  }
+  // the transition starts from the previous vector step's next_state (an env's very first one from its own)
+  const long s_row = (t == 0 && own) ? at(0) : (long)((first + t - 1 + a.cap) % a.cap) * a.E + env;
+  copy_row(a.states + out * a.obs_bytes, a.obs_ring + s_row * a.obs_bytes, a.obs_bytes, a.vec16);
+  copy_row(a.target_states + out * a.obs_bytes, a.obs_ring + at(t + want - 1) * a.obs_bytes, a.obs_bytes, a.vec16);
+}
+
+// ---- 3. the loss ---------------------------------------------------------------------------------------------------
+// ONE workgroup: thread i takes rows i, i + 1024, ... in ascending order into float64 accumulators, the workgroup adds
+// them in a fixed tree.  M is a few thousand rows (16 envs x 128 steps), so one compute unit is enough and the whole
+// loss — advantage statistics, forward, both gradients, the logged scalars — is one launch.
+constexpr int kLossThreads = 1024;
+
+__device__ inline double block_sum(double v, double* lds) {
+  __syncthreads();
+  lds[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = kLossThreads / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) lds[threadIdx.x] += lds[threadIdx.x + s];
+    __syncthreads();
+  }
+  return lds[0];
+}
+
+struct LossArgs {
+  long M; int A;
+  const float* logits; long pitch;
+  const float* values; const int* actions; const float* targets; const float* acting_values; const float* old_log_probs;
+  double vf_coef, entropy_factor, clip_value; int adv_norm;
+  float* dlogits; long dpitch; float* dvalues; float* log_probs; float* stats;
+};
+
+__global__ __launch_bounds__(kLossThreads) void k_ac_loss(LossArgs a) {
+  __shared__ double lds[kLossThreads];
+  const double invM = 1.0 / (double)a.M;
+  double mean = 0.0, denom = 1.0;
+  if (a.adv_norm) {
+    // torch: (adv - adv.mean()) / (adv.std() + 1e-5), the unbiased std; two passes, the second on the centred values
+    double s = 0.0;
+    for (long i = threadIdx.x; i < a.M; i += kLossThreads) s += (double)a.targets[i] - (double)a.acting_values[i];
+    mean = block_sum(s, lds) * invM;
+    double q = 0.0;
+    for (long i = threadIdx.x; i < a.M; i += kLossThreads) {
+      const double c = ((double)a.targets[i] - (double)a.acting_values[i]) - mean;
+      q += c * c;
+    }
+    denom = sqrt(block_sum(q, lds) / (double)(a.M - 1)) + 1e-5;
+  }
+  const double lo = 1.0 - a.clip_value, hi = 1.0 + a.clip_value;
+  double s_gain = 0.0, s_vl = 0.0, s_ent = 0.0, s_val = 0.0;
+  for (long i = threadIdx.x; i < a.M; i += kLossThreads) {
+    const float* z = a.logits + i * a.pitch;
+    const RowSoftmax r = row_softmax(z, a.A);
+    const double logS = log(r.S);
+    int act = a.actions[i];
+    act = act < 0 ? 0 : (act >= a.A ? a.A - 1 : act);          // (an action outside [0, A) reads no memory outside the row)
+    const float lp32 = row_log_prob(z, act, r, logS);
+    if (a.log_probs) a.log_probs[i] = lp32;
+    const double H = logS - r.W / r.S;                          // -sum_j p_j log p_j
+    double adv = (double)a.targets[i] - (double)a.acting_values[i];
+    if (a.adv_norm) adv = (adv - mean) / denom;
+    // d gain_i / d log-prob (before the 1 / M of the mean)
+    double gain, coef;
+    if (!a.old_log_probs) {
+      gain = (double)lp32 * adv;
+      coef = adv;
+    } else {
+      const double ratio = exp((double)lp32 - (double)a.old_log_probs[i]);
+      const double s1 = ratio * adv, s2 = fmin(fmax(ratio, lo), hi) * adv;
+      gain = fmin(s1, s2);
+      // autograd: minimum() hands a tie half the gradient each way, clamp() passes it inside [lo, hi], bounds included
+      const bool inside = ratio >= lo && ratio <= hi;
+      const double share = inside ? 1.0 : (s1 < s2 ? 1.0 : (s1 == s2 ? 0.5 : 0.0));
+      coef = share * (ratio * adv);
+    }
+    const double t = (double)a.targets[i], v = (double)a.values[i];
+    s_gain += gain;
+    s_vl += (t - v) * (t - v);
+    s_ent += H;
+    s_val += v;
+    a.dvalues[i] = (float)(a.vf_coef * (2.0 * (v - t)) * invM);
+    float* g = a.dlogits + i * a.dpitch;
+    const double w = coef * invM, we = a.entropy_factor * invM;
+    for (int j = 0; j < a.A; ++j) {
+      const double d = (double)z[j] - (double)r.zmax;
+      const double p = exp(d) / r.S;
+      double gj = -(w * ((j == act ? 1.0 : 0.0) - p));
+      if (a.entropy_factor != 0.0) gj += we * (p * ((d - logS) + H));
+      g[j] = (float)gj;
+    }
+  }
+  const double gain = block_sum(s_gain, lds) * invM;
+  const double vl = block_sum(s_vl, lds) * invM;
+  const double ent = block_sum(s_ent, lds) * invM;
+  const double val = block_sum(s_val, lds) * invM;
+  if (threadIdx.x == 0) {
+    a.stats[0] = (float)(a.vf_coef * vl - gain - a.entropy_factor * ent);
+    a.stats[1] = (float)vl;
+    a.stats[2] = (float)(-gain);
+    a.stats[3] = (float)ent;
+    a.stats[4] = (float)val;
+  }
+}
+
+}  // namespace mirl
+
+extern "C" int mirl_actor_head_ac(int32_t E, int32_t A, const float* logits, int64_t pitch, const float* values, const float* u,
+                                  int32_t greedy, int32_t* actions, float* action_log_probs, float* values_out, int32_t out_pitch,
+                                  void* stream) {
+  if (E < 1 || E > (1 << 24) || A < 1 || A > 64 || pitch < A || !logits || !values || (greedy != 0 && greedy != 1) || (!greedy && !u) ||
+      !actions || !action_log_probs || !values_out || out_pitch < 1)
+    return mirl::fail(MIRL_ERR_ARG, "bad actor_head_ac arguments (1 <= E <= 2^24, 1 <= A <= 64, pitch >= A, greedy 0 | 1, u unless greedy, "
+                                    "out_pitch >= 1, no null operands)");
+  mirl::ProfScope ps("k_actor_head_ac", (double)E * (A + 6) * 4.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_actor_head_ac, dim3((E + 63) / 64), dim3(64), 0, (hipStream_t)stream, (int)E, (int)A, logits, (long)pitch, values, u,
+                     (int)greedy, actions, action_log_probs, values_out, (int)out_pitch);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
+extern "C" int mirl_online_window(int32_t T, int32_t B, int32_t E, int32_t cap, int32_t nstep_target, double gamma, double lam,
+                                  int64_t obs_bytes, const int32_t* plan, const void* obs_ring, const int32_t* actions_ring,
+                                  const float* rewards_ring, const uint8_t* dones_ring, const float* logp_ring, const float* values_ring,
+                                  int32_t pol_pitch, float* returns, float* nsteps, float* target_masks, int32_t* actions,
+                                  float* action_log_probs, float* values, void* states, void* target_states, void* stream) {
+  // (the plan's entries are device data: the caller keeps env in [0, E), the slot in [0, cap) and T + 1 <= cap steps behind them)
+  if (T < 1 || B < 1 || E < 1 || cap < T || nstep_target < 1 || obs_bytes < 1 || pol_pitch < 1 || !(gamma >= 0.0) || !(lam >= 0.0) ||
+      (int64_t)T * B > (1 << 24) || (double)cap * (double)E * (double)obs_bytes >= 9.0e18 || !plan || !obs_ring || !actions_ring ||
+      !rewards_ring || !dones_ring || !logp_ring || !values_ring || !returns || !nsteps || !target_masks || !actions ||
+      !action_log_probs || !values || !states || !target_states)
+    return mirl::fail(MIRL_ERR_ARG, "bad online_window arguments (T, B, E >= 1, cap >= T, nstep_target >= 1, obs_bytes >= 1, "
+                                    "T B <= 2^24, no null operands)");
+  mirl::WindowArgs a;
+  a.T = T; a.B = B; a.E = E; a.cap = cap; a.nstep_target = nstep_target; a.gamma = gamma; a.lam = lam; a.obs_bytes = obs_bytes;
+  a.plan = plan; a.obs_ring = (const unsigned char*)obs_ring; a.actions_ring = actions_ring; a.rewards_ring = rewards_ring;
+  a.dones_ring = dones_ring; a.logp_ring = logp_ring; a.values_ring = values_ring; a.pol_pitch = pol_pitch;
+  a.returns = returns; a.nsteps = nsteps; a.masks = target_masks; a.actions = actions; a.logp = action_log_probs; a.values = values;
+  a.states = (unsigned char*)states; a.target_states = (unsigned char*)target_states;
+  a.vec16 = (obs_bytes % 16 == 0 && mirl::aligned16(obs_ring, states, target_states)) ? 1 : 0;
+  mirl::ProfScope ps("k_online_window", (double)T * B * (4.0 * (double)obs_bytes + 40.0), (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_online_window, dim3((unsigned)(T * B)), dim3(256), 0, (hipStream_t)stream, a);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
+extern "C" int mirl_ac_loss(int64_t M, int32_t A, const float* logits, int64_t pitch, const float* values, const int32_t* actions,
+                            const float* targets, const float* acting_values, const float* old_log_probs, double vf_coef,
+                            double entropy_factor, double clip_value, int32_t adv_norm, float* dlogits, int64_t dpitch, float* dvalues,
+                            float* log_probs, float* stats, void* stream) {
+  if (M < 1 || M > (1 << 22) || A < 1 || A > 64 || pitch < A || dpitch < A || (adv_norm != 0 && adv_norm != 1) || (adv_norm && M < 2) ||
+      !logits || !values || !actions || !targets || !acting_values || !dlogits || !dvalues || !stats ||
+      (old_log_probs && !(clip_value >= 0.0)))
+    return mirl::fail(MIRL_ERR_ARG, "bad ac_loss arguments (1 <= M <= 2^22, M >= 2 with adv_norm, 1 <= A <= 64, pitches >= A, "
+                                    "adv_norm 0 | 1, clip_value >= 0 with old_log_probs, no null operands)");
+  mirl::LossArgs a;
+  a.M = M; a.A = A; a.logits = logits; a.pitch = pitch; a.values = values; a.actions = actions; a.targets = targets;
+  a.acting_values = acting_values; a.old_log_probs = old_log_probs; a.vf_coef = vf_coef; a.entropy_factor = entropy_factor;
+  a.clip_value = clip_value; a.adv_norm = adv_norm; a.dlogits = dlogits; a.dpitch = dpitch; a.dvalues = dvalues;
+  a.log_probs = log_probs; a.stats = stats;
+  mirl::ProfScope ps("k_ac_loss", (double)M * (2.0 * A + 8.0) * 4.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_ac_loss, dim3(1), dim3(mirl::kLossThreads), 0, (hipStream_t)stream, a);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}

@@ -6,6 +6,8 @@ _TABLE = LazyTypes({
     "replay": "rltime_amd.history.replay_history:ReplayHistoryBuffer",
     "prioritized_replay": "rltime_amd.history.replay_history:PrioritizedReplayHistoryBuffer",
     "online": "rltime_amd.history.online_history:OnlineHistoryBuffer",
+    # what A2C / PPO resolve "online" to when actor and policy are on the GPU (training/a2c.py)
+    "online_device": "rltime_amd.history.online_device:DeviceOnlineHistory",
 })
 
 

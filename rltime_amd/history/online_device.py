@@ -1,0 +1,201 @@
+"""On-policy ("online") history on the device, for A2C / PPO with the device-resident actor (reference
+rltime/history/online_history.py:4-120 over history.py:71-286; the host mirror is history/online_history.py).
+
+The actor hands whole vector steps (acting_interface.DeviceSamples): `update` appends them to device rings, one slot per
+vector step, with no host copy and no synchronisation.  Everything the reference decides on the host is data-independent
+— which envs are served round-robin, the `not last_env` quirk, how many transitions each env has pending, the
+max_delayed_steps discards, the feed decision, an env's very first transition starting from its own next_state — and
+stays on the host as plain Python (`OnlinePlan`, no torch).  `get_train_data` uploads the plan of the served sequences
+(env, first ring slot) and one launch of csrc/actor_critic.hip (mirl_online_window) writes the (T, B) batch: lambda-returns
+in float64, step counts, masks, the gathered policy outputs and both observation blocks.
+"""
+import numpy as np
+import torch
+
+
+class OnlinePlan:
+    """The host bookkeeping of OnlineHistoryBuffer for envs that are fed in whole vector steps.  Vector step number s
+    (counted from 0) lives in ring slot s % capacity; env e's pending transitions are the last pending[e] vector steps."""
+
+    def __init__(self, nstep_train, max_delayed_steps):
+        self.nstep_train, self.max_delayed_steps = nstep_train, max_delayed_steps
+        self.pending = {}          # env id -> transitions not handed out yet
+        self.first_step = {}       # env id -> the vector step of its first ever transition
+        self.head = 0              # vector steps fed so far
+        self.last_env = None
+
+    def feed(self, env_ids):
+        """One vector step -> transitions discarded (online_history.py:61-73)."""
+        discarded = 0
+        for e in env_ids:
+            if e not in self.pending:
+                self.pending[e], self.first_step[e] = 0, self.head
+            self.pending[e] += 1
+            if self.pending[e] > self.max_delayed_steps:
+                self.pending[e] -= 1
+                discarded += 1
+        self.head += 1
+        return discarded
+
+    def live_steps(self):
+        """Vector steps the rings must hold: the longest pending run and the step before it (its first state)."""
+        return max(self.pending.values(), default=0) + 1
+
+    def sequences_ready(self):
+        return sum(n // self.nstep_train for n in self.pending.values())
+
+    def serve(self, mbatch_size):
+        """online_history.py:81-120 -> [(env id, vector step of the sequence's first transition, 1 if that is the env's
+        first ever transition)] in the served order, or None = feed more."""
+        T = self.nstep_train
+        if self.sequences_ready() < mbatch_size:
+            return None
+        ids = sorted(self.pending)
+        # (`not last_env`, online_history.py:101-103: env id 0 restarts the walk like "none served yet")
+        at = 0 if not self.last_env else (ids.index(self.last_env) + 1) % len(ids)
+        out = []
+        while len(out) < mbatch_size:
+            env = ids[at]
+            if self.pending[env] >= T:
+                start = self.head - self.pending[env]
+                out.append((env, start, int(start == self.first_step[env])))
+                self.pending[env] -= T
+                self.last_env = env
+            at = (at + 1) % len(ids)
+        return out
+
+
+class DeviceOnlineHistory:
+    def __init__(self, max_delayed_steps=5000, fixed_target=True, **kwargs):
+        """online_history.py:21-47; **kwargs are History's (nstep_target, nstep_train, prefix_steps=0,
+        discount_function=None, state_store=None).  The discount function must be A2C's (training/a2c.py): its `.gamma`
+        and `.lam` are what the kernel evaluates."""
+        self._base_init(**kwargs)
+        if not fixed_target:
+            raise ValueError("DeviceOnlineHistory: fixed_target=False is not supported on the device path: its targets "
+                             "look past the training window")
+        if self.prefix_steps:
+            raise ValueError("Online history does not support prefix/burnin steps")
+        fn = self.discount_function
+        if fn is None:
+            self.gamma, self.lam = 1.0, 1.0           # nstep_target == 1: no discounted term is ever formed
+        elif hasattr(fn, "gamma") and hasattr(fn, "lam"):
+            self.gamma, self.lam = float(fn.gamma), float(fn.lam)
+        else:
+            raise ValueError("DeviceOnlineHistory evaluates the GAE(lambda) return of training/a2c.py on the GPU and "
+                             "needs a discount_function that carries .gamma and .lam")
+        from rltime_amd import _lib
+        _lib.require_gpu()
+        self.max_delayed_steps, self.fixed_target = max_delayed_steps, fixed_target
+        self.plan = OnlinePlan(self.nstep_train, max_delayed_steps)
+        self.capacity = 0
+        self._rings = None
+        self._served = []              # env ids in the order the last batch took them (tests)
+
+    def _base_init(self, nstep_target, nstep_train, prefix_steps=0, discount_function=None, state_store=None):
+        assert nstep_target == 1 or discount_function is not None, \
+            "History buffer must get a 'discount_function' for nstep_target>1"
+        self.nstep_target, self.nstep_train, self.prefix_steps = nstep_target, nstep_train, prefix_steps
+        self.discount_function = discount_function
+        self.state_store = state_store
+
+    @property
+    def last_env(self):
+        return self.plan.last_env
+
+    # -- feeding ----------------------------------------------------------------------------
+    def _configure(self, samples, step):
+        frames = step["frames"]
+        self._state_keys = [k for k in samples.example_state if k != "x"]
+        if any(samples.example_state[k] for k in self._state_keys) or "state" in step:
+            raise ValueError("DeviceOnlineHistory: recurrent policies are not supported on the device path")
+        if "extra" in step:
+            raise ValueError("DeviceOnlineHistory: extra-feature observations are not supported on the device path")
+        self.num_envs, self.env_base = samples.num_envs, samples.env_base
+        self._obs_shape, self._obs_dtype = tuple(frames.shape[1:]), frames.dtype
+        self._obs_bytes = int(np.prod(self._obs_shape)) * frames.element_size()
+        self._device = frames.device
+
+    def _grow(self, need, written):
+        """Rings of `need` or more vector steps, at most max_delayed_steps + 1; the `written` steps already stored keep
+        their slot number modulo the new capacity."""
+        top = self.max_delayed_steps + 1
+        cap = min(max(need, 2 * self.capacity, self.nstep_train + 1), max(top, need))
+        E, dev = self.num_envs, self._device
+        new = {"obs": torch.empty((cap, E, self._obs_bytes), dtype=torch.uint8, device=dev),
+               "actions": torch.empty((cap, E), dtype=torch.int32, device=dev),
+               "rewards": torch.empty((cap, E), dtype=torch.float32, device=dev),
+               "dones": torch.empty((cap, E), dtype=torch.uint8, device=dev),
+               "policy": torch.empty((cap, E, 2), dtype=torch.float32, device=dev)}
+        if self._rings is not None:
+            live = np.arange(max(0, written - self.capacity), written)
+            if len(live):
+                src = torch.as_tensor(live % self.capacity, device=dev)
+                dst = torch.as_tensor(live % cap, device=dev)
+                for k, ring in self._rings.items():
+                    new[k][dst] = ring[src]
+        self._rings, self.capacity = new, cap
+
+    def update(self, samples):
+        """Appends the DeviceSamples' vector steps to the rings -> {"discarded_steps": n} (online_history.py:61-73)."""
+        if not hasattr(samples, "vector_steps"):
+            raise TypeError("DeviceOnlineHistory takes the device actor's DeviceSamples (whole vector steps); per-env "
+                            "sample dicts belong to OnlineHistoryBuffer")
+        discarded = 0
+        for step in samples.vector_steps:
+            if self._rings is None:
+                self._configure(samples, step)
+            if samples.num_envs != self.num_envs or samples.env_base != self.env_base:
+                raise ValueError("DeviceOnlineHistory: every vector step must cover the same envs")
+            discarded += self.plan.feed(range(self.env_base, self.env_base + self.num_envs))
+            if self.plan.live_steps() > self.capacity:
+                self._grow(self.plan.live_steps(), self.plan.head - 1)
+            slot = (self.plan.head - 1) % self.capacity
+            r = self._rings
+            r["obs"][slot].copy_(step["frames"].reshape(self.num_envs, -1).view(torch.uint8))
+            r["actions"][slot].copy_(step["actions"])
+            r["rewards"][slot].copy_(step["rewards"])
+            r["dones"][slot].copy_(step["dones"])
+            r["policy"][slot].copy_(step["policy"])
+        return {"discarded_steps": discarded}
+
+    def needed_feed_count(self, mbatch_size, num_envs):
+        """online_history.py:75-79: feed one vector step whenever no batch can be formed."""
+        return None if self.plan.sequences_ready() >= mbatch_size else num_envs
+
+    # -- training batches --------------------------------------------------------------------
+    def get_train_data(self, mbatch_size, train_progress=None):
+        """online_history.py:81-120: `mbatch_size` sequences of nstep_train consecutive transitions, round-robin over
+        the env ids, each removed as soon as it is handed out.  None = feed more.  The batch has the host class's keys
+        and (T, B, ...) layout, as device tensors."""
+        from rltime_amd._lib import lib, check, ptr as p, stream
+        served = self.plan.serve(mbatch_size)
+        if served is None:
+            return None
+        self._served = [env for env, _, _ in served]
+        T, B, E, cap, dev = self.nstep_train, mbatch_size, self.num_envs, self.capacity, self._device
+        rows = np.array([(env - self.env_base, start % cap, own) for env, start, own in served], dtype=np.int32)
+        assert rows[:, 0].min() >= 0 and rows[:, 0].max() < E and cap >= T + 1
+        plan = torch.from_numpy(rows).to(dev, non_blocking=True)
+        f32 = lambda: torch.empty((T, B), dtype=torch.float32, device=dev)      # noqa: E731
+        returns, nsteps, masks, logp, values = f32(), f32(), f32(), f32(), f32()
+        actions = torch.empty((T, B), dtype=torch.int32, device=dev)
+        obs = torch.empty((2, T, B, self._obs_bytes), dtype=torch.uint8, device=dev)
+        r = self._rings
+        pol = r["policy"]
+        check(lib.mirl_online_window(T, B, E, cap, self.nstep_target, self.gamma, self.lam, self._obs_bytes, p(plan), p(r["obs"]),
+                                     p(r["actions"]), p(r["rewards"]), p(r["dones"]), p(pol), p(pol.view(-1)[1:]), 2,
+                                     p(returns), p(nsteps), p(masks), p(actions), p(logp), p(values), p(obs[0]), p(obs[1]),
+                                     stream()), "mirl_online_window")
+        shaped = obs.view(self._obs_dtype).reshape((2, T, B) + self._obs_shape)
+        tree = lambda x: dict({"x": x}, **{k: {} for k in self._state_keys})      # noqa: E731
+        return {"states": tree(shaped[0]), "target_states": tree(shaped[1]), "returns": returns, "nsteps": nsteps,
+                "target_masks": masks, "policy_outputs": {"actions": actions, "action_log_probs": logp, "values": values},
+                "extra_data": {}}
+
+    def update_losses(self, indices, losses):
+        pass
+
+    def close(self):
+        self._rings = None
+

@@ -1,8 +1,9 @@
 """ActorCriticPolicy and its action-distribution heads (reference
 rltime/policies/torch/actor_critic.py:9-107, policies/torch/distributions/{categorical,normal}.py).
 
-Used by the A2C / PPO trainers of the CPU plumbing config (BASELINE configs[0],
-`cartpole_ppo.json`); plain PyTorch, not on the MI355X hot path."""
+Used by the A2C / PPO trainers.  On the CPU (BASELINE configs[0], `cartpole_ppo.json`) everything here is plain PyTorch;
+on the GPU a Categorical policy hands its raw logits and values to the kernels of csrc/actor_critic.hip
+(`actor_head_ac_raw` for the acting step, `get_logits_and_state_value` for the fused loss)."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -69,6 +70,33 @@ class ActorCriticPolicy(TorchPolicy):
         """actor_critic.py:73-80."""
         model = self.value_model if self.value_model is not None else self.model
         return self.critic(model(inp, timesteps)["output"]).squeeze(-1)
+
+    def why_not_on_device(self):
+        """What keeps this policy off the device actor-critic path (csrc/actor_critic.hip), or None."""
+        if not isinstance(self.actor, CategoricalHead):
+            return "the Normal (continuous) action head is not supported on the device path"
+        if self.value_model is not None:
+            return "critic_separate_model is not supported on the device path"
+        if self.is_recurrent():
+            return "recurrent actor-critic policies are not supported on the device path"
+        if self.actor.logits_layer.out_features > 64:
+            return "more than 64 actions are not supported on the device path"
+        return None
+
+    def get_logits_and_state_value(self, inp, timesteps):
+        """The Categorical head's raw logits (rows, A) and the state values (rows,): what the fused loss
+        (training/qops.py ac_loss) differentiates."""
+        features = self.model(inp, timesteps)["output"]
+        return self.actor.logits_layer(features), self.critic(features).squeeze(-1)
+
+    def actor_head_ac_raw(self, inp, timesteps):
+        """No-grad (logits, values) of one acting step for the sampling-head kernel (acting/actor.py _select)."""
+        why = self.why_not_on_device()
+        if why is not None:
+            raise ValueError(why)
+        with torch.no_grad():
+            logits, values = self.get_logits_and_state_value(inp, timesteps)
+        return logits.contiguous(), values.contiguous()
 
     @staticmethod
     def _joint(log_probs):

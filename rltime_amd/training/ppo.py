@@ -21,3 +21,9 @@ class PPO(A2C):
         ratio = torch.exp(action_log_probs - old)
         c = self._calc_clip_value()
         return torch.min(ratio * advantages, torch.clamp(ratio, 1.0 - c, 1.0 + c) * advantages).mean()
+
+    _fused_gain = _calc_action_gain
+
+    def _fused_loss_args(self, policy_outputs):
+        """The clipped surrogate of the fused loss: acting-time log-probabilities and the (annealed) clip value."""
+        return self.policy.make_tensor(policy_outputs["action_log_probs"]), self._calc_clip_value()

@@ -170,3 +170,38 @@ def c51_loss(logits, actions, targets, weights=None, mode="crossentropy", kappa=
     """dist_dqn.py:99-142 -> (scalar loss differentiable w.r.t. logits (M, A, Z), unweighted row loss report (M,))."""
     scale = row_scale(logits.shape[0], timesteps, batch_mode, time_mode)
     return _C51Loss.apply(logits, actions, targets, weights, mode, kappa, scale)
+
+
+class _ACLoss(torch.autograd.Function):
+    """csrc/actor_critic.hip mirl_ac_loss: the loss scalar is stats[0]; its gradients come out of the same launch."""
+
+    @staticmethod
+    def forward(ctx, logits, values, actions, targets, acting_values, old_log_probs, vf_coef, entropy_factor, clip_value,
+                adv_norm):
+        z, v = _f32(logits), _f32(values)
+        M, A = z.shape
+        dz, dv = torch.empty_like(z), torch.empty_like(v)
+        stats = torch.empty(5, dtype=torch.float32, device=z.device)
+        old = _f32(old_log_probs) if old_log_probs is not None else None
+        check(lib.mirl_ac_loss(
+            M, A, ptr(z), z.stride(0), ptr(v), ptr(actions.detach().to(torch.int32).contiguous()), ptr(_f32(targets)),
+            ptr(_f32(acting_values)), ptr(old), float(vf_coef), float(entropy_factor),
+            float(clip_value if clip_value is not None else 0.0), 1 if adv_norm else 0, ptr(dz), A, ptr(dv), None,
+            ptr(stats), stream()), "mirl_ac_loss")
+        ctx.save_for_backward(dz, dv)
+        ctx.mark_non_differentiable(stats)
+        return stats[0].clone(), stats
+
+    @staticmethod
+    def backward(ctx, g_loss, g_stats):
+        dz, dv = ctx.saved_tensors
+        return dz * g_loss, dv * g_loss, None, None, None, None, None, None, None, None
+
+
+def ac_loss(logits, values, actions, targets, acting_values, old_log_probs=None, vf_coef=1.0, entropy_factor=0.0,
+            clip_value=None, adv_norm=False):
+    """training/torch/a2c.py:101-141 with the gain of a2c.py:90-99 (old_log_probs None) or ppo.py:39-56, forward and
+    backward in one launch -> (scalar loss differentiable w.r.t. logits (M, A) and values (M,), stats (5,) = loss,
+    value loss, policy loss, mean entropy, mean value)."""
+    return _ACLoss.apply(logits, values, actions, targets, acting_values, old_log_probs, vf_coef, entropy_factor,
+                         clip_value, adv_norm)

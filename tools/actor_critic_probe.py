@@ -1,0 +1,142 @@
+"""Timings of the actor-critic device path on one GPU (docs/measurement.md, "A2C / PPO on the device"):
+
+  loss      M = 512 rows, A = 6 and 18, from logits / values to their gradients: the fused call (training/qops.py ac_loss +
+            backward) against the plain-torch expression of A2C._compute_grads / PPO._calc_action_gain on the same GPU tensors,
+            alternating, host clock around a synchronised window of `--iters` calls each, repeated `--repeats` times
+  window    one DeviceOnlineHistory.get_train_data at T = 128, B = 16 on (4, 84, 84) uint8 frames
+  acting    one vector step of the device actor at 16 envs (catch_ppo.json's network, generic device path)
+
+    python tools/actor_critic_probe.py [--iters 200] [--repeats 5]      -> one JSON line
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _timed(fn, iters):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters * 1e6          # microseconds per call
+
+
+def _torch_loss(logits, values, actions, targets, acting, old, vf, ef, clip):
+    """A2C._compute_grads with PPO's gain, as the trainers write it."""
+    dist = torch.distributions.Categorical(logits=logits)
+    log_probs, entropy = dist.log_prob(actions), dist.entropy().mean()
+    adv = targets - acting
+    adv = (adv - adv.mean()) / (adv.std() + 1e-5)
+    ratio = torch.exp(log_probs - old)
+    gain = torch.min(ratio * adv, torch.clamp(ratio, 1.0 - clip, 1.0 + clip) * adv).mean()
+    value_loss = (targets - values).pow(2).mean()
+    return value_loss * vf - gain - ef * entropy
+
+
+def loss_times(M, A, iters, repeats):
+    from rltime_amd.training import qops
+    g = torch.Generator(device="cuda").manual_seed(1)
+    logits = torch.randn(M, A, device="cuda", generator=g).requires_grad_(True)
+    values = torch.randn(M, device="cuda", generator=g).requires_grad_(True)
+    actions = torch.randint(0, A, (M,), device="cuda", generator=g)
+    a32 = actions.to(torch.int32)
+    targets, acting = values.detach() + torch.randn(M, device="cuda", generator=g), values.detach() + 0.3
+    old = torch.log_softmax(logits.detach(), 1).gather(1, actions[:, None])[:, 0] + 0.2 * torch.randn(M, device="cuda", generator=g)
+
+    def fused():
+        logits.grad = values.grad = None
+        loss, _ = qops.ac_loss(logits, values, a32, targets, acting, old_log_probs=old, vf_coef=0.5, entropy_factor=0.01,
+                               clip_value=0.2, adv_norm=True)
+        loss.backward()
+
+    def plain():
+        logits.grad = values.grad = None
+        _torch_loss(logits, values, actions, targets, acting, old, 0.5, 0.01, 0.2).backward()
+    fused()
+    g_f = logits.grad.clone()
+    fused()
+    diff = float((logits.grad - g_f).abs().max())           # (a rerun repeats the first run bit for bit: 0.0)
+    plain()
+    agree = float((logits.grad - g_f).abs().max() / g_f.abs().max())
+    for _ in range(20):
+        fused()
+        plain()
+    f, p = [], []
+    for _ in range(repeats):                                  # alternating, same process
+        f.append(_timed(fused, iters))
+        p.append(_timed(plain, iters))
+    return {"M": M, "A": A, "fused_us": [round(x, 1) for x in f], "torch_us": [round(x, 1) for x in p],
+            "fused_us_median": round(sorted(f)[len(f) // 2], 1), "torch_us_median": round(sorted(p)[len(p) // 2], 1),
+            "rerun_max_diff": diff, "fused_vs_torch_grad_rel": agree}
+
+
+def window_time(iters):
+    from rltime_amd.acting.acting_interface import DeviceSamples
+    from rltime_amd.history.online_device import DeviceOnlineHistory
+    T, B = 128, 16
+
+    def discount(n, r, po):
+        return 0.0
+    discount.gamma, discount.lam = 0.99, 0.95
+    hist = DeviceOnlineHistory(nstep_target=T, nstep_train=T, discount_function=discount)
+    frames = torch.randint(0, 256, (B, 4, 84, 84), dtype=torch.uint8, device="cuda")
+    step = dict(frames=frames, actions=torch.zeros(B, dtype=torch.int32, device="cuda"), policy=torch.zeros(B, 2, device="cuda"),
+                rewards=torch.ones(B, device="cuda"), dones=torch.zeros(B, dtype=torch.uint8, device="cuda"))
+    times = []
+    for _ in range(iters):
+        s = DeviceSamples({"x": None, "layer0_state": {}}, B, 0)
+        for _ in range(T):
+            s.append(**step)
+        hist.update(s)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        batch = hist.get_train_data(B)
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e6)
+        assert batch is not None
+    times = sorted(times[1:])
+    nbytes = 4 * T * B * 4 * 84 * 84                          # both blocks read and written
+    med = times[len(times) // 2]
+    return {"T": T, "B": B, "get_train_data_us_median": round(med, 1), "get_train_data_us_min": round(times[0], 1),
+            "observation_GBps_at_median": round(nbytes / med / 1e3, 1), "ring_capacity_steps": hist.capacity}
+
+
+def acting_time(iters):
+    from rltime_amd.general.config import load_config
+    from rltime_amd.policies.actor_critic import ActorCriticPolicy
+    from rltime_amd.train import create_actors
+    cfg = load_config("catch_ppo.json")
+    actors = create_actors(cfg, "cuda")
+    try:
+        obs_space, act_space = actors.get_spaces()
+        policy = ActorCriticPolicy.create(model_config=cfg["model"], observation_space=obs_space, action_space=act_space, cuda=True)
+        actors.set_actor_policy(policy)
+        E = actors.get_env_count()
+        actors.get_samples(E * 20)
+        us = _timed(lambda: actors.get_samples(E * 10), max(1, iters // 10)) / 10
+    finally:
+        actors.close()
+    return {"envs": E, "vector_step_us": round(us, 1)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--repeats", type=int, default=5)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("actor_critic_probe: no GPU visible; timings are taken on the device only")
+    out = {"loss": [loss_times(512, A, a.iters, a.repeats) for A in (6, 18)], "window": window_time(max(8, a.iters // 10)),
+           "acting": acting_time(a.iters)}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
