@@ -401,7 +401,9 @@ int mirl_lstm_seq_fwd(int32_t T, int32_t B, int32_t H, float* gx, const float* w
 int mirl_lstm_seq_status(int32_t* status);
 /* Launch geometry of the forward sweep for (B, H): the workgroups that must all be resident at once, their
  * dynamic LDS, the device's compute units and how many such workgroups one unit holds.  Two sweeps issued on
- * two streams only make progress together when 2 x workgroups <= compute_units x per_compute_unit.        */
+ * two streams only make progress together when 2 x workgroups <= compute_units x per_compute_unit.  The launcher
+ * reads the same geometry and mirl_lstm_seq_workspace_bytes the sizes it is built on (one function each in
+ * csrc/lstm_seq.hip), so what this call reports is what mirl_lstm_seq_fwd launches.                      */
 int mirl_lstm_seq_fwd_grid(int32_t B, int32_t H, int32_t* workgroups, int64_t* lds_bytes, int32_t* compute_units,
                            int32_t* per_compute_unit);
 /* The backward sweep of the same layer in ONE persistent launch (replaces the T-step loop of

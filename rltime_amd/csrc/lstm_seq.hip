@@ -36,6 +36,10 @@
 //     the next call into MIRL_ERR_STATE.  The grid never exceeds the CU count (one
 //     workgroup per CU: 137 KB of LDS each), clusters loop over row blocks instead.
 //
+// What the three kernels share word for word is in the sq_* helpers below (layout sq_slot, counter wait sq_wait_arrivals,
+// arrival sq_arrive, pre-poll sq_prepoll, give-up sq_give_up); the launch geometry is stated once on the host
+// (seq_fwd_geometry / seq_bwd_geometry over seq_fwd_sizes / seq_bwd_sizes).
+//
 // Outputs are those of the per-step path (rltime_amd/models/torch/lstm_seq.py): out[t],
 // the final (masked) state, and — for the backward pass — activated gates in place of
 // the pre-activations, c(t), and the masked step inputs hm / cm.
@@ -71,6 +75,63 @@ __device__ __forceinline__ unsigned sq_tag(int t) { return (unsigned)(((t >> 1) 
 #define SQ_SPIN_CAP (1u << 22)
 #define SQ_TP 20          // floats per row of the per-wave transposition tile (16 + 4: 16-byte aligned rows)
 
+// ---------------------------------------------------------------------------
+// The parts of the exchange protocol that the sweeps share word for word.  (The tagged sweep and the publish stay
+// written out in the two forward kernels: as helpers they compute the same bits, but the register allocation of
+// k_lstm_seq_fwd_narrow<512> changes and its step gets 7 % slower — docs/measurement.md.)
+// Exchange layout of a tile's 16 x H block of h: [q][lane = row + 16 kg][j], hidden k = (H / 4) kg + 4 q + j, the MFMA
+// A-operand order: a receiving lane's KQ loads are its operand.  -> float offset of (hidden quad k0 .. k0 + 3, row)
+template <int H>
+__device__ __forceinline__ int sq_slot(int k0, int row) {
+  constexpr int KG = H / 4;
+  return (((k0 % KG) >> 2) * 64 + (row + 16 * (k0 / KG))) * 4;
+}
+
+// Form R1, consumer: ONE lane polls the tile's arrival counter (relaxed, agent scope) under the spin cap; the verdict
+// is wave-uniform, false = gave up.  The forward reads with sc1 loads behind it, the backward adds its acquire.
+__device__ __forceinline__ bool sq_wait_arrivals(const unsigned* cnt, unsigned want, int lane) {
+  int bad = 0;
+  if (lane == 0) {
+    unsigned spins = 0;
+    while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
+      __builtin_amdgcn_s_sleep(1);
+      if (++spins > SQ_SPIN_CAP) { bad = 1; break; }
+    }
+  }
+  return __builtin_amdgcn_readfirstlane(bad) == 0;
+}
+// Form R1, producer: the storing wave drains its write-through stores, then ONE relaxed arrival on the tile's counter
+__device__ __forceinline__ void sq_arrive(unsigned* cnt, int lane) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (lane == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// A bounded spin gave up: the host-visible word turns the next call into MIRL_ERR_STATE; the caller returns
+__device__ __forceinline__ void sq_give_up(int* status, int lane) {
+  if (lane == 0) __hip_atomic_store(status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Cheap pre-poll of a tagged block `blk` written by NP producers of UNITS hidden units each: lane l watches producers
+// l, l + 64, ..., ONE word each (row 15 of the producer's last hidden quad), with relaxed agent-scope atomic loads:
+// 4 bytes per producer instead of 32 KB sweeps while the data is not there yet.  false = gave up.
+template <int H, int NP, int UNITS>
+__device__ __forceinline__ bool sq_prepoll(const float* blk, unsigned tag, int lane, unsigned& spins) {
+  for (;;) {
+    unsigned ok = 1u;
+#pragma unroll
+    for (int round = 0; round < (NP + 63) / 64; ++round) {
+      const int p = lane + 64 * round;
+      if (p < NP) {
+        const unsigned wv = __hip_atomic_load((const unsigned*)blk + sq_slot<H>(UNITS * p + UNITS - 4, 15), __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_AGENT);
+        ok &= (((wv ^ tag) & 0x40000000u) == 0u) ? 1u : 0u;
+      }
+    }
+    if (__all(ok != 0u)) return true;
+    __builtin_amdgcn_s_sleep(1);
+    if (++spins > SQ_SPIN_CAP) return false;
+  }
+}
+
 template <int H>
 __global__ void __launch_bounds__(256, 1)
 k_lstm_seq_fwd(SeqFwdArgs a, unsigned* __restrict__ counters, float* X, int64_t x_half_floats, int nclusters, int* status) {
@@ -94,14 +155,10 @@ k_lstm_seq_fwd(SeqFwdArgs a, unsigned* __restrict__ counters, float* X, int64_t 
   __syncthreads();
   float* Tw = Tl + wave * 16 * SQ_TP;
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(X, 0, (int)(3 * x_half_floats * 4), 0x00020000);
-  // exchange layout: [tile][q][lane = row + 16 kg][j]; this lane's 16-byte chunk on the publishing side:
-  // transposition-tile row pr = lane / 4, hidden quad pq = lane % 4  ->  k0 = 16 cg + 4 pq
+  // this lane's 16-byte chunk on the publishing side: transposition-tile row pr = lane / 4, hidden quad pq = lane % 4  ->  k0 = 16 cg + 4 pq
   const int pr = lane >> 2, pq = lane & 3;
   const int pk0 = 16 * cg + 4 * pq;
-  const int p_slot = (((pk0 % KG) >> 2) * 64 + (pr + 16 * (pk0 / KG))) * 4;     // float offset inside the tile's [KQ][64][4] block
-  // the word lane l polls for producer l (column group l): last row, last quad of its 16 x 16 block
-  const int poll_k0 = 16 * (lane % NCG) + 12;
-  const int poll_slot = (((poll_k0 % KG) >> 2) * 64 + (15 + 16 * (poll_k0 / KG))) * 4;
+  const int p_slot = sq_slot<H>(pk0, pr);
   const int nrb = (B + 63) >> 6;
   const int b_off = (li * PW + KG * lk);             // + g * 16 * PW + 4 q
   for (int rb = cluster; rb < nrb; rb += nclusters) {
@@ -139,16 +196,7 @@ k_lstm_seq_fwd(SeqFwdArgs a, unsigned* __restrict__ counters, float* X, int64_t 
         sq_f4 av[KQ];
         if (t == 0) {
           const unsigned want = (unsigned)NCG;
-          int bad = 0;
-          if (lane == 0) {
-            unsigned spins = 0;
-            while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-              __builtin_amdgcn_s_sleep(1);
-              if (++spins > SQ_SPIN_CAP) { bad = 1; break; }
-            }
-          }
-          bad = __builtin_amdgcn_readfirstlane(bad);
-          if (bad) { failed = true; break; }
+          if (!sq_wait_arrivals(cnt, want, lane)) { failed = true; break; }
           asm volatile("" ::: "memory");
         }
         {
@@ -156,16 +204,7 @@ k_lstm_seq_fwd(SeqFwdArgs a, unsigned* __restrict__ counters, float* X, int64_t 
           const int xb = (int)(((t == 0 ? 2 * x_half_floats : (t & 1) * x_half_floats) + x_tile) * 4) + lane * 16;
           unsigned spins = 0;
           if (t >= 1) {
-            // cheap pre-poll: lane l < NCG watches ONE word of producer l's block (a relaxed agent-scope
-            // atomic load: 4 bytes per producer instead of 32 KB sweeps while the data is not there yet)
-            const unsigned* probe = (const unsigned*)(X + (t & 1) * x_half_floats + x_tile + poll_slot);
-            for (;;) {
-              const unsigned wv = lane < NCG ? __hip_atomic_load(probe, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : tmask;
-              if (__all(((wv ^ tmask) & 0x40000000u) == 0u)) break;
-              __builtin_amdgcn_s_sleep(1);
-              if (++spins > SQ_SPIN_CAP) { failed = true; break; }
-            }
-            if (failed) break;
+            if (!sq_prepoll<H, NCG, 16>(X + (t & 1) * x_half_floats + x_tile, tmask, lane, spins)) { failed = true; break; }
             asm volatile("" ::: "memory");
           }
           for (;;) {
@@ -238,8 +277,7 @@ k_lstm_seq_fwd(SeqFwdArgs a, unsigned* __restrict__ counters, float* X, int64_t 
           // initial state: arbitrary values, no tag — counter-guarded (form R1)
           const int off = (int)((2 * x_half_floats + x_tile + p_slot) * 4);
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(sq_u4, chunk), xr, off, 0, 16);
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          if (lane == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          sq_arrive(cnt, lane);
         } else {
           const int off = (int)(((((t + 1) & 1) * x_half_floats) + x_tile + p_slot) * 4);
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(sq_u4, chunk) | sq_tag(t), xr, off, 0, 16);
@@ -282,10 +320,7 @@ k_lstm_seq_fwd(SeqFwdArgs a, unsigned* __restrict__ counters, float* X, int64_t 
         }
       }
     }
-    if (failed) {
-      if (lane == 0) __hip_atomic_store(status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      return;
-    }
+    if (failed) { sq_give_up(status, lane); return; }
   }
 }
 
@@ -297,8 +332,8 @@ k_lstm_seq_fwd(SeqFwdArgs a, unsigned* __restrict__ counters, float* X, int64_t 
 // 16-column MFMA tile: 128 MFMAs per step on four k-interleaved accumulators (1.7 us), four
 // times as many waves.  Lane n of a 16-lane row holds gate n / 4 of hidden n % 4, so the four
 // gates of a hidden unit sit in lanes n % 4 + {0, 4, 8, 12}: pre-activations are gathered with
-// three cross-lane reads (ds_bpermute) per row.  Exchange layout, tags and the acquire-before-
-// re-sweep rule are those of k_lstm_seq_fwd; a tile now has H / 4 producers.
+// three cross-lane reads (ds_bpermute) per row.  Exchange layout (sq_slot), tags and the acquire-before-
+// re-sweep rule are those of k_lstm_seq_fwd; a tile now has H / 4 producers of 4 hidden units each.
 template <int H>
 __global__ void __launch_bounds__(256, 1)
 k_lstm_seq_fwd_narrow(SeqFwdArgs a, unsigned* __restrict__ counters, float* X, int64_t x_half_floats, int nclusters, int* status) {
@@ -321,7 +356,7 @@ k_lstm_seq_fwd_narrow(SeqFwdArgs a, unsigned* __restrict__ counters, float* X, i
   float* Tw = Tl + wave * 64;
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(X, 0, (int)(3 * x_half_floats * 4), 0x00020000);
   const int pk0 = 4 * cgn;                           // this wave publishes hidden units pk0 .. pk0 + 3: lanes 0..15 = rows
-  const int p_slot = (((pk0 % KG) >> 2) * 64 + ((lane & 15) + 16 * (pk0 / KG))) * 4;
+  const int p_slot = sq_slot<H>(pk0, lane & 15);
   const int nrb = (B + 63) >> 6;
   const int b_off = (li * PW + KG * lk);
   const int src1 = (lane & 48) | ((li + 4) & 15), src2 = (lane & 48) | ((li + 8) & 15), src3 = (lane & 48) | ((li + 12) & 15);
@@ -354,16 +389,7 @@ k_lstm_seq_fwd_narrow(SeqFwdArgs a, unsigned* __restrict__ counters, float* X, i
         sq_f4 av[KQ];
         if (t == 0) {
           const unsigned want = (unsigned)NP;
-          int bad = 0;
-          if (lane == 0) {
-            unsigned spins = 0;
-            while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-              __builtin_amdgcn_s_sleep(1);
-              if (++spins > SQ_SPIN_CAP) { bad = 1; break; }
-            }
-          }
-          bad = __builtin_amdgcn_readfirstlane(bad);
-          if (bad) { failed = true; break; }
+          if (!sq_wait_arrivals(cnt, want, lane)) { failed = true; break; }
           asm volatile("" ::: "memory");
         }
         {
@@ -371,25 +397,7 @@ k_lstm_seq_fwd_narrow(SeqFwdArgs a, unsigned* __restrict__ counters, float* X, i
           const int xb = (int)(((t == 0 ? 2 * x_half_floats : (t & 1) * x_half_floats) + x_tile) * 4) + lane * 16;
           unsigned spins = 0;
           if (t >= 1) {
-            // pre-poll: one word of every producer's block (row 15 of its 4 hidden units), two loads per lane
-            const unsigned* base = (const unsigned*)(X + (t & 1) * x_half_floats + x_tile);
-            for (;;) {
-              unsigned ok = 1u;
-#pragma unroll
-              for (int half = 0; half < (NP + 63) / 64; ++half) {
-                const int pcg = lane + 64 * half;
-                if (pcg < NP) {
-                  const int k0 = 4 * pcg;
-                  const unsigned wv = __hip_atomic_load(base + (((k0 % KG) >> 2) * 64 + (15 + 16 * (k0 / KG))) * 4, __ATOMIC_RELAXED,
-                                                        __HIP_MEMORY_SCOPE_AGENT);
-                  ok &= (((wv ^ tmask) & 0x40000000u) == 0u) ? 1u : 0u;
-                }
-              }
-              if (__all(ok != 0u)) break;
-              __builtin_amdgcn_s_sleep(1);
-              if (++spins > SQ_SPIN_CAP) { failed = true; break; }
-            }
-            if (failed) break;
+            if (!sq_prepoll<H, NP, 4>(X + (t & 1) * x_half_floats + x_tile, tmask, lane, spins)) { failed = true; break; }
             asm volatile("" ::: "memory");
           }
           for (;;) {
@@ -449,8 +457,7 @@ k_lstm_seq_fwd_narrow(SeqFwdArgs a, unsigned* __restrict__ counters, float* X, i
         if (t < 0) {
           const int off = (int)((2 * x_half_floats + x_tile + p_slot) * 4);
           if (lane < 16) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(sq_u4, chunk), xr, off, 0, 16);
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          if (lane == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          sq_arrive(cnt, lane);
         } else {
           const int off = (int)(((((t + 1) & 1) * x_half_floats) + x_tile + p_slot) * 4);
           if (lane < 16) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(sq_u4, chunk) | sq_tag(t), xr, off, 0, 16);
@@ -490,10 +497,7 @@ k_lstm_seq_fwd_narrow(SeqFwdArgs a, unsigned* __restrict__ counters, float* X, i
         for (int v = 0; v < 4; ++v) gxs[(int64_t)v * 4 * H] = act[v];
       }
     }
-    if (failed) {
-      if (lane == 0) __hip_atomic_store(status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      return;
-    }
+    if (failed) { sq_give_up(status, lane); return; }
   }
 }
 
@@ -546,7 +550,6 @@ k_lstm_seq_bwd(SeqBwdArgs a, unsigned* __restrict__ counters, float* P, int64_t 
   }
   __syncthreads();
   float* Tw = Tl + wave * 1024;
-  const int tiles = B / 16;
   const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc(P, 0, (int)(2 * p_half_floats * 4), 0x00020000);
   const int nrb = (B + 63) >> 6;
   for (int rb = cluster; rb < nrb; rb += nclusters) {
@@ -581,16 +584,7 @@ k_lstm_seq_bwd(SeqBwdArgs a, unsigned* __restrict__ counters, float* P, int64_t 
       float dhr[4] = {0.f, 0.f, 0.f, 0.f};
       if (!first) {
         const unsigned want = (unsigned)NCG * (unsigned)(T - 1 - t);
-        int bad = 0;
-        if (lane == 0) {
-          unsigned spins = 0;
-          while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > SQ_SPIN_CAP) { bad = 1; break; }
-          }
-        }
-        bad = __builtin_amdgcn_readfirstlane(bad);
-        if (bad) { failed = true; break; }
+        if (!sq_wait_arrivals(cnt, want, lane)) { failed = true; break; }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         const int pb = (int)(((((t + 1) & 1) * p_half_floats) + p_tile + (int64_t)cg * NCG * 256) * 4) + lane * 16;
         sq_f4 part[NCG];
@@ -647,8 +641,7 @@ k_lstm_seq_bwd(SeqBwdArgs a, unsigned* __restrict__ counters, float* P, int64_t 
 #pragma unroll
         for (int jt = 0; jt < NCG; ++jt)
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(sq_u4, acc[jt]), pr, ob + jt * (NCG * 1024), 0, 16);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sq_arrive(cnt, lane);
       }
       // ---- d loss / d pre-activation of this step, in place of the activated gates
       {
@@ -660,12 +653,8 @@ k_lstm_seq_bwd(SeqBwdArgs a, unsigned* __restrict__ counters, float* P, int64_t 
         }
       }
     }
-    if (failed) {
-      if (lane == 0) __hip_atomic_store(status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      return;
-    }
+    if (failed) { sq_give_up(status, lane); return; }
   }
-  (void)tiles;
 }
 
 static int* g_seq_status = nullptr;       // pinned host word the kernels write on a spin timeout
@@ -679,62 +668,92 @@ static int seq_init() {
   return MIRL_OK;
 }
 
-// small batches: four times as many, four times narrower waves (k_lstm_seq_fwd_narrow) while they all
-// fit the chip at once (every wave a step waits for must be resident)
-static bool seq_narrow(int nrb, int H) { return nrb * (H / 4) <= cu_count(); }
+// The status word before a launch: allocated if need be; a failure that an earlier sweep left there is TAKEN — reported
+// once with `gave_up` as MIRL_ERR_STATE — and cleared
+static int seq_take_status(const char* gave_up) {
+  if (int rc = seq_init()) return rc;
+  if (!*(volatile int*)g_seq_status) return MIRL_OK;
+  *g_seq_status = 0;
+  return fail(MIRL_ERR_STATE, gave_up);
+}
+static int seq_status_device(int** dev) {
+  MIRL_HIP(hipHostGetDevicePointer((void**)dev, g_seq_status, 0));
+  return MIRL_OK;
+}
+
+// The workspace of a sweep — pure arithmetic, no device query: [arrival counters, 32 words per tile, padded to 256 bytes]
+// [exchange half 0][exchange half 1] and, forward only, [initial-state buffer], x_half_floats each
+struct SeqSizes {
+  int64_t x_half_floats;        // floats per exchange half (forward: h blocks; backward: partial dh blocks)
+  size_t counter_bytes, workspace_bytes;
+};
+
+static SeqSizes seq_sizes(int B, int64_t tile_floats, int halves) {
+  const int64_t tiles = B / 16, half = tiles * tile_floats;
+  const size_t counters = align_up((size_t)tiles * 32 * sizeof(unsigned), 256);
+  return SeqSizes{half, counters, counters + (size_t)(halves * half) * sizeof(float)};
+}
+// forward: a 16 x H block of h per tile; backward: a 16 x 16 partial block from every column group to every column group
+static SeqSizes seq_fwd_sizes(int B, int H) { return seq_sizes(B, (int64_t)(H / 16) * 256, 3); }
+static SeqSizes seq_bwd_sizes(int B, int H) { return seq_sizes(B, (int64_t)(H / 16) * (H / 16) * 256, 2); }
+
+// The launch geometry of a sweep: the ONE statement that the launcher and mirl_lstm_seq_fwd_grid read, on top of the
+// sizes that the workspace queries read.  workgroups = nclusters x (producers per tile) must all be resident at once;
+// a cluster loops over the row blocks c, c + nclusters, ...
+struct SeqGrid : SeqSizes {
+  bool narrow;                  // k_lstm_seq_fwd_narrow: a wave per 4 hidden units instead of 16
+  int workgroups, nclusters;    // nclusters < 1: fewer compute units than column groups, no launch
+  size_t lds_bytes;
+  int per_compute_unit;         // workgroups a compute unit holds: by LDS (160 KB), at most 8 (32 waves, 4 each)
+};
+
+static SeqGrid seq_grid(const SeqSizes& z, bool narrow, int B, int groups, size_t lds_floats) {
+  const int nrb = (B + 63) / 64;
+  SeqGrid g;
+  static_cast<SeqSizes&>(g) = z;
+  g.narrow = narrow, g.nclusters = narrow ? nrb : std::min(cu_count() / groups, nrb);
+  g.workgroups = g.nclusters * groups;
+  g.lds_bytes = lds_floats * sizeof(float);
+  g.per_compute_unit = (int)std::min<int64_t>((160 * 1024) / (int64_t)g.lds_bytes, 8);
+  return g;
+}
+
+// Small batches: four times as many, four times narrower waves (k_lstm_seq_fwd_narrow) while they all fit the chip at
+// once (every wave a step waits for must be resident)
+static SeqGrid seq_fwd_geometry(int B, int H) {
+  const bool narrow = ((B + 63) / 64) * (H / 4) <= cu_count();
+  return narrow ? seq_grid(seq_fwd_sizes(B, H), true, B, H / 4, 16 * (H + 4) + 4 * 64)
+                : seq_grid(seq_fwd_sizes(B, H), false, B, H / 16, 64 * (H + 4) + 4 * 16 * SQ_TP);
+}
+
+static SeqGrid seq_bwd_geometry(int B, int H) { return seq_grid(seq_bwd_sizes(B, H), false, B, H / 16, 64 * 16 * SQB_LP + 4 * 1024); }
 
 template <int H>
 static int seq_launch(const SeqFwdArgs& a, void* workspace, hipStream_t st) {
-  constexpr int NCG = H / 16, KQ = H / 16;
-  const int tiles = a.B / 16, nrb = (a.B + 63) / 64;
-  if (seq_narrow(nrb, H)) {
-    const size_t cnt_b = (size_t)tiles * 32 * sizeof(unsigned);
-    const int64_t x_half_n = (int64_t)tiles * KQ * 256;
-    unsigned* counters_n = (unsigned*)workspace;
-    float* Xn = (float*)((char*)workspace + align_up(cnt_b, 256));
-    MIRL_HIP(hipMemsetAsync(workspace, 0, align_up(cnt_b, 256) + (size_t)(2 * x_half_n) * sizeof(float), st));
-    const size_t lds_n = (size_t)(16 * (H + 4) + 4 * 64) * sizeof(float);
-    int* status_n = nullptr;
-    MIRL_HIP(hipHostGetDevicePointer((void**)&status_n, g_seq_status, 0));
-    hipLaunchKernelGGL(k_lstm_seq_fwd_narrow<H>, dim3((unsigned)(nrb * (H / 4))), dim3(256), lds_n, st, a, counters_n, Xn, x_half_n, nrb, status_n);
-    MIRL_LAUNCH_CHECK();
-    return MIRL_OK;
-  }
-  int ncl = cu_count() / NCG;
-  if (ncl < 1) return fail(MIRL_ERR_ARG, "lstm_seq_fwd: fewer compute units than column groups");
-  if (ncl > nrb) ncl = nrb;
-  const size_t cnt_bytes = (size_t)tiles * 32 * sizeof(unsigned);
-  const int64_t x_half = (int64_t)tiles * KQ * 256;
-  // [arrival counters][exchange half 0][exchange half 1][initial-state buffer]; the counters and
-  // both tagged halves start from zero (tag 0 = "nothing written yet") on every launch
-  unsigned* counters = (unsigned*)workspace;
-  float* X = (float*)((char*)workspace + align_up(cnt_bytes, 256));
-  MIRL_HIP(hipMemsetAsync(workspace, 0, align_up(cnt_bytes, 256) + (size_t)(2 * x_half) * sizeof(float), st));
-  const size_t lds = (size_t)(64 * (H + 4) + 4 * 16 * SQ_TP) * sizeof(float);
-  if (int rc = raise_lds_limit(k_lstm_seq_fwd<H>, lds)) return rc;
+  const SeqGrid g = seq_fwd_geometry(a.B, H);
+  if (g.nclusters < 1) return fail(MIRL_ERR_ARG, "lstm_seq_fwd: fewer compute units than column groups");
+  const auto kernel = g.narrow ? k_lstm_seq_fwd_narrow<H> : k_lstm_seq_fwd<H>;
+  // the counters and both tagged halves start from zero (tag 0 = "nothing written yet") on every launch
+  MIRL_HIP(hipMemsetAsync(workspace, 0, g.counter_bytes + (size_t)(2 * g.x_half_floats) * sizeof(float), st));
+  if (int rc = raise_lds_limit(kernel, g.lds_bytes)) return rc;
   int* status_dev = nullptr;
-  MIRL_HIP(hipHostGetDevicePointer((void**)&status_dev, g_seq_status, 0));
-  hipLaunchKernelGGL(k_lstm_seq_fwd<H>, dim3((unsigned)(ncl * NCG)), dim3(256), lds, st, a, counters, X, x_half, ncl, status_dev);
+  if (int rc = seq_status_device(&status_dev)) return rc;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)g.workgroups), dim3(256), g.lds_bytes, st, a, (unsigned*)workspace,
+                     (float*)((char*)workspace + g.counter_bytes), g.x_half_floats, g.nclusters, status_dev);
   MIRL_LAUNCH_CHECK();
   return MIRL_OK;
 }
 
 template <int H>
 static int seq_bwd_launch(const SeqBwdArgs& a, void* workspace, hipStream_t st) {
-  constexpr int NCG = H / 16;
-  const int tiles = a.B / 16, nrb = (a.B + 63) / 64;
-  int ncl = cu_count() / NCG;
-  if (ncl < 1) return fail(MIRL_ERR_ARG, "lstm_seq_bwd: fewer compute units than column groups");
-  if (ncl > nrb) ncl = nrb;
-  const size_t cnt_bytes = align_up((size_t)tiles * 32 * sizeof(unsigned), 256);
-  const int64_t p_half = (int64_t)tiles * NCG * NCG * 256;
-  MIRL_HIP(hipMemsetAsync(workspace, 0, cnt_bytes, st));
-  const size_t lds = (size_t)(64 * 16 * SQB_LP + 4 * 1024) * sizeof(float);
-  if (int rc = raise_lds_limit(k_lstm_seq_bwd<H>, lds)) return rc;
+  const SeqGrid g = seq_bwd_geometry(a.B, H);
+  if (g.nclusters < 1) return fail(MIRL_ERR_ARG, "lstm_seq_bwd: fewer compute units than column groups");
+  MIRL_HIP(hipMemsetAsync(workspace, 0, g.counter_bytes, st));
+  if (int rc = raise_lds_limit(k_lstm_seq_bwd<H>, g.lds_bytes)) return rc;
   int* status_dev = nullptr;
-  MIRL_HIP(hipHostGetDevicePointer((void**)&status_dev, g_seq_status, 0));
-  hipLaunchKernelGGL(k_lstm_seq_bwd<H>, dim3((unsigned)(ncl * NCG)), dim3(256), lds, st, a, (unsigned*)workspace,
-                     (float*)((char*)workspace + cnt_bytes), p_half, ncl, status_dev);
+  if (int rc = seq_status_device(&status_dev)) return rc;
+  hipLaunchKernelGGL(k_lstm_seq_bwd<H>, dim3((unsigned)g.workgroups), dim3(256), g.lds_bytes, st, a, (unsigned*)workspace,
+                     (float*)((char*)workspace + g.counter_bytes), g.x_half_floats, g.nclusters, status_dev);
   MIRL_LAUNCH_CHECK();
   return MIRL_OK;
 }
@@ -744,14 +763,14 @@ static int seq_bwd_launch(const SeqBwdArgs& a, void* workspace, hipStream_t st) 
 using namespace mirl;
 
 extern "C" int mirl_lstm_seq_bwd_supported(int32_t T, int32_t B, int32_t H) {
-  // the partial blocks of a sweep must fit 32-bit buffer offsets: 2 x (B / 16) x 1 MiB
-  return (T >= 1 && B >= 16 && B % 16 == 0 && H == 512 && (int64_t)(B / 16) * 2 * 1048576 < 2147483648LL) ? 1 : 0;
+  // the partial blocks of a sweep (both halves) must fit 32-bit buffer offsets: 2 x (B / 16) x 1 MiB
+  return (T >= 1 && B >= 16 && B % 16 == 0 && H == 512 &&
+          2 * seq_bwd_sizes(B, H).x_half_floats * (int64_t)sizeof(float) < 2147483648LL) ? 1 : 0;
 }
 
 extern "C" int mirl_lstm_seq_bwd_workspace_bytes(int32_t B, int32_t H, int64_t* bytes) {
   if (!bytes || B <= 0 || H != 512 || B % 16) return fail(MIRL_ERR_ARG, "bad lstm_seq_bwd_workspace_bytes arguments");
-  const int64_t tiles = B / 16, ncg = H / 16;
-  *bytes = (int64_t)align_up((size_t)tiles * 32 * sizeof(unsigned), 256) + 2 * tiles * ncg * ncg * 256 * (int64_t)sizeof(float);
+  *bytes = (int64_t)seq_bwd_sizes(B, H).workspace_bytes;
   return MIRL_OK;
 }
 
@@ -760,12 +779,8 @@ extern "C" int mirl_lstm_seq_bwd(int32_t T, int32_t B, int32_t H, float* gates, 
   if (!mirl_lstm_seq_bwd_supported(T, B, H)) return fail(MIRL_ERR_ARG, "lstm_seq_bwd: unsupported shape (B multiple of 16, H = 512)");
   if (!gates || !w_hh || !c_all || !cm || !keep || !workspace || ((uintptr_t)workspace % 256))
     return fail(MIRL_ERR_ARG, "bad lstm_seq_bwd arguments");
-  int rc = seq_init();
-  if (rc) return rc;
-  if (*(volatile int*)g_seq_status) {
-    *g_seq_status = 0;
-    return fail(MIRL_ERR_STATE, "an earlier lstm_seq launch gave up waiting for a peer workgroup (results of that sweep are invalid)");
-  }
+  if (int rc = seq_take_status("an earlier lstm_seq launch gave up waiting for a peer workgroup (results of that sweep are invalid)"))
+    return rc;
   SeqBwdArgs a{T, B, gates, w_hh, c_all, cm, d_out, keep};
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps("k_lstm_seq_bwd", 4.0 * B * H * T * (8.0 + 3.0) + 4.0 * 4.0 * H * H, st, 2.0 * B * H * 4.0 * H * T);
@@ -778,8 +793,7 @@ extern "C" int mirl_lstm_seq_supported(int32_t T, int32_t B, int32_t H) {
 
 extern "C" int mirl_lstm_seq_workspace_bytes(int32_t B, int32_t H, int64_t* bytes) {
   if (!bytes || B <= 0 || H <= 0 || B % 16 || H % 16) return fail(MIRL_ERR_ARG, "bad lstm_seq_workspace_bytes arguments");
-  const int64_t tiles = B / 16;
-  *bytes = (int64_t)align_up((size_t)tiles * 32 * sizeof(unsigned), 256) + 3 * tiles * (H / 16) * 256 * (int64_t)sizeof(float);
+  *bytes = (int64_t)seq_fwd_sizes(B, H).workspace_bytes;
   return MIRL_OK;
 }
 
@@ -790,12 +804,9 @@ extern "C" int mirl_lstm_seq_fwd(int32_t T, int32_t B, int32_t H, float* gx, con
   if (!gx || !w_hh || !h0 || !c0 || !keep || !workspace || (!hm != !cm) || (!h_last != !c_last) || (!hm && !h_last))
     return fail(MIRL_ERR_ARG, "bad lstm_seq_fwd arguments");
   if (!aligned16(w_hh) || ((uintptr_t)workspace % 256)) return fail(MIRL_ERR_ARG, "lstm_seq_fwd needs a 16-byte aligned w_hh and a 256-byte aligned workspace");
-  int rc = seq_init();
-  if (rc) return rc;
-  if (*(volatile int*)g_seq_status) {
-    *g_seq_status = 0;
-    return fail(MIRL_ERR_STATE, "an earlier lstm_seq_fwd launch gave up waiting for a peer workgroup — or its recurrent state became non-finite, which the tagged exchange cannot carry (results of that sweep are invalid)");
-  }
+  if (int rc = seq_take_status("an earlier lstm_seq_fwd launch gave up waiting for a peer workgroup — or its recurrent state became "
+                               "non-finite, which the tagged exchange cannot carry (results of that sweep are invalid)"))
+    return rc;
   SeqFwdArgs a{T, B, gx, w_hh, h0, c0, keep, out, c_all, hm, cm, h_last, c_last, save_gates ? 1 : 0};
   hipStream_t st = (hipStream_t)stream;
   // per step: pre-activations read (+ activated gates written), h / c outputs; HBM-side algorithmic bytes of the sweep
@@ -806,40 +817,28 @@ extern "C" int mirl_lstm_seq_fwd(int32_t T, int32_t B, int32_t H, float* gx, con
   return seq_launch<128>(a, workspace, st);
 }
 
-// The forward sweep's launch geometry (what seq_launch picks): how many workgroups must be CO-RESIDENT for the sweep's
-// exchange to make progress, their LDS, and how many of them one compute unit can hold.  Callers that want two sweeps in
-// flight at once (two streams) use it to check that both grids fit the chip together.
+// The forward sweep's launch geometry, read from the seq_fwd_geometry that seq_launch launches with: how many workgroups
+// must be CO-RESIDENT for the sweep's exchange to make progress, their LDS, and how many of them one compute unit can hold.
+// Callers that want two sweeps in flight at once (two streams) use it to check that both grids fit the chip together.
 extern "C" int mirl_lstm_seq_fwd_grid(int32_t B, int32_t H, int32_t* workgroups, int64_t* lds_bytes, int32_t* compute_units,
                                       int32_t* per_compute_unit) {
   if (!workgroups || !lds_bytes || !compute_units || !per_compute_unit || !mirl_lstm_seq_supported(2, B, H))
     return fail(MIRL_ERR_ARG, "bad lstm_seq_fwd_grid arguments");
-  int rc = seq_init();
-  if (rc) return rc;
-  const int NCG = H / 16, nrb = (B + 63) / 64;
-  int64_t lds;
-  if (seq_narrow(nrb, H)) {
-    *workgroups = nrb * (H / 4);
-    lds = (int64_t)(16 * (H + 4) + 4 * 64) * (int64_t)sizeof(float);
-  } else {
-    int ncl = cu_count() / NCG;
-    if (ncl > nrb) ncl = nrb;
-    *workgroups = ncl * NCG;
-    lds = (int64_t)(64 * (H + 4) + 4 * 16 * SQ_TP) * (int64_t)sizeof(float);
-  }
-  *lds_bytes = lds;
+  if (int rc = seq_init()) return rc;
+  const SeqGrid g = seq_fwd_geometry(B, H);
+  *workgroups = g.workgroups;
+  *lds_bytes = (int64_t)g.lds_bytes;
   *compute_units = cu_count();
-  int64_t per = (160 * 1024) / (lds > 0 ? lds : 1);
-  if (per > 8) per = 8;                       // 32 waves per compute unit, 4 per workgroup
-  *per_compute_unit = (int32_t)per;
+  *per_compute_unit = g.per_compute_unit;
   return MIRL_OK;
 }
 
 extern "C" int mirl_lstm_seq_status_device(const int32_t** p) {
   using namespace mirl;
   if (!p) return fail(MIRL_ERR_ARG, "bad lstm_seq_status_device arguments");
-  int rc = seq_init(); if (rc) return rc;          // allocates the word when no sweep has run yet: not inside a capture
+  if (int rc = seq_init()) return rc;              // allocates the word when no sweep has run yet: not inside a capture
   int* dev = nullptr;
-  MIRL_HIP(hipHostGetDevicePointer((void**)&dev, g_seq_status, 0));
+  if (int rc = seq_status_device(&dev)) return rc;
   *p = dev;
   return MIRL_OK;
 }

@@ -7,11 +7,20 @@ Same recurrence as the reference's LSTMCell time loop with per-step reset
     gates = W_ih x(t) + b_ih + W_hh h_in + b_hh       (i, f, g, o)
     c(t) = sig(f) c_in + sig(i) tanh(g) ; h(t) = sig(o) tanh(c(t))
 
-but the input projection of all T steps is ONE GEMM, a forward step is one rocBLAS
-GEMM accumulated IN PLACE onto its slice of that projection + one fused cell kernel
-(csrc/lstm.hip mirl_lstm_cell_fwd), a backward step one cell
-kernel (mirl_lstm_cell_bwd) + one rocBLAS GEMM, and the weight
-gradients of W_ih and W_hh are one GEMM each over all timesteps after the
+but the input projection of all T steps is ONE GEMM (csrc/gemm3.hip; extra-feature
+columns are added by csrc/lstm_extras.hip), and the time loop over it is
+
+  * one persistent launch per sweep (csrc/lstm_seq.hip: W_hh resident in LDS, h
+    exchanged between workgroups inside the launch) wherever the shape is covered:
+    forward for H in {128, 256, 512} and T >= 2, backward for H = 512 and
+    B <= _BWD_PERSISTENT_MAX_B; check_status() reports a sweep that gave up and
+    two_sweeps_fit() says whether two forward grids may share the chip;
+  * else the per-step path: a forward step is one rocBLAS GEMM accumulated IN PLACE
+    onto its slice of the projection + one fused cell kernel (csrc/lstm.hip
+    mirl_lstm_cell_fwd), a backward step one cell kernel (mirl_lstm_cell_bwd) + one
+    rocBLAS GEMM.
+
+The weight gradients of W_ih and W_hh are one GEMM each over all timesteps after the
 backward sweep.
 """
 import ctypes as C
@@ -68,6 +77,19 @@ def two_sweeps_fit(B, H):
     return 2 * wg.value <= cus.value * per.value
 
 
+def _sweep_workspace(query, B, H, dev):
+    """The workspace of one persistent sweep: `query` (mirl_lstm_seq[_bwd]_workspace_bytes) says how large.  It stays
+    allocated until the launch that the caller now enqueues on the current stream has run: record_stream is called here,
+    before that launch, which is equivalent (the allocator looks at the recorded streams when the tensor is freed).  Both
+    sweeps assert the 256-byte alignment that the entry points require (torch aligns its blocks to 512)."""
+    nbytes = C.c_int64()
+    check(query(B, H, C.byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    assert ws.data_ptr() % 256 == 0
+    ws.record_stream(torch.cuda.current_stream())
+    return ws
+
+
 def _forward_sweep(gates, w, h0, c0, keep, need_grad):
     """The time loop over `gates` (T, B, 4H) = the input projection (+ biases), in place.
     Returns (out, hm, cm, c_all, h_last, c_last); hm / cm / c_all are None unless need_grad
@@ -78,10 +100,7 @@ def _forward_sweep(gates, w, h0, c0, keep, need_grad):
     out = torch.empty((T, B, H), dtype=torch.float32, device=dev)
     st = stream()
     if persistent_supported(T, B, H) and w.data_ptr() % 16 == 0:
-        nbytes = C.c_int64()
-        check(lib.mirl_lstm_seq_workspace_bytes(B, H, C.byref(nbytes)))
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        assert ws.data_ptr() % 256 == 0
+        ws = _sweep_workspace(lib.mirl_lstm_seq_workspace_bytes, B, H, dev)
         hm = cm = c_all = h_last = c_last = None
         if need_grad:
             hm = torch.empty((T + 1, B, H), dtype=torch.float32, device=dev)
@@ -93,7 +112,6 @@ def _forward_sweep(gates, w, h0, c0, keep, need_grad):
         check(lib.mirl_lstm_seq_fwd(
             T, B, H, ptr(gates), ptr(w), ptr(h0), ptr(c0), ptr(keep), ptr(out), ptr(c_all), ptr(hm), ptr(cm),
             ptr(h_last), ptr(c_last), 1 if need_grad else 0, ptr(ws), st), "mirl_lstm_seq_fwd")
-        ws.record_stream(torch.cuda.current_stream())
         if need_grad:
             h_last, c_last = hm[T], cm[T]
         return out, hm, cm, c_all, h_last, c_last
@@ -121,12 +139,9 @@ def _backward_sweep(gates, c_all, cm, d_out, keep, w):
     st = stream()
     if _PERSISTENT and T >= 2 and B <= _BWD_PERSISTENT_MAX_B and lib.mirl_lstm_seq_bwd_supported(T, B, H) \
             and w.data_ptr() % 16 == 0:
-        nbytes = C.c_int64()
-        check(lib.mirl_lstm_seq_bwd_workspace_bytes(B, H, C.byref(nbytes)))
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=gates.device)
+        ws = _sweep_workspace(lib.mirl_lstm_seq_bwd_workspace_bytes, B, H, gates.device)
         check(lib.mirl_lstm_seq_bwd(T, B, H, ptr(gates), ptr(w), ptr(c_all), ptr(cm), ptr(d_out), ptr(keep), ptr(ws), st),
               "mirl_lstm_seq_bwd")
-        ws.record_stream(torch.cuda.current_stream())
         return
     dh_rec = torch.empty((B, H), dtype=torch.float32, device=gates.device)
     dc_rec = torch.empty((B, H), dtype=torch.float32, device=gates.device)
@@ -224,7 +239,6 @@ class _LSTMSequence(torch.autograd.Function):
         # `track`: decided by the caller from torch.is_grad_enabled() — inside forward() grad mode is
         # always off and ctx.needs_input_grad mirrors requires_grad even in a no_grad pass
         need_grad = track and (any(ctx.needs_input_grad[:4]) or ctx.needs_input_grad[9])
-        dev = x.device
         # with extras: x holds the F feature columns only and w_ih = W_ih[:, :F]; the X extra columns are added to the
         # K = F product in place (csrc/lstm_extras.hip) — the (T*B, F + X) block is never formed
         gates = gemm3.linear_fwd(x, w_ih.float(), bias.float().contiguous())
@@ -269,7 +283,6 @@ class _LSTMSequenceFromProjection(torch.autograd.Function):
         w = w_hh.float().contiguous()
         keep = keep.float().contiguous()
         need_grad = track and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[7])
-        dev = gx.device
         if extra is not None:
             extra = _compact(extra)
             gates = extras_add(gx.reshape(T * B, G), extra, w_x).view(T, B, G)      # a fresh buffer: gx stays as it is
