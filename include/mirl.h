@@ -906,6 +906,26 @@ int mirl_catch_env_step_pre(int32_t E, int32_t P, int32_t S, int32_t G, int32_t 
  * 16-byte aligned, else MIRL_ERR_ARG before any launch.                                                                  */
 int mirl_cartpole_env_step(int32_t E, int32_t max_episode_steps, const int32_t* actions, void* state, uint64_t seed,
                            int32_t reset_all, float* obs, float* rewards, uint8_t* dones, void* stream);
+/* One step of MountainCarContinuous-v0 as a device-native vector env (csrc/acting.hip k_mountaincar_env_step): one thread per
+ * env, float64, on the plan of mirl_cartpole_env_step.  `state` is [E] 32-byte records {double p = position; double v =
+ * velocity; int64 episodes_started; int32 t; int32 pad} read and written IN PLACE, so the launch replays from a captured
+ * graph.  actions float32 [E] (one raw, unbounded component per env).  Transition (every operation IEEE float64 in this
+ * order, nothing contracted), a = (double)action:
+ *   f = a < -1 ? -1 : (a > 1 ? 1 : a)
+ *   v = v + (f * 0.0015 - 0.0025 * C(3.0 * p));  v = min(v, 0.07), then max(v, -0.07)
+ *   p = p + v;  p = min(p, 0.6), then max(p, -1.2);  if p == -1.2 and v < 0: v = 0
+ *   goal = p >= 0.45 and v >= 0;  t += 1;  reward = (float)((goal ? 100.0 : 0.0) - (a * a) * 0.1)  — the RAW action's cost
+ *   done = goal or t >= max_episode_steps
+ * C(x) = the Taylor polynomial of cos in z = x * x through x^34, Horner from -1/34! down to the constant 1, coefficients
+ * +-1/k! as float64 — not libm; |C(x) - cos(x)| < 7.6e-14 on [-3.6, 1.8] (derived at the kernel).  A finished env starts its
+ * next episode in the same step and returns the NEW episode's first observation with done = 1:
+ * p = ((double)w_0 + 0.5) * 2^-32 * 0.2 - 0.6 (uniform in [-0.6, -0.4)) from word 0 of Philox4x32-10 with key
+ * seed ^ 0xC0A7CA2E and counter (episodes_started, env), v = 0, then episodes_started += 1, t = 0.  reset_all = 1: every env
+ * starts an episode that way; rewards 0, dones 1; actions may be NULL.  obs float32 [E][2] = (p, v) rounded to nearest,
+ * rewards float32 [E], dones uint8 [E].  1 <= E <= 2^24, max_episode_steps >= 1, state 16-byte aligned, else MIRL_ERR_ARG
+ * before any launch.                                                                                                     */
+int mirl_mountaincar_env_step(int32_t E, int32_t max_episode_steps, const float* actions, void* state, uint64_t seed,
+                              int32_t reset_all, float* obs, float* rewards, uint8_t* dones, void* stream);
 int mirl_episode_track(int32_t E, int32_t A, const float* rewards, const uint8_t* dones,
                        const int32_t* actions, float* ep_reward, int32_t* ep_len,
                        float* out_reward, int32_t* out_len, int32_t* action_counts, void* stream);
@@ -1077,6 +1097,43 @@ int mirl_ac_loss(int64_t M, int32_t A, const float* logits, int64_t pitch, const
                  const float* targets, const float* acting_values, const float* old_log_probs, double vf_coef,
                  double entropy_factor, double clip_value, int32_t adv_norm, float* dlogits, int64_t dpitch, float* dvalues,
                  float* log_probs, float* stats, void* stream);
+
+/* ---- the same three for a Box action space: the Normal head (distributions/normal.py:9-36) --------------------------
+ * D = action components, 1 <= D <= 16; logstd [D] is state-independent.  Component d of a float32 action a contributes
+ *   term_d = -(double(a_d) - double(mean_d))^2 / (2 exp(2 logstd_d)) - logstd_d - log(2 pi) / 2        (float64)
+ * and the joint log-probability is float32(sum_d term_d), the terms added in ascending d, ONE rounding — the same sequence
+ * in the head and in the loss, so a row re-evaluated with unchanged weights gives the head's float32 back.
+ *
+ * The sampling head, one thread per env: mean [E] rows of D floats `pitch` apart, values [E], eps [E][D] standard-normal
+ * draws made by the caller (the kernel is deterministic).  actions[e][d] = float32(mean_d + exp(logstd_d) * eps_d) (float64,
+ * one rounding) and the log-probability is that of the ROUNDED action: torch evaluates log_prob of the sampled float32
+ * tensor, and the learner later sees that tensor.  The [log-probability | value] outputs are mirl_actor_head_ac's.  There
+ * is no greedy mode (the reference's force_best fails for a Box space).  1 <= E <= 2^24, pitch >= D, out_pitch >= 1.   */
+int mirl_actor_head_normal(int32_t E, int32_t D, const float* mean, int64_t pitch, const float* logstd, const float* values,
+                           const float* eps, float* actions, float* action_log_probs, float* values_out, int32_t out_pitch,
+                           void* stream);
+/* mirl_online_window with vector actions: actions_ring [cap][E][action_words] and actions [T * B][action_words] are opaque
+ * 4-byte words (the float32 components of a Box action) gathered exactly; everything else is mirl_online_window's, which is
+ * this entry with action_words = 1 — one kernel body.  1 <= action_words <= 16.                                        */
+int mirl_online_window_box(int32_t T, int32_t B, int32_t E, int32_t cap, int32_t nstep_target, double gamma, double lam,
+                           int64_t obs_bytes, const int32_t* plan, const void* obs_ring, const void* actions_ring,
+                           const float* rewards_ring, const uint8_t* dones_ring, const float* logp_ring, const float* values_ring,
+                           int32_t pol_pitch, float* returns, float* nsteps, float* target_masks, void* actions,
+                           float* action_log_probs, float* values, void* states, void* target_states, int32_t action_words,
+                           void* stream);
+/* mirl_ac_loss under the Normal head, ONE launch of one workgroup: mean [M][D] (`pitch` apart), logstd [D], actions
+ * float32 [M][D]; advantages, gains (A2C / PPO with autograd's tie rules), value loss and stats are mirl_ac_loss's — the
+ * same code.  The entropy of component d is 1/2 + log(2 pi) / 2 + logstd_d; the reference takes .mean() over the un-summed
+ * [M][D] entropies (a2c.py:113), so the entropy term is the MEAN over the components: stats[3] = sum_d (..) / D.
+ * With w_i = d loss / d logp_i and s2_d = exp(2 logstd_d), diff = a - mean:
+ *   dmean[i][d] = float32(w_i * diff_d / s2_d)                                          (`dpitch` apart)
+ *   dlogstd[d]  = float32(sum_i w_i * (diff_d^2 / s2_d - 1)  -  entropy_factor / D)     per thread in ascending rows, then
+ *                 the fixed tree: no atomics, a second launch repeats the first bit for bit
+ * dvalues [M], log_probs [M] (may be NULL), stats [5] as in mirl_ac_loss.  1 <= M <= 2^22, M >= 2 with adv_norm.       */
+int mirl_ac_loss_normal(int64_t M, int32_t D, const float* mean, int64_t pitch, const float* logstd, const float* values,
+                        const float* actions, const float* targets, const float* acting_values, const float* old_log_probs,
+                        double vf_coef, double entropy_factor, double clip_value, int32_t adv_norm, float* dmean, int64_t dpitch,
+                        float* dlogstd, float* dvalues, float* log_probs, float* stats, void* stream);
 
 #ifdef __cplusplus
 }

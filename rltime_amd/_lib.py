@@ -237,6 +237,11 @@ _SIGNATURES = {
     "mirl_online_window": [_i32, _i32, _i32, _i32, _i32, _f64, _f64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
                            _vp, _vp, _vp, _vp, _vp],
     "mirl_ac_loss": [_i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _i32, _vp, _i64, _vp, _vp, _vp, _vp],
+    "mirl_actor_head_normal": [_i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
+    "mirl_online_window_box": [_i32, _i32, _i32, _i32, _i32, _f64, _f64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                               _vp, _vp, _vp, _vp, _vp, _i32, _vp],
+    "mirl_ac_loss_normal": [_i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _i32, _vp, _i64, _vp, _vp, _vp, _vp,
+                            _vp],
     "mirl_stack_shift": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "mirl_synth_env_step": [_i32, _i64, _vp, _i32, _vp, _i32, _u64, C.c_float, C.c_float, C.c_float, _vp, _vp, _vp, _vp],
     "mirl_synth_env_step_pre": [_i32, _i64, _vp, _i32, _vp, _i32, _u64, C.c_float, C.c_float, C.c_float, _vp, _vp, _vp,
@@ -245,6 +250,7 @@ _SIGNATURES = {
     "mirl_catch_env_step_pre": [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _u64, _i32, _vp, _vp, _vp,
                                 _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp],
     "mirl_cartpole_env_step": [_i32, _i32, _vp, _vp, _u64, _i32, _vp, _vp, _vp, _vp],
+    "mirl_mountaincar_env_step": [_i32, _i32, _vp, _vp, _u64, _i32, _vp, _vp, _vp, _vp],
     "mirl_actor_pre": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
                        _vp, _vp, _u64, _vp],
     "mirl_episode_track": [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

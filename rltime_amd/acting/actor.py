@@ -277,6 +277,16 @@ class Actor(ActingInterface):
         value] where the Q-learning path returns its q-values, so the vector steps carry both policy outputs to the
         history.  The policy samples for itself: exploration configs are ignored, as in the reference."""
         from rltime_amd._lib import lib, check, ptr as p, stream
+        if self._policy.has_normal_head():
+            # a Box action space: float32 actions [E, D] from the Normal head's kernel, on torch.randn draws
+            mean, logstd, values = self._policy.actor_head_normal_raw(state, 1)
+            E, D = mean.shape
+            eps = torch.randn((E, D), device=mean.device)
+            actions = torch.empty((E, D), dtype=torch.float32, device=mean.device)
+            block = torch.empty((E, 2), dtype=torch.float32, device=mean.device)
+            check(lib.mirl_actor_head_normal(E, D, p(mean), mean.stride(0), p(logstd), p(values), p(eps), p(actions), p(block),
+                                             p(block[:, 1]), 2, stream()), "mirl_actor_head_normal")
+            return actions, block
         logits, values = self._policy.actor_head_ac_raw(state, 1)
         E, A = logits.shape
         dev = logits.device
@@ -386,8 +396,11 @@ class Actor(ActingInterface):
                 # episode reward / length and the action histogram on the device
                 # (policy_trainer.py:75-131), one launch per vector step
                 if self._tracker is None:
-                    from .episode_tracker import EpisodeTracker
-                    self._tracker = EpisodeTracker(self._num_envs, self._action_space.n, rewards.device)
+                    from .episode_tracker import BoxEpisodeTracker, EpisodeTracker
+                    if hasattr(self._action_space, "n"):
+                        self._tracker = EpisodeTracker(self._num_envs, self._action_space.n, rewards.device)
+                    else:               # Box actions: the mean of each component instead of the histogram
+                        self._tracker = BoxEpisodeTracker(self._num_envs, int(np.prod(self._action_space.shape)), rewards.device)
                     if getattr(self, "_tracker_restore", None) is not None:
                         self._tracker.set_state(self._tracker_restore)
                         self._tracker_restore = None

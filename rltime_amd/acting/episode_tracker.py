@@ -112,3 +112,31 @@ class EpisodeTracker:
         last = getattr(self, "_counts_read", None)
         self._counts_read = now
         return (now if last is None else now - last).tolist()
+
+
+class BoxEpisodeTracker(EpisodeTracker):
+    """The tracker for a Box action space: episode rewards / lengths as above (the kernel takes no actions), and beside
+    them what the reference logs in the histogram's place (policy_trainer.py:148-160, :72-81) — the sum of every action
+    component over the acted transitions, accumulated on the device in float64, and their count."""
+
+    def __init__(self, num_envs, action_dims, device):
+        super().__init__(num_envs, 0, device)
+        self.D = int(action_dims)
+        self.action_sums = torch.zeros(self.D + 1, dtype=torch.float64, device=device)      # [D] sums | transitions counted
+
+    def step(self, rewards, dones_u8, actions_f32):
+        """One vector step: raw rewards (f32 [E]), dones (u8 [E]), actions (f32 [E, D])."""
+        super().step(rewards, dones_u8, None)
+        self.action_sums[:self.D] += actions_f32.reshape(self.E, self.D).sum(dim=0, dtype=torch.float64)
+        self.action_sums[self.D] += self.E
+
+    def take_action_counts(self):
+        return []
+
+    def take_action_sums(self):
+        """(per-component sums, transitions) since the last call (synchronises: log-interval use only)."""
+        now = self.action_sums.cpu()
+        last = getattr(self, "_sums_read", None)
+        self._sums_read = now
+        diff = (now if last is None else now - last).tolist()
+        return diff[:self.D], int(diff[self.D])

@@ -99,6 +99,9 @@ class _ConstantEpsilon(EpsilonGreedyExplorationManager):
 
 class Evaluator:
     def __init__(self, policy, env, episode_count, eps=0.0, seed=0, steps_per_launch=32):
+        if not hasattr(getattr(env, "action_space", None), "n"):
+            raise ValueError("Evaluator: the env's action space %r is not Discrete; the evaluation is greedy (arg-max) and the "
+                             "reference's has no greedy mode for a Box space either" % (getattr(env, "action_space", None),))
         if not getattr(policy, "is_cuda", lambda: False)():
             raise ValueError("Evaluator: the policy is on the CPU; evaluation runs the device actor (a GPU policy) only")
         if not hasattr(env, "step_device") or torch.device(getattr(env, "device", "cpu")).type != "cuda":

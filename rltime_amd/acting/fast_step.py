@@ -108,6 +108,8 @@ class FastActingStep:
         try:
             if not pol.is_cuda():
                 return False
+            if not hasattr(actor._action_space, "n") or hasattr(pol, "actor_head_ac_raw"):
+                return False                      # Box actions and actor-critic heads act on the generic device path
             parts = FastActingStep._parts(pol)
             if parts is None:
                 return False

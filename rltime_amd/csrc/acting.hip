@@ -351,6 +351,87 @@ k_cartpole_env_step(int E, int max_steps, int reset_all, const int32_t* __restri
   dones[e] = (uint8_t)dn;
 }
 
+// One step of MountainCarContinuous-v0 as a device-native vector env (acting/mountaincar_device_env.py): the car of
+// acting/mountaincar_env.py (Moore 1990; gym's Continuous_MountainCarEnv) in float64, one thread per env, on the plan of
+// k_cartpole_env_step: ONE 32-byte record per env {p, v, episodes_started, t, pad} updated in place, no clock, no atomics,
+// a fixed launch on caller-owned buffers that captures as it is.  The action is ONE raw float32 per env, unbounded: the
+// force is its clip to [-1, 1], the reward's cost term takes the raw value.
+// cos(3p) is a fixed polynomial, not libm: x = 3.0 * p lies in [-3.6, 1.8], too wide for the cart-pole's nine terms, so it
+// is the Taylor series of cos in z = x * x through x^34 (17 coefficients +-1/k! below the constant 1), Horner from the
+// highest down.  Error against the exact cos(x) for |x| <= 3.6, u = 2^-53:
+//   truncation        3.6^36 / 36! / (1 - 3.6^2 / (37 * 38))                      <  3e-22
+//   Horner rounding   gamma_35 * sum_k |c_k| |z|^k <= 35 u / (1 - 35 u) * cosh(3.6)   <  7.12e-14   (17 multiply-adds = 34
+//                     roundings, one more for the rounded coefficients; Higham, Accuracy and Stability, section 5.1)
+//   z = fl(x * x)     |z p'(z)| u = |x| sinh|x| / 2 * u                           <  3.7e-15
+// so |mountaincar_cos(x) - cos(x)| < 7.5e-14 (the measured worst case is 1.6e-15: the a-priori bound is pessimistic); against
+// libm's cos, itself within one ulp (1.2e-16) of the exact value, the stated bound is 7.6e-14.  tests/mountaincar_restate.py
+// restates these lines in NumPy bit for bit (the build compiles with -ffp-contract=off).
+struct MountainCarRecord { double p, v; int64_t episodes_started; int32_t t; int32_t pad; };
+static_assert(sizeof(MountainCarRecord) == 32, "the record is 32 bytes: two 16-byte vectors");
+
+__device__ __forceinline__ double mountaincar_cos(double x) {
+  const double z = x * x;
+  double p = -3.387157535521162e-39;                     // -1/34!
+  p = p * z + 3.800390754854744e-36;                     // +1/32!
+  p = p * z + -3.7699876288159054e-33;                   // -1/30!
+  p = p * z + 3.279889237069838e-30;                     // +1/28!
+  p = p * z + -2.4795962632247972e-27;                   // -1/26!
+  p = p * z + 1.6117375710961184e-24;                    // +1/24!
+  p = p * z + -8.896791392450574e-22;                    // -1/22!
+  p = p * z + 4.110317623312165e-19;                     // +1/20!
+  p = p * z + -1.5619206968586225e-16;                   // -1/18!
+  p = p * z + 4.779477332387385e-14;                     // +1/16!
+  p = p * z + -1.1470745597729725e-11;                   // -1/14!
+  p = p * z + 2.08767569878681e-09;                      // +1/12!
+  p = p * z + -2.755731922398589e-07;                    // -1/10!
+  p = p * z + 2.48015873015873e-05;                      // +1/8!
+  p = p * z + -0.001388888888888889;                     // -1/6!
+  p = p * z + 0.041666666666666664;                      // +1/4!
+  p = p * z + -0.5;                                      // -1/2!
+  p = p * z + 1.0;
+  return p;
+}
+
+__global__ void __launch_bounds__(64)
+k_mountaincar_env_step(int E, int max_steps, int reset_all, const float* __restrict__ actions, MountainCarRecord* __restrict__ state,
+                       uint64_t seed, float* __restrict__ obs, float* __restrict__ rewards, uint8_t* __restrict__ dones) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= E) return;
+  MountainCarRecord s = state[e];
+  int dn = 1;
+  float rr = 0.0f;
+  if (!reset_all) {
+    const double a = (double)actions[e];
+    const double f = a < -1.0 ? -1.0 : (a > 1.0 ? 1.0 : a);
+    double v = s.v + (f * 0.0015 - 0.0025 * mountaincar_cos(3.0 * s.p));
+    if (v > 0.07) v = 0.07;
+    if (v < -0.07) v = -0.07;
+    double p = s.p + v;
+    if (p > 0.6) p = 0.6;
+    if (p < -1.2) p = -1.2;
+    if (p == -1.2 && v < 0.0) v = 0.0;
+    const int goal = (p >= 0.45 && v >= 0.0) ? 1 : 0;
+    s.p = p;
+    s.v = v;
+    s.t += 1;
+    rr = (float)((goal ? 100.0 : 0.0) - (a * a) * 0.1);     // the RAW action's cost; formed in float64, rounded once
+    dn = (goal || s.t >= max_steps) ? 1 : 0;
+  }
+  if (dn) {                                             // a new episode starts in the same step
+    uint32_t r[4];
+    philox_4x32(seed ^ 0xC0A7CA2Eull, (uint64_t)s.episodes_started, (uint32_t)e, r);
+    s.p = ((double)r[0] + 0.5) * 2.3283064365386963e-10 * 0.2 - 0.6;      // 2^-32: uniform in [-0.6, -0.4)
+    s.v = 0.0;
+    s.episodes_started += 1;
+    s.t = 0;
+  }
+  state[e] = s;
+  obs[2 * (long)e] = (float)s.p;
+  obs[2 * (long)e + 1] = (float)s.v;
+  rewards[e] = rr;
+  dones[e] = (uint8_t)dn;
+}
+
 // The reference evaluation's counting rule (rltime/eval.py:59-72, loop :113-149) as ONE launch per vector step: of E
 // envs in parallel, the first N episodes that STARTED are counted, in the order the host loop meets them — step by
 // step, env by env — and an env's mask closes when the running count of started episodes passes N.  The sequential
@@ -597,6 +678,20 @@ extern "C" int mirl_cartpole_env_step(int32_t E, int32_t max_episode_steps, cons
   mirl::ProfScope ps("k_cartpole_env_step", (double)E * (2.0 * 48.0 + 16.0 + 4.0 + 1.0 + 4.0), (hipStream_t)stream);
   hipLaunchKernelGGL(mirl::k_cartpole_env_step, dim3((E + 63) / 64), dim3(64), 0, (hipStream_t)stream, (int)E, (int)max_episode_steps,
                      (int)reset_all, actions, (mirl::CartPoleRecord*)state, seed, (float4*)obs, rewards, dones);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
+extern "C" int mirl_mountaincar_env_step(int32_t E, int32_t max_episode_steps, const float* actions, void* state, uint64_t seed,
+                                         int32_t reset_all, float* obs, float* rewards, uint8_t* dones, void* stream) {
+  // (E <= 2^24 keeps the grid and every byte offset far inside 32 bits)
+  if (E <= 0 || E > (1 << 24) || max_episode_steps < 1 || (reset_all != 0 && reset_all != 1) || (!reset_all && !actions) || !state ||
+      !obs || !rewards || !dones || !mirl::aligned16(state))
+    return mirl::fail(MIRL_ERR_ARG, "bad mountaincar_env_step arguments (1 <= E <= 2^24, max_episode_steps >= 1, reset_all 0 | 1, "
+                                    "16-byte aligned state)");
+  mirl::ProfScope ps("k_mountaincar_env_step", (double)E * (2.0 * 32.0 + 8.0 + 4.0 + 1.0 + 4.0), (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_mountaincar_env_step, dim3((E + 63) / 64), dim3(64), 0, (hipStream_t)stream, (int)E, (int)max_episode_steps,
+                     (int)reset_all, actions, (mirl::MountainCarRecord*)state, seed, obs, rewards, dones);
   MIRL_LAUNCH_CHECK();
   return MIRL_OK;
 }

@@ -1,6 +1,8 @@
 // actor_critic.hip — the actor-critic (A2C / PPO) part of the device path: the sampling head of a vector step, the
 // on-policy rollout window with its lambda-returns, and the loss with its gradients (include/mirl.h has the contracts).
-// All three are latency-sized: a few thousand rows of at most 64 actions.  Plain C++, float64 inside, one rounding to
+// Each exists for a Discrete action space (Categorical head, one int32 per action) and for a Box one (Normal head, up to 16
+// float32 components per action); what does not depend on the distribution is stated once and shared.
+// All are latency-sized: a few thousand rows of at most 64 actions.  Plain C++, float64 inside, one rounding to
 // float32 per output; no float atomics, every sum in a fixed order, so a rerun repeats the first run bit for bit.
 #include "common.hpp"
 
@@ -54,6 +56,40 @@ __global__ __launch_bounds__(64) void k_actor_head_ac(int E, int A, const float*
   values_out[(long)e * out_pitch] = values[e];
 }
 
+// ---- 1b. the Normal (continuous) head: independent Gaussians over a Box action, state-independent log-std ----------------
+// (policies/torch/distributions/normal.py:9-36).  The pieces the head and the loss share, the SAME sequence of operations in
+// both: component d of an action a (float32) under N(mean_d, exp(logstd_d)) contributes
+//   -(a_d - mean_d)^2 / (2 exp(2 logstd_d)) - logstd_d - log(2 pi) / 2
+// to the joint log-probability, the contributions added in ascending d and the sum rounded once to float32.
+constexpr int kMaxBoxDims = 16;
+constexpr double kHalfLog2Pi = 0.9189385332046727;      // log(2 pi) / 2, correctly rounded
+
+__device__ inline double normal_log_prob_term(double a, double mean, double logstd) {
+  const double diff = a - mean;
+  return -(diff * diff) / (2.0 * exp(2.0 * logstd)) - logstd - kHalfLog2Pi;
+}
+
+// One thread per env.  a_d = float32(mean_d + exp(logstd_d) eps_d) with eps the caller's standard-normal draws (the kernel
+// is deterministic); the log-probability is that of the ROUNDED action — torch evaluates log_prob of the sampled float32
+// tensor, and the learner later sees that tensor.
+__global__ __launch_bounds__(64) void k_actor_head_normal(int E, int D, const float* __restrict__ mean, long pitch,
+                                                          const float* __restrict__ logstd, const float* __restrict__ values,
+                                                          const float* __restrict__ eps, float* __restrict__ actions,
+                                                          float* __restrict__ logp, float* __restrict__ values_out, int out_pitch) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= E) return;
+  const float* m = mean + (long)e * pitch;
+  double lp = 0.0;
+  for (int d = 0; d < D; ++d) {
+    const double ls = (double)logstd[d];
+    const float a = (float)((double)m[d] + exp(ls) * (double)eps[(long)e * D + d]);
+    actions[(long)e * D + d] = a;
+    lp += normal_log_prob_term((double)a, (double)m[d], ls);
+  }
+  logp[(long)e * out_pitch] = (float)lp;
+  values_out[(long)e * out_pitch] = values[e];
+}
+
 // ---- 2. the on-policy window ---------------------------------------------------------------------------------------
 // One workgroup per (t, sequence): thread 0 walks the transition's return, all threads move its two observation rows.
 struct WindowArgs {
@@ -62,17 +98,17 @@ struct WindowArgs {
   long obs_bytes;
   const int* plan;                 // [B][3]: env, ring slot of the sequence's first transition, 1 = that transition is the env's first ever
   const unsigned char* obs_ring;   // [cap][E][obs_bytes]: next_state of the transition
-  const int* actions_ring;         // [cap][E]
+  const int* actions_ring;         // [cap][E][action_words]: opaque 4-byte words (one int32 action, or the float32 components of a Box one)
   const float* rewards_ring;
   const unsigned char* dones_ring;
   const float* logp_ring;          // [(slot E + env) pol_pitch]
   const float* values_ring;
   int pol_pitch;
   float *returns, *nsteps, *masks;
-  int* actions;
+  int* actions;                    // [T B][action_words]
   float *logp, *values;
   unsigned char *states, *target_states;
-  int vec16;
+  int vec16, action_words;
 };
 
 __device__ inline void copy_row(unsigned char* __restrict__ dst, const unsigned char* __restrict__ src, long bytes, int vec16) {
@@ -107,7 +143,7 @@ __global__ __launch_bounds__(256) void k_online_window(WindowArgs a) {
     a.returns[out] = (float)ret;
     a.nsteps[out] = (float)want;
     a.masks[out] = mask;
-    a.actions[out] = a.actions_ring[r0];
+    for (int w = 0; w < a.action_words; ++w) a.actions[out * a.action_words + w] = a.actions_ring[r0 * a.action_words + w];
     a.logp[out] = a.logp_ring[r0 * a.pol_pitch];
     a.values[out] = a.values_ring[r0 * a.pol_pitch];
   }
@@ -142,22 +178,71 @@ struct LossArgs {
   float* dlogits; long dpitch; float* dvalues; float* log_probs; float* stats;
 };
 
+// The parts of the loss that do not depend on the action distribution — stated once, used by the Categorical and the Normal
+// kernel: the advantage statistics, a row's advantage, its action gain with the coefficient of the log-probability's
+// gradient, its value terms, and the stats block.
+struct AdvNorm { double mean, denom; };
+
+__device__ inline AdvNorm advantage_stats(const float* __restrict__ targets, const float* __restrict__ acting_values, long M,
+                                          int adv_norm, double invM, double* lds) {
+  AdvNorm n;
+  n.mean = 0.0; n.denom = 1.0;
+  if (adv_norm) {
+    // torch: (adv - adv.mean()) / (adv.std() + 1e-5), the unbiased std; two passes, the second on the centred values
+    double s = 0.0;
+    for (long i = threadIdx.x; i < M; i += kLossThreads) s += (double)targets[i] - (double)acting_values[i];
+    n.mean = block_sum(s, lds) * invM;
+    double q = 0.0;
+    for (long i = threadIdx.x; i < M; i += kLossThreads) {
+      const double c = ((double)targets[i] - (double)acting_values[i]) - n.mean;
+      q += c * c;
+    }
+    n.denom = sqrt(block_sum(q, lds) / (double)(M - 1)) + 1e-5;
+  }
+  return n;
+}
+
+__device__ inline double row_advantage(const float* __restrict__ targets, const float* __restrict__ acting_values, long i,
+                                       int adv_norm, const AdvNorm& n) {
+  double adv = (double)targets[i] - (double)acting_values[i];
+  if (adv_norm) adv = (adv - n.mean) / n.denom;
+  return adv;
+}
+
+// gain_i and coef_i = d gain_i / d log-prob (before the 1 / M of the mean): A2C without old log-probabilities, else PPO's
+// clipped surrogate
+struct RowGain { double gain, coef; };
+
+__device__ inline RowGain row_gain(float lp32, double adv, const float* __restrict__ old_log_probs, long i, double lo, double hi) {
+  RowGain g;
+  if (!old_log_probs) {
+    g.gain = (double)lp32 * adv;
+    g.coef = adv;
+  } else {
+    const double ratio = exp((double)lp32 - (double)old_log_probs[i]);
+    const double s1 = ratio * adv, s2 = fmin(fmax(ratio, lo), hi) * adv;
+    g.gain = fmin(s1, s2);
+    // autograd: minimum() hands a tie half the gradient each way, clamp() passes it inside [lo, hi], bounds included
+    const bool inside = ratio >= lo && ratio <= hi;
+    const double share = inside ? 1.0 : (s1 < s2 ? 1.0 : (s1 == s2 ? 0.5 : 0.0));
+    g.coef = share * (ratio * adv);
+  }
+  return g;
+}
+
+__device__ inline void write_stats(float* __restrict__ stats, double vf_coef, double entropy_factor, double gain, double vl,
+                                   double ent, double val) {
+  stats[0] = (float)(vf_coef * vl - gain - entropy_factor * ent);
+  stats[1] = (float)vl;
+  stats[2] = (float)(-gain);
+  stats[3] = (float)ent;
+  stats[4] = (float)val;
+}
+
 __global__ __launch_bounds__(kLossThreads) void k_ac_loss(LossArgs a) {
   __shared__ double lds[kLossThreads];
   const double invM = 1.0 / (double)a.M;
-  double mean = 0.0, denom = 1.0;
-  if (a.adv_norm) {
-    // torch: (adv - adv.mean()) / (adv.std() + 1e-5), the unbiased std; two passes, the second on the centred values
-    double s = 0.0;
-    for (long i = threadIdx.x; i < a.M; i += kLossThreads) s += (double)a.targets[i] - (double)a.acting_values[i];
-    mean = block_sum(s, lds) * invM;
-    double q = 0.0;
-    for (long i = threadIdx.x; i < a.M; i += kLossThreads) {
-      const double c = ((double)a.targets[i] - (double)a.acting_values[i]) - mean;
-      q += c * c;
-    }
-    denom = sqrt(block_sum(q, lds) / (double)(a.M - 1)) + 1e-5;
-  }
+  const AdvNorm norm = advantage_stats(a.targets, a.acting_values, a.M, a.adv_norm, invM, lds);
   const double lo = 1.0 - a.clip_value, hi = 1.0 + a.clip_value;
   double s_gain = 0.0, s_vl = 0.0, s_ent = 0.0, s_val = 0.0;
   for (long i = threadIdx.x; i < a.M; i += kLossThreads) {
@@ -169,22 +254,9 @@ __global__ __launch_bounds__(kLossThreads) void k_ac_loss(LossArgs a) {
     const float lp32 = row_log_prob(z, act, r, logS);
     if (a.log_probs) a.log_probs[i] = lp32;
     const double H = logS - r.W / r.S;                          // -sum_j p_j log p_j
-    double adv = (double)a.targets[i] - (double)a.acting_values[i];
-    if (a.adv_norm) adv = (adv - mean) / denom;
-    // d gain_i / d log-prob (before the 1 / M of the mean)
-    double gain, coef;
-    if (!a.old_log_probs) {
-      gain = (double)lp32 * adv;
-      coef = adv;
-    } else {
-      const double ratio = exp((double)lp32 - (double)a.old_log_probs[i]);
-      const double s1 = ratio * adv, s2 = fmin(fmax(ratio, lo), hi) * adv;
-      gain = fmin(s1, s2);
-      // autograd: minimum() hands a tie half the gradient each way, clamp() passes it inside [lo, hi], bounds included
-      const bool inside = ratio >= lo && ratio <= hi;
-      const double share = inside ? 1.0 : (s1 < s2 ? 1.0 : (s1 == s2 ? 0.5 : 0.0));
-      coef = share * (ratio * adv);
-    }
+    const double adv = row_advantage(a.targets, a.acting_values, i, a.adv_norm, norm);
+    const RowGain rg = row_gain(lp32, adv, a.old_log_probs, i, lo, hi);
+    const double gain = rg.gain, coef = rg.coef;
     const double t = (double)a.targets[i], v = (double)a.values[i];
     s_gain += gain;
     s_vl += (t - v) * (t - v);
@@ -205,13 +277,73 @@ __global__ __launch_bounds__(kLossThreads) void k_ac_loss(LossArgs a) {
   const double vl = block_sum(s_vl, lds) * invM;
   const double ent = block_sum(s_ent, lds) * invM;
   const double val = block_sum(s_val, lds) * invM;
-  if (threadIdx.x == 0) {
-    a.stats[0] = (float)(a.vf_coef * vl - gain - a.entropy_factor * ent);
-    a.stats[1] = (float)vl;
-    a.stats[2] = (float)(-gain);
-    a.stats[3] = (float)ent;
-    a.stats[4] = (float)val;
+  if (threadIdx.x == 0) write_stats(a.stats, a.vf_coef, a.entropy_factor, gain, vl, ent, val);
+}
+
+// ---- 3b. the loss under the Normal head ----------------------------------------------------------------------------------
+// The skeleton above with the Normal pieces of 1b in the softmax's place.  Per row: the joint log-probability of the stored
+// float32 action (rounded once, then used as the float32 it is), and with s2_d = exp(2 logstd_d), diff_d = a_d - mean_d
+//   d log-prob / d mean_d = diff_d / s2_d,        d log-prob / d logstd_d = diff_d^2 / s2_d - 1.
+// The entropy of component d is 1/2 + log(2 pi) / 2 + logstd_d whatever the row.  The reference's evaluate_actions returns it
+// un-summed, [M][D], and the trainer takes .mean() over all M D elements (a2c.py:113): the entropy term is the MEAN over the
+// components, not their sum, and its gradient to logstd_d is 1 / D.  dlogstd is a reduction over the M rows: thread i adds
+// its rows in ascending order into D float64 accumulators, the workgroup adds those in the fixed tree — no atomics.
+struct NormalLossArgs {
+  long M; int D;
+  const float* mean; long pitch; const float* logstd;
+  const float* values; const float* actions; const float* targets; const float* acting_values; const float* old_log_probs;
+  double vf_coef, entropy_factor, clip_value; int adv_norm;
+  float* dmean; long dpitch; float* dlogstd; float* dvalues; float* log_probs; float* stats;
+};
+
+__global__ __launch_bounds__(kLossThreads) void k_ac_loss_normal(NormalLossArgs a) {
+  __shared__ double lds[kLossThreads];
+  const double invM = 1.0 / (double)a.M;
+  const AdvNorm norm = advantage_stats(a.targets, a.acting_values, a.M, a.adv_norm, invM, lds);
+  const double lo = 1.0 - a.clip_value, hi = 1.0 + a.clip_value;
+  double ent_sum = 0.0;
+  for (int d = 0; d < a.D; ++d) ent_sum += (0.5 + kHalfLog2Pi) + (double)a.logstd[d];
+  const double ent = ent_sum / (double)a.D;
+  double s_gain = 0.0, s_vl = 0.0, s_val = 0.0;
+  double acc[kMaxBoxDims];
+#pragma unroll
+  for (int d = 0; d < kMaxBoxDims; ++d) acc[d] = 0.0;
+  for (long i = threadIdx.x; i < a.M; i += kLossThreads) {
+    const float* m = a.mean + i * a.pitch;
+    const float* act = a.actions + i * a.D;
+    double lp = 0.0;
+    for (int d = 0; d < a.D; ++d) lp += normal_log_prob_term((double)act[d], (double)m[d], (double)a.logstd[d]);
+    const float lp32 = (float)lp;
+    if (a.log_probs) a.log_probs[i] = lp32;
+    const double adv = row_advantage(a.targets, a.acting_values, i, a.adv_norm, norm);
+    const RowGain rg = row_gain(lp32, adv, a.old_log_probs, i, lo, hi);
+    const double t = (double)a.targets[i], v = (double)a.values[i];
+    s_gain += rg.gain;
+    s_vl += (t - v) * (t - v);
+    s_val += v;
+    a.dvalues[i] = (float)(a.vf_coef * (2.0 * (v - t)) * invM);
+    float* g = a.dmean + i * a.dpitch;
+    const double w = rg.coef * invM;
+#pragma unroll
+    for (int d = 0; d < kMaxBoxDims; ++d) {
+      if (d < a.D) {
+        const double diff = (double)act[d] - (double)m[d], s2 = exp(2.0 * (double)a.logstd[d]);
+        g[d] = (float)(-(w * (diff / s2)));
+        acc[d] += -(w * ((diff * diff) / s2 - 1.0));
+      }
+    }
   }
+  const double gain = block_sum(s_gain, lds) * invM;
+  const double vl = block_sum(s_vl, lds) * invM;
+  const double val = block_sum(s_val, lds) * invM;
+#pragma unroll
+  for (int d = 0; d < kMaxBoxDims; ++d) {
+    if (d < a.D) {                                               // (uniform: every thread takes the same barriers)
+      const double total = block_sum(acc[d], lds);
+      if (threadIdx.x == 0) a.dlogstd[d] = (float)(total - a.entropy_factor / (double)a.D);
+    }
+  }
+  if (threadIdx.x == 0) write_stats(a.stats, a.vf_coef, a.entropy_factor, gain, vl, ent, val);
 }
 
 }  // namespace mirl
@@ -230,27 +362,85 @@ extern "C" int mirl_actor_head_ac(int32_t E, int32_t A, const float* logits, int
   return MIRL_OK;
 }
 
+extern "C" int mirl_actor_head_normal(int32_t E, int32_t D, const float* mean, int64_t pitch, const float* logstd, const float* values,
+                                      const float* eps, float* actions, float* action_log_probs, float* values_out, int32_t out_pitch,
+                                      void* stream) {
+  if (E < 1 || E > (1 << 24) || D < 1 || D > mirl::kMaxBoxDims || pitch < D || !mean || !logstd || !values || !eps || !actions ||
+      !action_log_probs || !values_out || out_pitch < 1)
+    return mirl::fail(MIRL_ERR_ARG, "bad actor_head_normal arguments (1 <= E <= 2^24, 1 <= D <= 16, pitch >= D, out_pitch >= 1, "
+                                    "no null operands)");
+  mirl::ProfScope ps("k_actor_head_normal", (double)E * (3.0 * D + 3.0) * 4.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_actor_head_normal, dim3((E + 63) / 64), dim3(64), 0, (hipStream_t)stream, (int)E, (int)D, mean, (long)pitch,
+                     logstd, values, eps, actions, action_log_probs, values_out, (int)out_pitch);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
+// both window entries: the protocol is stated once, mirl_online_window is action_words = 1
+static int online_window(const char* name, int32_t T, int32_t B, int32_t E, int32_t cap, int32_t nstep_target, double gamma, double lam,
+                         int64_t obs_bytes, int32_t action_words, const int32_t* plan, const void* obs_ring, const void* actions_ring,
+                         const float* rewards_ring, const uint8_t* dones_ring, const float* logp_ring, const float* values_ring,
+                         int32_t pol_pitch, float* returns, float* nsteps, float* target_masks, void* actions,
+                         float* action_log_probs, float* values, void* states, void* target_states, void* stream) {
+  // (the plan's entries are device data: the caller keeps env in [0, E), the slot in [0, cap) and T + 1 <= cap steps behind them)
+  if (T < 1 || B < 1 || E < 1 || cap < T || nstep_target < 1 || obs_bytes < 1 || pol_pitch < 1 || !(gamma >= 0.0) || !(lam >= 0.0) ||
+      action_words < 1 || action_words > mirl::kMaxBoxDims ||
+      (int64_t)T * B > (1 << 24) || (double)cap * (double)E * (double)obs_bytes >= 9.0e18 || !plan || !obs_ring || !actions_ring ||
+      !rewards_ring || !dones_ring || !logp_ring || !values_ring || !returns || !nsteps || !target_masks || !actions ||
+      !action_log_probs || !values || !states || !target_states)
+    return mirl::fail(MIRL_ERR_ARG, std::string("bad ") + name + " arguments (T, B, E >= 1, cap >= T, nstep_target >= 1, obs_bytes >= 1, "
+                                    "T B <= 2^24, 1 <= action_words <= 16, no null operands)");
+  mirl::WindowArgs a;
+  a.action_words = action_words;
+  a.T = T; a.B = B; a.E = E; a.cap = cap; a.nstep_target = nstep_target; a.gamma = gamma; a.lam = lam; a.obs_bytes = obs_bytes;
+  a.plan = plan; a.obs_ring = (const unsigned char*)obs_ring; a.actions_ring = (const int*)actions_ring; a.rewards_ring = rewards_ring;
+  a.dones_ring = dones_ring; a.logp_ring = logp_ring; a.values_ring = values_ring; a.pol_pitch = pol_pitch;
+  a.returns = returns; a.nsteps = nsteps; a.masks = target_masks; a.actions = (int*)actions; a.logp = action_log_probs; a.values = values;
+  a.states = (unsigned char*)states; a.target_states = (unsigned char*)target_states;
+  a.vec16 = (obs_bytes % 16 == 0 && mirl::aligned16(obs_ring, states, target_states)) ? 1 : 0;
+  mirl::ProfScope ps("k_online_window", (double)T * B * (4.0 * (double)obs_bytes + 32.0 + 8.0 * action_words), (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_online_window, dim3((unsigned)(T * B)), dim3(256), 0, (hipStream_t)stream, a);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
 extern "C" int mirl_online_window(int32_t T, int32_t B, int32_t E, int32_t cap, int32_t nstep_target, double gamma, double lam,
                                   int64_t obs_bytes, const int32_t* plan, const void* obs_ring, const int32_t* actions_ring,
                                   const float* rewards_ring, const uint8_t* dones_ring, const float* logp_ring, const float* values_ring,
                                   int32_t pol_pitch, float* returns, float* nsteps, float* target_masks, int32_t* actions,
                                   float* action_log_probs, float* values, void* states, void* target_states, void* stream) {
-  // (the plan's entries are device data: the caller keeps env in [0, E), the slot in [0, cap) and T + 1 <= cap steps behind them)
-  if (T < 1 || B < 1 || E < 1 || cap < T || nstep_target < 1 || obs_bytes < 1 || pol_pitch < 1 || !(gamma >= 0.0) || !(lam >= 0.0) ||
-      (int64_t)T * B > (1 << 24) || (double)cap * (double)E * (double)obs_bytes >= 9.0e18 || !plan || !obs_ring || !actions_ring ||
-      !rewards_ring || !dones_ring || !logp_ring || !values_ring || !returns || !nsteps || !target_masks || !actions ||
-      !action_log_probs || !values || !states || !target_states)
-    return mirl::fail(MIRL_ERR_ARG, "bad online_window arguments (T, B, E >= 1, cap >= T, nstep_target >= 1, obs_bytes >= 1, "
-                                    "T B <= 2^24, no null operands)");
-  mirl::WindowArgs a;
-  a.T = T; a.B = B; a.E = E; a.cap = cap; a.nstep_target = nstep_target; a.gamma = gamma; a.lam = lam; a.obs_bytes = obs_bytes;
-  a.plan = plan; a.obs_ring = (const unsigned char*)obs_ring; a.actions_ring = actions_ring; a.rewards_ring = rewards_ring;
-  a.dones_ring = dones_ring; a.logp_ring = logp_ring; a.values_ring = values_ring; a.pol_pitch = pol_pitch;
-  a.returns = returns; a.nsteps = nsteps; a.masks = target_masks; a.actions = actions; a.logp = action_log_probs; a.values = values;
-  a.states = (unsigned char*)states; a.target_states = (unsigned char*)target_states;
-  a.vec16 = (obs_bytes % 16 == 0 && mirl::aligned16(obs_ring, states, target_states)) ? 1 : 0;
-  mirl::ProfScope ps("k_online_window", (double)T * B * (4.0 * (double)obs_bytes + 40.0), (hipStream_t)stream);
-  hipLaunchKernelGGL(mirl::k_online_window, dim3((unsigned)(T * B)), dim3(256), 0, (hipStream_t)stream, a);
+  return online_window("online_window", T, B, E, cap, nstep_target, gamma, lam, obs_bytes, 1, plan, obs_ring, actions_ring, rewards_ring,
+                       dones_ring, logp_ring, values_ring, pol_pitch, returns, nsteps, target_masks, actions, action_log_probs, values,
+                       states, target_states, stream);
+}
+
+extern "C" int mirl_online_window_box(int32_t T, int32_t B, int32_t E, int32_t cap, int32_t nstep_target, double gamma, double lam,
+                                      int64_t obs_bytes, const int32_t* plan, const void* obs_ring, const void* actions_ring,
+                                      const float* rewards_ring, const uint8_t* dones_ring, const float* logp_ring,
+                                      const float* values_ring, int32_t pol_pitch, float* returns, float* nsteps, float* target_masks,
+                                      void* actions, float* action_log_probs, float* values, void* states, void* target_states,
+                                      int32_t action_words, void* stream) {
+  return online_window("online_window_box", T, B, E, cap, nstep_target, gamma, lam, obs_bytes, action_words, plan, obs_ring, actions_ring,
+                       rewards_ring, dones_ring, logp_ring, values_ring, pol_pitch, returns, nsteps, target_masks, actions,
+                       action_log_probs, values, states, target_states, stream);
+}
+
+extern "C" int mirl_ac_loss_normal(int64_t M, int32_t D, const float* mean, int64_t pitch, const float* logstd, const float* values,
+                                   const float* actions, const float* targets, const float* acting_values, const float* old_log_probs,
+                                   double vf_coef, double entropy_factor, double clip_value, int32_t adv_norm, float* dmean,
+                                   int64_t dpitch, float* dlogstd, float* dvalues, float* log_probs, float* stats, void* stream) {
+  if (M < 1 || M > (1 << 22) || D < 1 || D > mirl::kMaxBoxDims || pitch < D || dpitch < D || (adv_norm != 0 && adv_norm != 1) ||
+      (adv_norm && M < 2) || !mean || !logstd || !values || !actions || !targets || !acting_values || !dmean || !dlogstd || !dvalues ||
+      !stats || (old_log_probs && !(clip_value >= 0.0)))
+    return mirl::fail(MIRL_ERR_ARG, "bad ac_loss_normal arguments (1 <= M <= 2^22, M >= 2 with adv_norm, 1 <= D <= 16, pitches >= D, "
+                                    "adv_norm 0 | 1, clip_value >= 0 with old_log_probs, no null operands)");
+  mirl::NormalLossArgs a;
+  a.M = M; a.D = D; a.mean = mean; a.pitch = pitch; a.logstd = logstd; a.values = values; a.actions = actions; a.targets = targets;
+  a.acting_values = acting_values; a.old_log_probs = old_log_probs; a.vf_coef = vf_coef; a.entropy_factor = entropy_factor;
+  a.clip_value = clip_value; a.adv_norm = adv_norm; a.dmean = dmean; a.dpitch = dpitch; a.dlogstd = dlogstd; a.dvalues = dvalues;
+  a.log_probs = log_probs; a.stats = stats;
+  mirl::ProfScope ps("k_ac_loss_normal", (double)M * (3.0 * D + 8.0) * 4.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_ac_loss_normal, dim3(1), dim3(mirl::kLossThreads), 0, (hipStream_t)stream, a);
   MIRL_LAUNCH_CHECK();
   return MIRL_OK;
 }

@@ -115,6 +115,15 @@ class DeviceOnlineHistory:
         self._obs_shape, self._obs_dtype = tuple(frames.shape[1:]), frames.dtype
         self._obs_bytes = int(np.prod(self._obs_shape)) * frames.element_size()
         self._device = frames.device
+        # the action dtype and trailing shape of the first vector step: int32 [E] (Discrete) or float32 [E, D] (Box), kept in
+        # the rings as `_action_words` opaque 4-byte words per transition
+        actions = step["actions"]
+        self._action_shape = tuple(actions.shape[1:])
+        self._action_dtype = torch.float32 if self._action_shape else torch.int32
+        self._action_words = int(np.prod(self._action_shape)) if self._action_shape else 1
+        if (self._action_shape and actions.dtype != torch.float32) or not 1 <= self._action_words <= 16:
+            raise ValueError("DeviceOnlineHistory: actions are integers [E] or float32 [E, D] with D <= 16, not %s %s"
+                             % (actions.dtype, tuple(actions.shape)))
 
     def _grow(self, need, written):
         """Rings of `need` or more vector steps, at most max_delayed_steps + 1; the `written` steps already stored keep
@@ -123,7 +132,7 @@ class DeviceOnlineHistory:
         cap = min(max(need, 2 * self.capacity, self.nstep_train + 1), max(top, need))
         E, dev = self.num_envs, self._device
         new = {"obs": torch.empty((cap, E, self._obs_bytes), dtype=torch.uint8, device=dev),
-               "actions": torch.empty((cap, E), dtype=torch.int32, device=dev),
+               "actions": torch.empty((cap, E) + self._action_shape, dtype=self._action_dtype, device=dev),
                "rewards": torch.empty((cap, E), dtype=torch.float32, device=dev),
                "dones": torch.empty((cap, E), dtype=torch.uint8, device=dev),
                "policy": torch.empty((cap, E, 2), dtype=torch.float32, device=dev)}
@@ -179,14 +188,17 @@ class DeviceOnlineHistory:
         plan = torch.from_numpy(rows).to(dev, non_blocking=True)
         f32 = lambda: torch.empty((T, B), dtype=torch.float32, device=dev)      # noqa: E731
         returns, nsteps, masks, logp, values = f32(), f32(), f32(), f32(), f32()
-        actions = torch.empty((T, B), dtype=torch.int32, device=dev)
+        actions = torch.empty((T, B) + self._action_shape, dtype=self._action_dtype, device=dev)
         obs = torch.empty((2, T, B, self._obs_bytes), dtype=torch.uint8, device=dev)
         r = self._rings
         pol = r["policy"]
-        check(lib.mirl_online_window(T, B, E, cap, self.nstep_target, self.gamma, self.lam, self._obs_bytes, p(plan), p(r["obs"]),
-                                     p(r["actions"]), p(r["rewards"]), p(r["dones"]), p(pol), p(pol.view(-1)[1:]), 2,
-                                     p(returns), p(nsteps), p(masks), p(actions), p(logp), p(values), p(obs[0]), p(obs[1]),
-                                     stream()), "mirl_online_window")
+        args = (T, B, E, cap, self.nstep_target, self.gamma, self.lam, self._obs_bytes, p(plan), p(r["obs"]),
+                p(r["actions"]), p(r["rewards"]), p(r["dones"]), p(pol), p(pol.view(-1)[1:]), 2,
+                p(returns), p(nsteps), p(masks), p(actions), p(logp), p(values), p(obs[0]), p(obs[1]))
+        if self._action_shape:        # Box actions: the same kernel body moving `_action_words` words per transition
+            check(lib.mirl_online_window_box(*args, self._action_words, stream()), "mirl_online_window_box")
+        else:
+            check(lib.mirl_online_window(*args, stream()), "mirl_online_window")
         shaped = obs.view(self._obs_dtype).reshape((2, T, B) + self._obs_shape)
         tree = lambda x: dict({"x": x}, **{k: {} for k in self._state_keys})      # noqa: E731
         return {"states": tree(shaped[0]), "target_states": tree(shaped[1]), "returns": returns, "nsteps": nsteps,

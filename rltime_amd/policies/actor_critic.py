@@ -3,7 +3,8 @@ rltime/policies/torch/actor_critic.py:9-107, policies/torch/distributions/{categ
 
 Used by the A2C / PPO trainers.  On the CPU (BASELINE configs[0], `cartpole_ppo.json`) everything here is plain PyTorch;
 on the GPU a Categorical policy hands its raw logits and values to the kernels of csrc/actor_critic.hip
-(`actor_head_ac_raw` for the acting step, `get_logits_and_state_value` for the fused loss)."""
+(`actor_head_ac_raw` for the acting step, `get_logits_and_state_value` for the fused loss), a Normal policy its means,
+log-std and values (`actor_head_normal_raw`, `get_mean_logstd_and_state_value`)."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -73,15 +74,34 @@ class ActorCriticPolicy(TorchPolicy):
 
     def why_not_on_device(self):
         """What keeps this policy off the device actor-critic path (csrc/actor_critic.hip), or None."""
-        if not isinstance(self.actor, CategoricalHead):
-            return "the Normal (continuous) action head is not supported on the device path"
         if self.value_model is not None:
             return "critic_separate_model is not supported on the device path"
         if self.is_recurrent():
             return "recurrent actor-critic policies are not supported on the device path"
-        if self.actor.logits_layer.out_features > 64:
+        if isinstance(self.actor, NormalHead):
+            if self.actor.logstd.numel() > 16:
+                return "more than 16 action components are not supported on the device path"
+        elif self.actor.logits_layer.out_features > 64:
             return "more than 64 actions are not supported on the device path"
         return None
+
+    def has_normal_head(self):
+        return isinstance(self.actor, NormalHead)
+
+    def get_mean_logstd_and_state_value(self, inp, timesteps):
+        """The Normal head's raw means (rows, D), its log-std parameter (D,) and the state values (rows,): what the fused
+        loss (training/qops.py ac_loss_normal) differentiates."""
+        features = self.model(inp, timesteps)["output"]
+        return self.actor.mean_layer(features), self.actor.logstd, self.critic(features).squeeze(-1)
+
+    def actor_head_normal_raw(self, inp, timesteps):
+        """No-grad (means, logstd, values) of one acting step for the Normal sampling-head kernel (acting/actor.py)."""
+        why = self.why_not_on_device()
+        if why is not None:
+            raise ValueError(why)
+        with torch.no_grad():
+            mean, logstd, values = self.get_mean_logstd_and_state_value(inp, timesteps)
+        return mean.contiguous(), logstd.detach().contiguous(), values.contiguous()
 
     def get_logits_and_state_value(self, inp, timesteps):
         """The Categorical head's raw logits (rows, A) and the state values (rows,): what the fused loss
@@ -94,6 +114,8 @@ class ActorCriticPolicy(TorchPolicy):
         why = self.why_not_on_device()
         if why is not None:
             raise ValueError(why)
+        if self.has_normal_head():
+            raise ValueError("actor_head_ac_raw is the Categorical head's; a Normal head acts through actor_head_normal_raw")
         with torch.no_grad():
             logits, values = self.get_logits_and_state_value(inp, timesteps)
         return logits.contiguous(), values.contiguous()
@@ -106,6 +128,9 @@ class ActorCriticPolicy(TorchPolicy):
     def actor_predict(self, inp, timesteps, force_best=False):
         """actor_critic.py:37-71: sampled (or arg-max) actions with the log-probabilities and value estimates
         the trainer needs later."""
+        if force_best and not isinstance(self.actor, CategoricalHead):
+            # (the reference's arg-max of dist.logits fails for a Normal distribution too: actor_critic.py:50-53)
+            raise ValueError("force_best is not supported for the Normal (continuous) action head: it has no greedy mode")
         with torch.no_grad():
             dist, values = self.get_dist_and_state_value(inp, timesteps)
             actions = dist.logits.argmax(dim=-1) if force_best else dist.sample()

@@ -10,6 +10,10 @@ from rltime_amd.models.torch.utils import linear
 
 class DQNPolicy(TorchPolicy):
     def __init__(self, action_space, dueling=False, dueling_value_layer_hidden_size=None, **kwargs):
+        if not hasattr(action_space, "n"):
+            # (refused before the model, optimizer or history are built)
+            raise ValueError("Q-learning policies (dqn / dist_dqn / iqn) need a Discrete action space, not %r: a Box action "
+                             "space runs under the actor-critic trainers (a2c / ppo) only" % (action_space,))
         super().__init__(**kwargs)
         self.num_actions = action_space.n
         self.out_layer = linear(self.model.out_size, action_space.n * self._outputs_per_action())

@@ -37,6 +37,9 @@ def make_vec_env(env, env_args, num_envs, device, seed=0):
     if isinstance(env, str) and env.startswith("CartPole-"):
         raise ValueError("extra_features: the CartPole envs step on the CPU; the extra-features wrapper is a device kernel "
                          "and wraps 'catch' and 'synthetic-atari' only")
+    if env == "MountainCarContinuous-v0":
+        raise ValueError("extra_features: the wrapper's one-hot last action needs a Discrete action space; "
+                         "'MountainCarContinuous-v0' has a Box one (it wraps 'catch' and 'synthetic-atari' only)")
     if extra is not True and not isinstance(extra, dict):
         raise ValueError("extra_features: true (the wrapper's defaults) or a dict of its arguments %s" % (_EXTRA_FEATURES_KEYS,))
     kwargs = {} if extra is True else dict(extra)
@@ -59,6 +62,19 @@ def _make_base_vec_env(env, env_args, num_envs, device, seed=0):
             return CartPoleDeviceVecEnv(num_envs, max_episode_steps=limit, device=device, seed=seed)
         from rltime_amd.acting.cartpole_env import CartPoleVecEnv
         return CartPoleVecEnv(num_envs, max_episode_steps=limit, seed=seed)
+    if env == "MountainCarContinuous-v0":
+        # the one Box-action env (the reference's mountaincar_continuous_ppo.json): the build's own car, 999-step episodes
+        args = dict(env_args or {})
+        unknown = set(args) - {"max_episode_steps", "device"}
+        if unknown:
+            raise ValueError("MountainCarContinuous-v0: unknown env_args %s" % sorted(unknown))
+        limit = args.get("max_episode_steps", 999)
+        if args.get("device", False):
+            # the same car as ONE HIP kernel per vector step (acting/mountaincar_device_env.py)
+            from rltime_amd.acting.mountaincar_device_env import MountainCarDeviceVecEnv
+            return MountainCarDeviceVecEnv(num_envs, max_episode_steps=limit, device=device, seed=seed)
+        from rltime_amd.acting.mountaincar_env import MountainCarVecEnv
+        return MountainCarVecEnv(num_envs, max_episode_steps=limit, seed=seed)
     if env == "catch":
         # the one device-native game (acting/catch_env.py: a single HIP kernel per vector step)
         from rltime_amd.acting.catch_env import CatchVecEnv
@@ -71,8 +87,8 @@ def _make_base_vec_env(env, env_args, num_envs, device, seed=0):
         return CatchVecEnv(num_envs, device=device, seed=seed, **args)
     if env != "synthetic-atari":
         raise ValueError(
-            "rltime_amd ships the synthetic vector env ('synthetic-atari'), the device-native game 'catch' and its own "
-            "CartPole ('CartPole-v0/-v1'): real emulators are CPU code outside the scope of this backend (DESIGN.md)")
+            "rltime_amd ships the synthetic vector env ('synthetic-atari'), the device-native game 'catch', its own "
+            "CartPole ('CartPole-v0/-v1') and its own 'MountainCarContinuous-v0': real emulators are CPU code outside the scope of this backend (DESIGN.md)")
     from rltime_amd.acting.synthetic_env import SyntheticAtariVecEnv
     args = dict(env_args or {})
     args["frame_shape"] = tuple(args.get("frame_shape", (4, 84, 84)))

@@ -28,6 +28,9 @@ class A2C(TorchTrainer):
                 raise ValueError("%s is not supported with an actor-critic trainer (A2C / PPO)" % key)
         if getattr(self, "eval_episodes", 0):
             raise ValueError("eval_episodes is not supported with an actor-critic trainer (A2C / PPO)")
+        if not hasattr(self.actors.get_spaces()[1], "n") and history_mode.get("type") != "online":
+            raise ValueError("a Box action space needs history_mode type 'online', not %r: the replay histories store one "
+                             "integer action per transition" % (history_mode.get("type"),))
         if not self._on_device():
             return
         dp = getattr(self, "data_parallel", None)
@@ -87,8 +90,8 @@ class A2C(TorchTrainer):
         return None, None
 
     def _fused_loss_ok(self):
-        """A GPU policy with a Categorical head, and an action gain the kernel knows (a plugin trainer that overrides
-        _calc_action_gain keeps the plain-torch expression)."""
+        """A GPU policy the device path covers (Categorical or Normal head), and an action gain the kernel knows (a plugin
+        trainer that overrides _calc_action_gain keeps the plain-torch expression)."""
         pol = self.policy
         known = type(self)._calc_action_gain is getattr(type(self), "_fused_gain", None)
         return known and pol.is_cuda() and hasattr(pol, "why_not_on_device") and pol.why_not_on_device() is None
@@ -97,13 +100,20 @@ class A2C(TorchTrainer):
         """The same loss as below with forward and backward in one launch (csrc/actor_critic.hip mirl_ac_loss); the four
         logged scalars come out of the launch's stats block."""
         from . import qops
-        logits, values = self.policy.get_logits_and_state_value(states, timesteps)
         mk = self.policy.make_tensor
         old, clip = self._fused_loss_args(policy_outputs)
-        assert targets.dim() == 1 and targets.shape == values.shape
-        loss, stats = qops.ac_loss(logits, values, mk(policy_outputs["actions"]), targets, mk(policy_outputs["values"]),
-                                   old_log_probs=old, vf_coef=self.vf_coef, entropy_factor=self._calc_entropy_factor(),
-                                   clip_value=clip, adv_norm=self.adv_norm)
+        common = dict(old_log_probs=old, vf_coef=self.vf_coef, entropy_factor=self._calc_entropy_factor(), clip_value=clip,
+                      adv_norm=self.adv_norm)
+        if self.policy.has_normal_head():
+            # Box actions: mirl_ac_loss_normal, with the gradient of the state-independent log-std out of the same launch
+            mean, logstd, values = self.policy.get_mean_logstd_and_state_value(states, timesteps)
+            assert targets.dim() == 1 and targets.shape == values.shape
+            loss, stats = qops.ac_loss_normal(mean, logstd, values, mk(policy_outputs["actions"]), targets,
+                                              mk(policy_outputs["values"]), **common)
+        else:
+            logits, values = self.policy.get_logits_and_state_value(states, timesteps)
+            assert targets.dim() == 1 and targets.shape == values.shape
+            loss, stats = qops.ac_loss(logits, values, mk(policy_outputs["actions"]), targets, mk(policy_outputs["values"]), **common)
         loss.backward()
         log = self.value_log.log
         stats = stats.detach()

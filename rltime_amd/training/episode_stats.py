@@ -47,12 +47,23 @@ class EpisodeStats:
         if "env_stats" in info:
             self.value_log.log_dict(info["env_stats"], group="acting->env_stats")
         action = sample["policy_output"].get("actions")
-        if action is not None and not isinstance(action, np.ndarray):
+        if isinstance(action, np.ndarray) and action.ndim > 0:
+            # Box actions: the mean value of each action component over the window (policy_trainer.py:148-160, :72-81)
+            for i, val in enumerate(action.reshape(-1)):
+                self.action_counts[i] = self.action_counts.get(i, 0) + float(val)
+            self.action_total += 1
+        elif action is not None and not isinstance(action, np.ndarray):
             self.action_counts[int(action)] = self.action_counts.get(int(action), 0) + 1
             self.action_total += 1
 
     def action_histogram(self):
-        if self.device_tracker is not None:
+        if hasattr(self.device_tracker, "take_action_sums"):
+            # Box actions: the per-component sums and the transition count, so that the row carries the component means
+            sums, count = self.device_tracker.take_action_sums()
+            for i, s in enumerate(sums if count else []):
+                self.action_counts[i] = self.action_counts.get(i, 0) + s
+            self.action_total += count
+        elif self.device_tracker is not None:
             for a, c in enumerate(self.device_tracker.take_action_counts()):
                 if c:
                     self.action_counts[a] = self.action_counts.get(a, 0) + c

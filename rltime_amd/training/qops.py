@@ -198,6 +198,43 @@ class _ACLoss(torch.autograd.Function):
         return dz * g_loss, dv * g_loss, None, None, None, None, None, None, None, None
 
 
+class _ACLossNormal(torch.autograd.Function):
+    """csrc/actor_critic.hip mirl_ac_loss_normal: the loss scalar is stats[0]; its three gradients come out of the same launch."""
+
+    @staticmethod
+    def forward(ctx, mean, logstd, values, actions, targets, acting_values, old_log_probs, vf_coef, entropy_factor, clip_value,
+                adv_norm):
+        m, ls, v = _f32(mean), _f32(logstd), _f32(values)
+        M, D = m.shape
+        act = _f32(actions.detach()).reshape(M, -1)
+        if act.shape[1] != D or ls.numel() != D:
+            raise ValueError("ac_loss_normal: mean (M, D), logstd (D,), actions (M, D); got %s, %s, %s"
+                             % (tuple(m.shape), tuple(ls.shape), tuple(actions.shape)))
+        dm, dls, dv = torch.empty_like(m), torch.empty_like(ls), torch.empty_like(v)
+        stats = torch.empty(5, dtype=torch.float32, device=m.device)
+        old = _f32(old_log_probs) if old_log_probs is not None else None
+        check(lib.mirl_ac_loss_normal(
+            M, D, ptr(m), m.stride(0), ptr(ls), ptr(v), ptr(act), ptr(_f32(targets)), ptr(_f32(acting_values)), ptr(old),
+            float(vf_coef), float(entropy_factor), float(clip_value if clip_value is not None else 0.0), 1 if adv_norm else 0,
+            ptr(dm), D, ptr(dls), ptr(dv), None, ptr(stats), stream()), "mirl_ac_loss_normal")
+        ctx.save_for_backward(dm, dls, dv)
+        ctx.mark_non_differentiable(stats)
+        return stats[0].clone(), stats
+
+    @staticmethod
+    def backward(ctx, g_loss, g_stats):
+        dm, dls, dv = ctx.saved_tensors
+        return dm * g_loss, dls * g_loss, dv * g_loss, None, None, None, None, None, None, None, None
+
+
+def ac_loss_normal(mean, logstd, values, actions, targets, acting_values, old_log_probs=None, vf_coef=1.0, entropy_factor=0.0,
+                   clip_value=None, adv_norm=False):
+    """ac_loss under the Normal head (distributions/normal.py): mean (M, D), logstd (D,), float32 actions (M, D) -> (scalar
+    loss differentiable w.r.t. mean, logstd and values, stats (5,)); the entropy is the mean over the components."""
+    return _ACLossNormal.apply(mean, logstd, values, actions, targets, acting_values, old_log_probs, vf_coef, entropy_factor,
+                               clip_value, adv_norm)
+
+
 def ac_loss(logits, values, actions, targets, acting_values, old_log_probs=None, vf_coef=1.0, entropy_factor=0.0,
             clip_value=None, adv_norm=False):
     """training/torch/a2c.py:101-141 with the gain of a2c.py:90-99 (old_log_probs None) or ppo.py:39-56, forward and

@@ -77,6 +77,97 @@ def loss_times(M, A, iters, repeats):
             "rerun_max_diff": diff, "fused_vs_torch_grad_rel": agree}
 
 
+def _torch_loss_normal(mean, logstd, values, actions, targets, acting, old, vf, ef, clip):
+    """The same with the Normal head: joint log-probability, entropy .mean() over all M * D elements."""
+    dist = torch.distributions.Normal(mean, logstd.exp().expand_as(mean))
+    log_probs, entropy = dist.log_prob(actions).sum(-1), dist.entropy().mean()
+    adv = targets - acting
+    adv = (adv - adv.mean()) / (adv.std() + 1e-5)
+    ratio = torch.exp(log_probs - old)
+    gain = torch.min(ratio * adv, torch.clamp(ratio, 1.0 - clip, 1.0 + clip) * adv).mean()
+    value_loss = (targets - values).pow(2).mean()
+    return value_loss * vf - gain - ef * entropy
+
+
+def normal_loss_times(M, D, iters, repeats):
+    """mountaincar_continuous_ppo's loss: M = 128 is one minibatch of the config (16 envs x 32 steps / 4)."""
+    from rltime_amd.training import qops
+    g = torch.Generator(device="cuda").manual_seed(2)
+    mean = torch.randn(M, D, device="cuda", generator=g).requires_grad_(True)
+    logstd = (torch.rand(D, device="cuda", generator=g) - 0.7).requires_grad_(True)
+    values = torch.randn(M, device="cuda", generator=g).requires_grad_(True)
+    actions = (mean + logstd.exp() * torch.randn(M, D, device="cuda", generator=g)).detach()
+    targets, acting = values.detach() + torch.randn(M, device="cuda", generator=g), values.detach() + 0.3
+    with torch.no_grad():
+        old = torch.distributions.Normal(mean, logstd.exp().expand_as(mean)).log_prob(actions).sum(-1) \
+            + 0.2 * torch.randn(M, device="cuda", generator=g)
+
+    def fused():
+        mean.grad = logstd.grad = values.grad = None
+        loss, _ = qops.ac_loss_normal(mean, logstd, values, actions, targets, acting, old_log_probs=old, vf_coef=0.5,
+                                      entropy_factor=0.01, clip_value=0.2, adv_norm=True)
+        loss.backward()
+
+    def plain():
+        mean.grad = logstd.grad = values.grad = None
+        _torch_loss_normal(mean, logstd, values, actions, targets, acting, old, 0.5, 0.01, 0.2).backward()
+    fused()
+    g_m, g_s = mean.grad.clone(), logstd.grad.clone()
+    fused()
+    diff = max(float((mean.grad - g_m).abs().max()), float((logstd.grad - g_s).abs().max()))
+    plain()
+    agree = max(float((mean.grad - g_m).abs().max() / g_m.abs().max()), float((logstd.grad - g_s).abs().max() / g_s.abs().max()))
+    for _ in range(20):
+        fused()
+        plain()
+    f, p = [], []
+    for _ in range(repeats):                                  # alternating, same process
+        f.append(_timed(fused, iters))
+        p.append(_timed(plain, iters))
+    return {"M": M, "D": D, "fused_us": [round(x, 1) for x in f], "torch_us": [round(x, 1) for x in p],
+            "fused_us_median": round(sorted(f)[len(f) // 2], 1), "torch_us_median": round(sorted(p)[len(p) // 2], 1),
+            "rerun_max_diff": diff, "fused_vs_torch_grad_rel": agree}
+
+
+def normal_head_time(E, D, iters, repeats):
+    """One launch of the Normal sampling head on ready operands against the torch expression of actor_predict."""
+    from rltime_amd._lib import lib, check, ptr as p, stream
+    g = torch.Generator(device="cuda").manual_seed(3)
+    mean, values = torch.randn(E, D, device="cuda", generator=g), torch.randn(E, device="cuda", generator=g)
+    logstd, eps = torch.zeros(D, device="cuda"), torch.randn(E, D, device="cuda", generator=g)
+    actions, block = torch.empty(E, D, device="cuda"), torch.empty(E, 2, device="cuda")
+
+    def kernel():
+        check(lib.mirl_actor_head_normal(E, D, p(mean), D, p(logstd), p(values), p(eps), p(actions), p(block), p(block[:, 1]), 2,
+                                         stream()), "mirl_actor_head_normal")
+
+    def plain():
+        dist = torch.distributions.Normal(mean, logstd.exp().expand_as(mean))
+        a = dist.sample()
+        return a, dist.log_prob(a).sum(-1)
+    for _ in range(20):
+        kernel()
+        plain()
+    k, t = [], []
+    for _ in range(repeats):
+        k.append(_timed(kernel, iters))
+        t.append(_timed(plain, iters))
+    return {"E": E, "D": D, "kernel_us_median": round(sorted(k)[len(k) // 2], 1), "torch_us_median": round(sorted(t)[len(t) // 2], 1)}
+
+
+def mountaincar_step_time(E, iters, repeats):
+    """One env step (step_into on static buffers with a bound action buffer)."""
+    from rltime_amd.acting.mountaincar_device_env import MountainCarDeviceVecEnv
+    env = MountainCarDeviceVecEnv(E, max_episode_steps=999, seed=0)
+    env.reset()
+    env.bind_actions(torch.randn(E, 1, device="cuda"))
+    out = env._fresh()
+    for _ in range(20):
+        env.step_into(*out)
+    s = [_timed(lambda: env.step_into(*out), iters) for _ in range(repeats)]
+    return {"E": E, "step_us_median": round(sorted(s)[len(s) // 2], 1)}
+
+
 def window_time(iters):
     from rltime_amd.acting.acting_interface import DeviceSamples
     from rltime_amd.history.online_device import DeviceOnlineHistory
@@ -134,7 +225,10 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("actor_critic_probe: no GPU visible; timings are taken on the device only")
     out = {"loss": [loss_times(512, A, a.iters, a.repeats) for A in (6, 18)], "window": window_time(max(8, a.iters // 10)),
-           "acting": acting_time(a.iters)}
+           "acting": acting_time(a.iters),
+           "normal_loss": [normal_loss_times(M, 1, a.iters, a.repeats) for M in (128, 512)],
+           "normal_head": [normal_head_time(E, 1, a.iters, a.repeats) for E in (128, 512)],
+           "mountaincar_step": [mountaincar_step_time(E, a.iters, a.repeats) for E in (128, 512)]}
     print(json.dumps(out))
 
 
