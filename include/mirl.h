@@ -1121,6 +1121,22 @@ int mirl_online_window_box(int32_t T, int32_t B, int32_t E, int32_t cap, int32_t
                            int32_t pol_pitch, float* returns, float* nsteps, float* target_masks, void* actions,
                            float* action_log_probs, float* values, void* states, void* target_states, int32_t action_words,
                            void* stream);
+/* mirl_online_window_box for a recurrent policy: every stored next_state also carries its recurrent state, state_ring
+ * [cap][E][state_f32] float32 (hx, cx of each recurrent layer, in the order the caller packed them) and its initials flag,
+ * initials_ring [cap][E] float32 (1 = that next_state opens an episode).  For every batch row (t, b) both are read from
+ * exactly the ring row the observation block is read from — states: one slot before the transition (its own slot for an
+ * env's first ever transition), target_states: the slot of transition i + n - 1 — into states_state / target_state
+ * [T * B][state_f32] and states_initials / target_initials [T * B].  Every row is written: a model that re-starts its
+ * sequences inside the window (rnn_steps_train < nstep_train) and the one-step bootstrap pass read rows at t > 0.  A copy:
+ * no arithmetic, bit-exact; 16-byte accesses when state_f32 % 4 == 0 and the three state blocks are 16-byte aligned, 4-byte
+ * words otherwise.  The two older entries are this kernel body with state_f32 = 0.  1 <= state_f32 <= 2^20.            */
+int mirl_online_window_rec(int32_t T, int32_t B, int32_t E, int32_t cap, int32_t nstep_target, double gamma, double lam,
+                           int64_t obs_bytes, const int32_t* plan, const void* obs_ring, const void* actions_ring,
+                           const float* rewards_ring, const uint8_t* dones_ring, const float* logp_ring, const float* values_ring,
+                           int32_t pol_pitch, float* returns, float* nsteps, float* target_masks, void* actions,
+                           float* action_log_probs, float* values, void* states, void* target_states, int32_t action_words,
+                           const float* state_ring, const float* initials_ring, int32_t state_f32, float* states_state,
+                           float* target_state, float* states_initials, float* target_initials, void* stream);
 /* mirl_ac_loss under the Normal head, ONE launch of one workgroup: mean [M][D] (`pitch` apart), logstd [D], actions
  * float32 [M][D]; advantages, gains (A2C / PPO with autograd's tie rules), value loss and stats are mirl_ac_loss's — the
  * same code.  The entropy of component d is 1/2 + log(2 pi) / 2 + logstd_d; the reference takes .mean() over the un-summed

@@ -240,6 +240,8 @@ _SIGNATURES = {
     "mirl_actor_head_normal": [_i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
     "mirl_online_window_box": [_i32, _i32, _i32, _i32, _i32, _f64, _f64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                _vp, _vp, _vp, _vp, _vp, _i32, _vp],
+    "mirl_online_window_rec": [_i32, _i32, _i32, _i32, _i32, _f64, _f64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                               _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "mirl_ac_loss_normal": [_i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _i32, _vp, _i64, _vp, _vp, _vp, _vp,
                             _vp],
     "mirl_stack_shift": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],

@@ -109,13 +109,26 @@ struct WindowArgs {
   float *logp, *values;
   unsigned char *states, *target_states;
   int vec16, action_words;
+  // the recurrent state stored with each next_state (S = 0: none, the two older entries)
+  int S;                           // float32 words per transition: hx, cx of every recurrent layer
+  const float* state_ring;         // [cap][E][S]
+  const float* initials_ring;      // [cap][E]: 1 = that next_state opens an episode
+  float *states_state, *target_state;        // [T B][S]
+  float *states_initials, *target_initials;  // [T B]
+  int state_vec16;
 };
 
-__device__ inline void copy_row(unsigned char* __restrict__ dst, const unsigned char* __restrict__ src, long bytes, int vec16) {
-  if (vec16) {
+// `width` bytes per access: 16 (the launcher saw 16-byte aligned bases and a row length that keeps every row aligned),
+// 4 (float32 rows) or 1
+__device__ inline void copy_row(unsigned char* __restrict__ dst, const unsigned char* __restrict__ src, long bytes, int width) {
+  if (width == 16) {
     const uint4* s = (const uint4*)src;
     uint4* d = (uint4*)dst;
     for (long q = threadIdx.x; q < bytes / 16; q += blockDim.x) d[q] = s[q];
+  } else if (width == 4) {
+    const unsigned* s = (const unsigned*)src;
+    unsigned* d = (unsigned*)dst;
+    for (long q = threadIdx.x; q < bytes / 4; q += blockDim.x) d[q] = s[q];
   } else {
     for (long q = threadIdx.x; q < bytes; q += blockDim.x) dst[q] = src[q];
   }
@@ -147,10 +160,23 @@ __global__ __launch_bounds__(256) void k_online_window(WindowArgs a) {
     a.logp[out] = a.logp_ring[r0 * a.pol_pitch];
     a.values[out] = a.values_ring[r0 * a.pol_pitch];
   }
-  // the transition starts from the previous vector step's next_state (an env's very first one from its own)
+  // the transition starts from the previous vector step's next_state (an env's very first one from its own) and its target is
+  // the next_state of the last step it covers: the ring rows every block of a stored next_state — observation, recurrent
+  // state, initials flag — is read from
   const long s_row = (t == 0 && own) ? at(0) : (long)((first + t - 1 + a.cap) % a.cap) * a.E + env;
-  copy_row(a.states + out * a.obs_bytes, a.obs_ring + s_row * a.obs_bytes, a.obs_bytes, a.vec16);
-  copy_row(a.target_states + out * a.obs_bytes, a.obs_ring + at(t + want - 1) * a.obs_bytes, a.obs_bytes, a.vec16);
+  const long t_row = at(t + want - 1);
+  copy_row(a.states + out * a.obs_bytes, a.obs_ring + s_row * a.obs_bytes, a.obs_bytes, a.vec16 ? 16 : 1);
+  copy_row(a.target_states + out * a.obs_bytes, a.obs_ring + t_row * a.obs_bytes, a.obs_bytes, a.vec16 ? 16 : 1);
+  if (a.S) {
+    const long sb = (long)a.S * 4;
+    const int width = a.state_vec16 ? 16 : 4;
+    copy_row((unsigned char*)(a.states_state + out * a.S), (const unsigned char*)(a.state_ring + s_row * a.S), sb, width);
+    copy_row((unsigned char*)(a.target_state + out * a.S), (const unsigned char*)(a.state_ring + t_row * a.S), sb, width);
+    if (threadIdx.x == 0) {
+      a.states_initials[out] = a.initials_ring[s_row];
+      a.target_initials[out] = a.initials_ring[t_row];
+    }
+  }
 }
 
 // ---- 3. the loss ---------------------------------------------------------------------------------------------------
@@ -376,12 +402,20 @@ extern "C" int mirl_actor_head_normal(int32_t E, int32_t D, const float* mean, i
   return MIRL_OK;
 }
 
-// both window entries: the protocol is stated once, mirl_online_window is action_words = 1
+// the recurrent blocks of mirl_online_window_rec; the two older entries pass none (S = 0)
+struct WindowState {
+  int32_t S = 0;
+  const float* state_ring = nullptr;
+  const float* initials_ring = nullptr;
+  float *states_state = nullptr, *target_state = nullptr, *states_initials = nullptr, *target_initials = nullptr;
+};
+
+// all three window entries: the protocol is stated once, mirl_online_window is action_words = 1, and both older entries S = 0
 static int online_window(const char* name, int32_t T, int32_t B, int32_t E, int32_t cap, int32_t nstep_target, double gamma, double lam,
                          int64_t obs_bytes, int32_t action_words, const int32_t* plan, const void* obs_ring, const void* actions_ring,
                          const float* rewards_ring, const uint8_t* dones_ring, const float* logp_ring, const float* values_ring,
                          int32_t pol_pitch, float* returns, float* nsteps, float* target_masks, void* actions,
-                         float* action_log_probs, float* values, void* states, void* target_states, void* stream) {
+                         float* action_log_probs, float* values, void* states, void* target_states, const WindowState& rec, void* stream) {
   // (the plan's entries are device data: the caller keeps env in [0, E), the slot in [0, cap) and T + 1 <= cap steps behind them)
   if (T < 1 || B < 1 || E < 1 || cap < T || nstep_target < 1 || obs_bytes < 1 || pol_pitch < 1 || !(gamma >= 0.0) || !(lam >= 0.0) ||
       action_words < 1 || action_words > mirl::kMaxBoxDims ||
@@ -390,7 +424,15 @@ static int online_window(const char* name, int32_t T, int32_t B, int32_t E, int3
       !action_log_probs || !values || !states || !target_states)
     return mirl::fail(MIRL_ERR_ARG, std::string("bad ") + name + " arguments (T, B, E >= 1, cap >= T, nstep_target >= 1, obs_bytes >= 1, "
                                     "T B <= 2^24, 1 <= action_words <= 16, no null operands)");
+  if (rec.S && (rec.S < 1 || rec.S > (1 << 20) || !rec.state_ring || !rec.initials_ring || !rec.states_state || !rec.target_state ||
+                !rec.states_initials || !rec.target_initials || (uintptr_t)rec.state_ring % 4 || (uintptr_t)rec.states_state % 4 ||
+                (uintptr_t)rec.target_state % 4))
+    return mirl::fail(MIRL_ERR_ARG, std::string("bad ") + name + " arguments (1 <= state_f32 <= 2^20, float32 state blocks on 4-byte "
+                                    "boundaries, no null operands)");
   mirl::WindowArgs a;
+  a.S = rec.S; a.state_ring = rec.state_ring; a.initials_ring = rec.initials_ring; a.states_state = rec.states_state;
+  a.target_state = rec.target_state; a.states_initials = rec.states_initials; a.target_initials = rec.target_initials;
+  a.state_vec16 = (rec.S && rec.S % 4 == 0 && mirl::aligned16(rec.state_ring, rec.states_state, rec.target_state)) ? 1 : 0;
   a.action_words = action_words;
   a.T = T; a.B = B; a.E = E; a.cap = cap; a.nstep_target = nstep_target; a.gamma = gamma; a.lam = lam; a.obs_bytes = obs_bytes;
   a.plan = plan; a.obs_ring = (const unsigned char*)obs_ring; a.actions_ring = (const int*)actions_ring; a.rewards_ring = rewards_ring;
@@ -398,7 +440,8 @@ static int online_window(const char* name, int32_t T, int32_t B, int32_t E, int3
   a.returns = returns; a.nsteps = nsteps; a.masks = target_masks; a.actions = (int*)actions; a.logp = action_log_probs; a.values = values;
   a.states = (unsigned char*)states; a.target_states = (unsigned char*)target_states;
   a.vec16 = (obs_bytes % 16 == 0 && mirl::aligned16(obs_ring, states, target_states)) ? 1 : 0;
-  mirl::ProfScope ps("k_online_window", (double)T * B * (4.0 * (double)obs_bytes + 32.0 + 8.0 * action_words), (hipStream_t)stream);
+  mirl::ProfScope ps("k_online_window", (double)T * B * (4.0 * (double)obs_bytes + 32.0 + 8.0 * action_words + (rec.S ? 16.0 * rec.S + 16.0 : 0.0)),
+                     (hipStream_t)stream);
   hipLaunchKernelGGL(mirl::k_online_window, dim3((unsigned)(T * B)), dim3(256), 0, (hipStream_t)stream, a);
   MIRL_LAUNCH_CHECK();
   return MIRL_OK;
@@ -411,7 +454,7 @@ extern "C" int mirl_online_window(int32_t T, int32_t B, int32_t E, int32_t cap, 
                                   float* action_log_probs, float* values, void* states, void* target_states, void* stream) {
   return online_window("online_window", T, B, E, cap, nstep_target, gamma, lam, obs_bytes, 1, plan, obs_ring, actions_ring, rewards_ring,
                        dones_ring, logp_ring, values_ring, pol_pitch, returns, nsteps, target_masks, actions, action_log_probs, values,
-                       states, target_states, stream);
+                       states, target_states, WindowState(), stream);
 }
 
 extern "C" int mirl_online_window_box(int32_t T, int32_t B, int32_t E, int32_t cap, int32_t nstep_target, double gamma, double lam,
@@ -422,7 +465,24 @@ extern "C" int mirl_online_window_box(int32_t T, int32_t B, int32_t E, int32_t c
                                       int32_t action_words, void* stream) {
   return online_window("online_window_box", T, B, E, cap, nstep_target, gamma, lam, obs_bytes, action_words, plan, obs_ring, actions_ring,
                        rewards_ring, dones_ring, logp_ring, values_ring, pol_pitch, returns, nsteps, target_masks, actions,
-                       action_log_probs, values, states, target_states, stream);
+                       action_log_probs, values, states, target_states, WindowState(), stream);
+}
+
+extern "C" int mirl_online_window_rec(int32_t T, int32_t B, int32_t E, int32_t cap, int32_t nstep_target, double gamma, double lam,
+                                      int64_t obs_bytes, const int32_t* plan, const void* obs_ring, const void* actions_ring,
+                                      const float* rewards_ring, const uint8_t* dones_ring, const float* logp_ring,
+                                      const float* values_ring, int32_t pol_pitch, float* returns, float* nsteps, float* target_masks,
+                                      void* actions, float* action_log_probs, float* values, void* states, void* target_states,
+                                      int32_t action_words, const float* state_ring, const float* initials_ring, int32_t state_f32,
+                                      float* states_state, float* target_state, float* states_initials, float* target_initials,
+                                      void* stream) {
+  if (state_f32 < 1) return mirl::fail(MIRL_ERR_ARG, "bad online_window_rec arguments (state_f32 >= 1)");
+  WindowState rec;
+  rec.S = state_f32; rec.state_ring = state_ring; rec.initials_ring = initials_ring; rec.states_state = states_state;
+  rec.target_state = target_state; rec.states_initials = states_initials; rec.target_initials = target_initials;
+  return online_window("online_window_rec", T, B, E, cap, nstep_target, gamma, lam, obs_bytes, action_words, plan, obs_ring, actions_ring,
+                       rewards_ring, dones_ring, logp_ring, values_ring, pol_pitch, returns, nsteps, target_masks, actions,
+                       action_log_probs, values, states, target_states, rec, stream);
 }
 
 extern "C" int mirl_ac_loss_normal(int64_t M, int32_t D, const float* mean, int64_t pitch, const float* logstd, const float* values,

@@ -8,9 +8,16 @@ max_delayed_steps discards, the feed decision, an env's very first transition st
 stays on the host as plain Python (`OnlinePlan`, no torch).  `get_train_data` uploads the plan of the served sequences
 (env, first ring slot) and one launch of csrc/actor_critic.hip (mirl_online_window) writes the (T, B) batch: lambda-returns
 in float64, step counts, masks, the gathered policy outputs and both observation blocks.
+
+A recurrent policy's next_state also carries each recurrent layer's hx, cx and the `initials` flag.  The vector steps hand
+them over packed (`state` [E, S], `initials` [E]: acting/actor.py _pack_state), two more rings keep them, and the same
+launch (mirl_online_window_rec) moves them from exactly the ring rows the observations come from; the stored pytree is
+described by the replay's _Layout, which is where the field order is stated.
 """
 import numpy as np
 import torch
+
+from .replay_history import _Layout
 
 
 class OnlinePlan:
@@ -106,11 +113,23 @@ class DeviceOnlineHistory:
     # -- feeding ----------------------------------------------------------------------------
     def _configure(self, samples, step):
         frames = step["frames"]
-        self._state_keys = [k for k in samples.example_state if k != "x"]
-        if any(samples.example_state[k] for k in self._state_keys) or "state" in step:
-            raise ValueError("DeviceOnlineHistory: recurrent policies are not supported on the device path")
-        if "extra" in step:
+        if "extra" in step or isinstance(samples.example_state["x"], (tuple, list)):
             raise ValueError("DeviceOnlineHistory: extra-feature observations are not supported on the device path")
+        lay = self._layout = _Layout(samples.example_state)
+        if lay.recurrent:
+            if "state" not in step or "initials" not in step or not lay.has_initials:
+                raise ValueError("DeviceOnlineHistory: the vector steps of a recurrent policy must carry both its packed "
+                                 "`state` [E, S] and its `initials` [E]")
+            state, initials = step["state"], step["initials"]
+            if tuple(state.shape) != (samples.num_envs, lay.state_f32) or state.dtype != torch.float32:
+                raise ValueError("DeviceOnlineHistory: the vector step's state is %s %s, the stored pytree holds float32 [%d, %d]"
+                                 % (state.dtype, tuple(state.shape), samples.num_envs, lay.state_f32))
+            if tuple(initials.shape) != (samples.num_envs,) or initials.dtype != torch.float32:
+                raise ValueError("DeviceOnlineHistory: the vector step's initials are %s %s, not float32 [%d]"
+                                 % (initials.dtype, tuple(initials.shape), samples.num_envs))
+        elif "state" in step or "initials" in step or lay.has_initials:
+            raise ValueError("DeviceOnlineHistory: the vector steps carry a recurrent state or initials that the stored "
+                             "pytree has no recurrent layer for")
         self.num_envs, self.env_base = samples.num_envs, samples.env_base
         self._obs_shape, self._obs_dtype = tuple(frames.shape[1:]), frames.dtype
         self._obs_bytes = int(np.prod(self._obs_shape)) * frames.element_size()
@@ -136,6 +155,9 @@ class DeviceOnlineHistory:
                "rewards": torch.empty((cap, E), dtype=torch.float32, device=dev),
                "dones": torch.empty((cap, E), dtype=torch.uint8, device=dev),
                "policy": torch.empty((cap, E, 2), dtype=torch.float32, device=dev)}
+        if self._layout.recurrent:
+            new["state"] = torch.empty((cap, E, self._layout.state_f32), dtype=torch.float32, device=dev)
+            new["initials"] = torch.empty((cap, E), dtype=torch.float32, device=dev)
         if self._rings is not None:
             live = np.arange(max(0, written - self.capacity), written)
             if len(live):
@@ -166,6 +188,9 @@ class DeviceOnlineHistory:
             r["rewards"][slot].copy_(step["rewards"])
             r["dones"][slot].copy_(step["dones"])
             r["policy"][slot].copy_(step["policy"])
+            if self._layout.recurrent:
+                r["state"][slot].copy_(step["state"])
+                r["initials"][slot].copy_(step["initials"])
         return {"discarded_steps": discarded}
 
     def needed_feed_count(self, mbatch_size, num_envs):
@@ -195,13 +220,31 @@ class DeviceOnlineHistory:
         args = (T, B, E, cap, self.nstep_target, self.gamma, self.lam, self._obs_bytes, p(plan), p(r["obs"]),
                 p(r["actions"]), p(r["rewards"]), p(r["dones"]), p(pol), p(pol.view(-1)[1:]), 2,
                 p(returns), p(nsteps), p(masks), p(actions), p(logp), p(values), p(obs[0]), p(obs[1]))
-        if self._action_shape:        # Box actions: the same kernel body moving `_action_words` words per transition
+        lay = self._layout
+        state = initials = None
+        if lay.recurrent:             # the same kernel body also moving the recurrent state and the initials flag of every row
+            state = torch.empty((2, T, B, lay.state_f32), dtype=torch.float32, device=dev)
+            initials = torch.empty((2, T, B), dtype=torch.float32, device=dev)
+            check(lib.mirl_online_window_rec(*args, self._action_words, p(r["state"]), p(r["initials"]), lay.state_f32,
+                                             p(state[0]), p(state[1]), p(initials[0]), p(initials[1]), stream()),
+                  "mirl_online_window_rec")
+        elif self._action_shape:      # Box actions: the same kernel body moving `_action_words` words per transition
             check(lib.mirl_online_window_box(*args, self._action_words, stream()), "mirl_online_window_box")
         else:
             check(lib.mirl_online_window(*args, stream()), "mirl_online_window")
         shaped = obs.view(self._obs_dtype).reshape((2, T, B) + self._obs_shape)
-        tree = lambda x: dict({"x": x}, **{k: {} for k in self._state_keys})      # noqa: E731
-        return {"states": tree(shaped[0]), "target_states": tree(shaped[1]), "returns": returns, "nsteps": nsteps,
+
+        def tree(i):
+            out, at, rec = {"x": shaped[i]}, 0, dict(lay.recurrent)
+            for k in lay.layer_keys:
+                out[k] = {}
+                for name, size, shape in rec.get(k, ()):
+                    out[k][name] = state[i][..., at:at + size].reshape((T, B) + shape)
+                    at += size
+                if k in rec:
+                    out[k]["initials"] = initials[i]
+            return out
+        return {"states": tree(0), "target_states": tree(1), "returns": returns, "nsteps": nsteps,
                 "target_masks": masks, "policy_outputs": {"actions": actions, "action_log_probs": logp, "values": values},
                 "extra_data": {}}
 

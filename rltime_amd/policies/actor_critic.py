@@ -73,11 +73,11 @@ class ActorCriticPolicy(TorchPolicy):
         return self.critic(model(inp, timesteps)["output"]).squeeze(-1)
 
     def why_not_on_device(self):
-        """What keeps this policy off the device actor-critic path (csrc/actor_critic.hip), or None."""
+        """What keeps this policy off the device actor-critic path (csrc/actor_critic.hip), or None.  (A recurrent model is
+        covered: the raw-output getters below pass the state pytree through the model, and the device history keeps the
+        recurrent state of every row.)"""
         if self.value_model is not None:
             return "critic_separate_model is not supported on the device path"
-        if self.is_recurrent():
-            return "recurrent actor-critic policies are not supported on the device path"
         if isinstance(self.actor, NormalHead):
             if self.actor.logstd.numel() > 16:
                 return "more than 16 action components are not supported on the device path"

@@ -43,6 +43,23 @@ class A2C(TorchTrainer):
             raise ValueError("A2C / PPO on the device path need history_mode type 'online', not %r" % (history_mode.get("type"),))
         if not history_mode.get("args", {}).get("fixed_target", True):
             raise ValueError("fixed_target=False is not supported on the device path: its targets look past the window")
+        if kwargs.get("burn_in_timesteps"):
+            raise ValueError("burn_in_timesteps is not supported with the device online history: it has no prefix steps")
+        if kwargs.get("rnn_bootstrap"):
+            raise ValueError("rnn_bootstrap is not supported with the device online history: its n-steps are not fixed")
+        if self.policy.is_recurrent():
+            # whole sequences per minibatch (multi_step_trainer.py:47-68 asserts the same in the middle of training)
+            T = kwargs["nstep_train"]
+            rnn = kwargs.get("rnn_steps_train") or T
+            seqs = kwargs.get("mbatch_size") or self.actors.get_env_count()
+            parts = kwargs.get("minibatches", 1)
+            if T % rnn:
+                raise ValueError("a recurrent policy trains on whole sequences: nstep_train (%d) must be a multiple of "
+                                 "rnn_steps_train (%d)" % (T, rnn))
+            if (seqs * T) % parts or (seqs * T // parts) % T:
+                raise ValueError("a recurrent policy trains on whole sequences: every minibatch must hold a whole number of "
+                                 "the batch's %d sequences of nstep_train = %d steps, so minibatches (%d) must divide %d"
+                                 % (seqs, T, parts, seqs))
 
     def _init_history_buffer(self, mode, *args, **kwargs):
         """The reference's history_mode {"type": "online"} resolves to the device class when the rollouts are on the

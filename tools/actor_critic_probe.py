@@ -3,7 +3,8 @@
   loss      M = 512 rows, A = 6 and 18, from logits / values to their gradients: the fused call (training/qops.py ac_loss +
             backward) against the plain-torch expression of A2C._compute_grads / PPO._calc_action_gain on the same GPU tensors,
             alternating, host clock around a synchronised window of `--iters` calls each, repeated `--repeats` times
-  window    one DeviceOnlineHistory.get_train_data at T = 128, B = 16 on (4, 84, 84) uint8 frames
+  window    one DeviceOnlineHistory.get_train_data at T = 128, B = 16 on (4, 84, 84) uint8 frames, and the same with a
+            recurrent state of S = 1024 float32 words (hx, cx of an LSTM 512) and the initials flag moved beside every row
   acting    one vector step of the device actor at 16 envs (catch_ppo.json's network, generic device path)
 
     python tools/actor_critic_probe.py [--iters 200] [--repeats 5]      -> one JSON line
@@ -168,7 +169,7 @@ def mountaincar_step_time(E, iters, repeats):
     return {"E": E, "step_us_median": round(sorted(s)[len(s) // 2], 1)}
 
 
-def window_time(iters):
+def window_time(iters, state_f32=0):
     from rltime_amd.acting.acting_interface import DeviceSamples
     from rltime_amd.history.online_device import DeviceOnlineHistory
     T, B = 128, 16
@@ -180,9 +181,15 @@ def window_time(iters):
     frames = torch.randint(0, 256, (B, 4, 84, 84), dtype=torch.uint8, device="cuda")
     step = dict(frames=frames, actions=torch.zeros(B, dtype=torch.int32, device="cuda"), policy=torch.zeros(B, 2, device="cuda"),
                 rewards=torch.ones(B, device="cuda"), dones=torch.zeros(B, dtype=torch.uint8, device="cuda"))
+    example = {"x": frames[0].cpu().numpy(), "layer0_state": {}}
+    if state_f32:
+        H = state_f32 // 2
+        step.update(state=torch.randn(B, state_f32, device="cuda"), initials=torch.zeros(B, device="cuda"))
+        example["layer1_state"] = {"hx": step["state"][0, :H].cpu().numpy(), "cx": step["state"][0, H:].cpu().numpy(),
+                                   "initials": step["initials"][0].cpu().numpy()}
     times = []
     for _ in range(iters):
-        s = DeviceSamples({"x": None, "layer0_state": {}}, B, 0)
+        s = DeviceSamples(example, B, 0)
         for _ in range(T):
             s.append(**step)
         hist.update(s)
@@ -195,7 +202,8 @@ def window_time(iters):
     times = sorted(times[1:])
     nbytes = 4 * T * B * 4 * 84 * 84                          # both blocks read and written
     med = times[len(times) // 2]
-    return {"T": T, "B": B, "get_train_data_us_median": round(med, 1), "get_train_data_us_min": round(times[0], 1),
+    return {"T": T, "B": B, "state_f32": state_f32, "state_MB": round(4 * T * B * 4 * state_f32 / 1e6, 1),
+            "get_train_data_us_median": round(med, 1), "get_train_data_us_min": round(times[0], 1),
             "observation_GBps_at_median": round(nbytes / med / 1e3, 1), "ring_capacity_steps": hist.capacity}
 
 
@@ -225,6 +233,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("actor_critic_probe: no GPU visible; timings are taken on the device only")
     out = {"loss": [loss_times(512, A, a.iters, a.repeats) for A in (6, 18)], "window": window_time(max(8, a.iters // 10)),
+           "window_recurrent": window_time(max(8, a.iters // 10), state_f32=1024),
            "acting": acting_time(a.iters),
            "normal_loss": [normal_loss_times(M, 1, a.iters, a.repeats) for M in (128, 512)],
            "normal_head": [normal_head_time(E, 1, a.iters, a.repeats) for E in (128, 512)],
