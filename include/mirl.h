@@ -887,6 +887,38 @@ int mirl_catch_env_step_pre(int32_t E, int32_t P, int32_t S, int32_t G, int32_t 
                             float* rewards_out, uint8_t* dones_out, int32_t clip_rewards, float* ep_reward, int32_t* ep_len,
                             float* out_reward, int32_t* out_len, int32_t* action_counts, uint64_t* rng_step, uint64_t step,
                             void* stream);
+/* One step of Flappy as a device-native vector env (csrc/acting.hip k_flappy_env_step): an R x C grid of cell x cell pixel
+ * cells (R = H / cell rows, row 0 on top; C = W / cell columns) on P <= 4 history planes of H x W uint8, plane P - 1 newest.
+ * Required: H % cell == 0, W % cell == 0, W % 4 == 0, H * W % 16 == 0, 4 <= R <= 255, 3 <= C <= 255, 1 <= gap < R,
+ * spacing >= 2, A >= 2, max_episode_steps >= 1, H, W <= 8192, E <= 65535.  The bird lives in column 1.  One step on action a,
+ * in this order: v <- -2 if a == 1 else min(v + 1, 2) (any other value: no flap); y <- y + v, and y < 0 gives y = 0, v = 0;
+ * tau <- tau + 1; pipe j = 0, 1, .. stands in column C + j * spacing - tau (on screen in [0, C - 1]) and is at the bird when
+ * that is 1; dead <- y > R - 1, or a pipe is at the bird and not (top_j <= y < top_j + gap); passed <- a pipe is at the bird
+ * and not dead; reward <- death_reward if dead, 1 if passed, else 0; done <- dead or tau == max_episode_steps.  On done the
+ * next episode starts in the same step (n <- n + 1, tau <- 0, y <- R / 2, v <- 0, history cleared) and obs is its reset
+ * frame; rewards / dones are those of the step that ended.  top_j = (word 0 of Philox4x32-10 * (R - gap + 1)) >> 32 with key
+ * = seed ^ 0xF1A9 (low word, high word), counter = {env, j, n, 0x52544D45} (csrc/philox.hpp philox_4x32(seed ^ 0xF1A9,
+ * n << 32 | j, env)), n the env's episode number, counted from 0 and never reset.  obs [E][P][H][W]: plane P - 1 - k shows
+ * the state k steps ago in the current episode — the bird cell 255, every on-screen pipe's cells outside its gap 128 at that
+ * step's scroll (the bird is tested first; a live bird in a pipe's column is inside the gap, so they never coincide), 0
+ * elsewhere — or zeros when k > tau.  `state` is [2][E] 16-byte records {bird rows now | 1 | 2 | 3 steps ago as bytes 0..3,
+ * v + 2, tau, n} and `clock` the pair of step words: the launch reads half `slot` of both and writes half slot ^ 1.
+ * reset_all = 1: every env restarts episode n of its old record (tau = 0, y = R / 2, v = 0; n is NOT advanced, nor is the
+ * clock); rewards 0, dones 1; actions may be NULL.  state, clock and obs 16-byte aligned.  Bad arguments return
+ * MIRL_ERR_ARG and write nothing.                                                                                          */
+int mirl_flappy_env_step(int32_t E, int32_t P, int32_t H, int32_t W, int32_t cell, int32_t gap, int32_t spacing, int32_t A,
+                         int32_t max_episode_steps, float death_reward, const int32_t* actions, void* state, uint64_t* clock,
+                         int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards, uint8_t* dones,
+                         void* stream);
+/* mirl_flappy_env_step and mirl_actor_pre as ONE launch (arguments: those of the two calls, the pre-step's from H on).       */
+int mirl_flappy_env_step_pre(int32_t E, int32_t P, int32_t H, int32_t W, int32_t cell, int32_t gap, int32_t spacing, int32_t A,
+                             int32_t max_episode_steps, float death_reward, const int32_t* actions, void* state, uint64_t* clock,
+                             int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards, uint8_t* dones,
+                             int32_t H_pre, int32_t A_pre, const int32_t* actions_pre, const float* h, const float* c,
+                             float* xh_tail, int64_t xh_pitch, float* c_in, float* state_pack, float* initials,
+                             float* rewards_out, uint8_t* dones_out, int32_t clip_rewards, float* ep_reward, int32_t* ep_len,
+                             float* out_reward, int32_t* out_len, int32_t* action_counts, uint64_t* rng_step, uint64_t step,
+                             void* stream);
 /* One step of CartPole as a device-native vector env (csrc/acting.hip k_cartpole_env_step): one thread per env, float64.
  * `state` is [E] 48-byte records {double x[4] = cart position, cart velocity, pole angle, pole angular velocity; int64
  * episodes_started; int32 t; int32 pad} that the launch reads and writes IN PLACE — there is no clock and no pair of halves,

@@ -251,6 +251,11 @@ _SIGNATURES = {
     "mirl_catch_env_step": [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _u64, _i32, _vp, _vp, _vp, _vp],
     "mirl_catch_env_step_pre": [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _u64, _i32, _vp, _vp, _vp,
                                 _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp],
+    "mirl_flappy_env_step": [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _vp, _i32, _u64, _i32,
+                             _vp, _vp, _vp, _vp],
+    "mirl_flappy_env_step_pre": [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _vp, _i32, _u64, _i32,
+                                 _vp, _vp, _vp,
+                                 _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp],
     "mirl_cartpole_env_step": [_i32, _i32, _vp, _vp, _u64, _i32, _vp, _vp, _vp, _vp],
     "mirl_mountaincar_env_step": [_i32, _i32, _vp, _vp, _u64, _i32, _vp, _vp, _vp, _vp],
     "mirl_actor_pre": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp,

@@ -273,6 +273,122 @@ k_catch_env_step(CatchArgs a, ActorPreArgs pre) {
   }
 }
 
+// One step of Flappy as a device-native vector env (acting/flappy_env.py): a bird in column 1 of an R x C grid of cell x cell
+// pixel cells (R = H / cell rows, row 0 on top; C = W / cell columns) falls under gravity or flaps, while pipes D columns
+// apart scroll left one column per step; each pipe spans every row but a gap of g rows.  On action a, in this order:
+//   v <- -2 if a == 1 else min(v + 1, 2);  y <- y + v, and y < 0 -> y = 0, v = 0;  tau <- tau + 1;
+//   pipe j (j = 0, 1, ..) stands in column C + j D - tau and is AT THE BIRD when that is 1;
+//   dead <- y > R - 1, or a pipe is at the bird and not (top_j <= y < top_j + g);  passed <- a pipe at the bird and not dead;
+//   reward <- death_reward if dead, 1 if passed, else 0;  done <- dead or tau == max_steps;
+//   done: n <- n + 1, tau <- 0, y <- R / 2, v <- 0 and the frame returned is the new episode's reset frame.
+// top_j = (word 0 of philox_4x32(seed ^ 0xF1A9, call = n << 32 | j, lane = env) * (R - g + 1)) >> 32 with n the env's
+// episode number (counted from 0, never reset): a function of (seed, env, n, j) only — the seed's two halves are the
+// Philox key, (j, n) counter words 1 and 2, env counter word 0.
+// The env's state is ONE 16-byte record {bird rows now | 1 | 2 | 3 steps ago as bytes 0..3, v + 2, tau, n}, kept like Catch's
+// as a pair of blocks read / written alternately next to the clock pair: every workgroup of an env reads the old record
+// and the action and recomputes the transition (at most one Philox block; no exchange, no atomics), workgroup 0 writes the
+// new record, reward, done and the clock.  The P history planes are rebuilt from the record — the previous observation is
+// never read: plane P - 1 - k shows the state k steps ago (bird cell 255, pipe cells outside the gap 128 at that step's
+// scroll) and is zero when k > tau.  A live bird in a pipe's column is inside the gap, so bird and pipe cells never
+// coincide; the bird is tested first and would win.  Each workgroup first tabulates in LDS, per plane and grid column, the
+// gap top of the pipe standing there (0xFF: none) — at most ceil(P C / 256) Philox blocks per thread — and the pixel loop
+// looks columns up.  reset_all: every env restarts episode n of its old record (a zeroed record: episode 0); the clock
+// is not advanced.
+struct FlappyArgs {
+  int P, H, W, cell, R, C, gap, spacing, max_steps, plane_q, reset_all;
+  float death_reward;
+  const int32_t* actions; const uint4* state_in; uint4* state_out;
+  const uint64_t* clock_in; uint64_t* clock_out; uint64_t seed;
+  uint4* obs; float* rewards; uint8_t* dones;
+};
+
+__device__ __forceinline__ int flappy_gap_top(uint64_t seed, uint32_t n, uint32_t j, int e, int span) {
+  uint32_t r[4];
+  philox_4x32(seed ^ 0xF1A9ull, ((uint64_t)n << 32) | (uint64_t)j, (uint32_t)e, r);
+  return (int)(((uint64_t)r[0] * (uint64_t)span) >> 32);
+}
+
+template <bool PRE>
+__global__ void __launch_bounds__(256)
+k_flappy_env_step(FlappyArgs a, ActorPreArgs pre) {
+  __shared__ uint8_t tops[4 * 256];                     // [k][grid column]: gap top of the pipe there k steps ago, 0xFF = none
+  const int e = blockIdx.y;
+  const int R = a.R, C = a.C, D = a.spacing, g = a.gap, span = R - g + 1;
+  const uint64_t t = *a.clock_in + (a.reset_all ? 0ull : 1ull);   // every workgroup reads the word nobody writes in this launch
+  const uint4 s = a.state_in[e];
+  uint32_t n = s.w, rows = 0;
+  int v = 0, tau = 0, dn = 1;
+  float rr = 0.0f;
+  if (!a.reset_all) {
+    const int act = a.actions[e];
+    v = (int)s.y - 2;
+    v = act == 1 ? -2 : (v + 1 > 2 ? 2 : v + 1);
+    int y = (int)(s.x & 0xFFu) + v;
+    if (y < 0) { y = 0; v = 0; }
+    tau = (int)s.z + 1;
+    const int q = tau + 1 - C;                          // pipe j is at the bird when C + j D - tau == 1
+    const bool at = q >= 0 && q % D == 0;
+    bool dead = y > R - 1;
+    if (at && !dead) {
+      const int top = flappy_gap_top(a.seed, n, (uint32_t)(q / D), e, span);
+      dead = !(top <= y && y < top + g);
+    }
+    dn = (dead || tau == a.max_steps) ? 1 : 0;
+    rr = dead ? a.death_reward : (at ? 1.0f : 0.0f);
+    rows = (s.x << 8) | ((uint32_t)y & 0xFFu);
+  }
+  if (dn) {                                             // a new episode starts in the same step
+    if (!a.reset_all) n += 1u;
+    tau = 0; v = 0;
+    rows = (uint32_t)(R / 2) * 0x01010101u;
+  }
+  for (int i = threadIdx.x; i < a.P * C; i += 256) {
+    const int k = i / C, col = i - k * C;
+    const int q = col + (tau - k) - C;                  // pipe j stood in column C + j D - (tau - k)
+    int top = 0xFF;
+    if (q >= 0 && q % D == 0) top = flappy_gap_top(a.seed, n, (uint32_t)(q / D), e, span);
+    tops[k * 256 + col] = (uint8_t)top;
+  }
+  __syncthreads();
+  // frames: plane P-1-k shows the state k steps ago; planes from before the episode began are zero
+  const int W = a.W, cell = a.cell, plane_q = a.plane_q;
+  uint4* dst = a.obs + (int64_t)e * a.P * plane_q;
+  for (int c = blockIdx.x * 256 + threadIdx.x; c < a.P * plane_q; c += gridDim.x * 256) {
+    const int p = c / plane_q, k = a.P - 1 - p;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (k <= tau) {
+      const int o = (c - p * plane_q) * 16;             // first pixel of the chunk in its plane
+      int py = o / W, px = o - py * W;
+      int ry = py / cell, sy = py - ry * cell, cx = px / cell, sx = px - cx * cell;
+      const int yk = (int)((rows >> (8 * k)) & 0xFFu);
+      const uint8_t* tk = tops + k * 256;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int top = tk[cx];
+        uint32_t val = 0u;
+        if (cx == 1 && ry == yk) val = 255u;
+        else if (top != 0xFF && (ry < top || ry >= top + g)) val = 128u;
+        w[j >> 2] |= val << (8 * (j & 3));
+        if (++sx == cell) { sx = 0; ++cx; }
+        if (++px == W) {                                // the chunk straddles pixel rows when W % 16 != 0
+          px = 0; cx = 0; sx = 0;
+          if (++sy == cell) { sy = 0; ++ry; }
+        }
+      }
+    }
+    dst[c] = uint4{w[0], w[1], w[2], w[3]};
+  }
+  if (blockIdx.x == 0) {
+    if (threadIdx.x == 0) {
+      a.state_out[e] = uint4{rows, (uint32_t)(v + 2), (uint32_t)tau, n};
+      a.rewards[e] = rr;
+      a.dones[e] = (uint8_t)dn;
+      if (e == 0) *a.clock_out = t;                     // the OTHER word of the pair: the next launch reads it
+    }
+    if (PRE) actor_pre_env(pre, e, rr, dn);
+  }
+}
+
 // One step of CartPole as a device-native vector env (acting/cartpole_device_env.py): the cart-pole of
 // acting/cartpole_env.py (Barto, Sutton & Anderson 1983; Euler steps of 0.02 s) in float64, one thread per env.  The env's
 // whole state is ONE 48-byte record that only its thread reads and writes, in place — no shared clock, no pair of halves,
@@ -664,6 +780,68 @@ extern "C" int mirl_catch_env_step_pre(int32_t E, int32_t P, int32_t S, int32_t 
   int gx = (row_q + 255) / 256; if (gx > 8) gx = 8;
   mirl::ProfScope ps("k_catch_env_step_pre", (double)E * (double)row_q * 16.0 + (double)E * H * 4.0 * 6.0, (hipStream_t)stream);
   hipLaunchKernelGGL(mirl::k_catch_env_step<true>, dim3(gx, E), dim3(256), 0, (hipStream_t)stream, a, p);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
+static int fill_flappy(mirl::FlappyArgs& a, int32_t E, int32_t P, int32_t H, int32_t W, int32_t cell, int32_t gap, int32_t spacing,
+                       int32_t A, int32_t max_episode_steps, float death_reward, const int32_t* actions, void* state, uint64_t* clock,
+                       int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards, uint8_t* dones) {
+  // (E is a grid dimension; H, W <= 8192 keep every pixel index of an env's P planes in 32 bits; R, C <= 255 fit the
+  // record's bytes and the LDS column table, whose 0xFF means "no pipe")
+  const bool dims_ok = E > 0 && E <= 65535 && P >= 1 && P <= 4 && cell >= 1 && H >= 1 && H <= 8192 && W >= 1 && W <= 8192 &&
+                       H % cell == 0 && W % cell == 0 && W % 4 == 0 && ((int64_t)H * W) % 16 == 0;
+  const int R = dims_ok ? H / cell : 0, C = dims_ok ? W / cell : 0;
+  if (!dims_ok || R < 4 || R > 255 || C < 3 || C > 255 || gap < 1 || gap >= R || spacing < 2 || A < 2 || max_episode_steps < 1 ||
+      (slot != 0 && slot != 1) || (reset_all != 0 && reset_all != 1) || (!reset_all && !actions) || !state || !clock || !obs ||
+      !rewards || !dones || !mirl::aligned16(state, clock, obs))
+    return mirl::fail(MIRL_ERR_ARG, "bad flappy_env_step arguments (1 <= P <= 4, H % cell == 0, W % cell == 0, W % 4 == 0, H * W % 16 == 0, "
+                                    "4 <= H / cell <= 255, 3 <= W / cell <= 255, 1 <= gap < H / cell, spacing >= 2, A >= 2, "
+                                    "max_episode_steps >= 1, 16-byte aligned state / clock / obs, slot 0 | 1)");
+  a.P = P; a.H = H; a.W = W; a.cell = cell; a.R = R; a.C = C; a.gap = gap; a.spacing = spacing; a.max_steps = max_episode_steps;
+  a.plane_q = H * W / 16; a.reset_all = reset_all; a.death_reward = death_reward;
+  a.actions = actions; a.state_in = (const uint4*)state + (int64_t)slot * E; a.state_out = (uint4*)state + (int64_t)(slot ^ 1) * E;
+  a.clock_in = clock + slot; a.clock_out = clock + (slot ^ 1); a.seed = seed;
+  a.obs = (uint4*)obs; a.rewards = rewards; a.dones = dones;
+  return MIRL_OK;
+}
+
+extern "C" int mirl_flappy_env_step(int32_t E, int32_t P, int32_t H, int32_t W, int32_t cell, int32_t gap, int32_t spacing, int32_t A,
+                                    int32_t max_episode_steps, float death_reward, const int32_t* actions, void* state,
+                                    uint64_t* clock, int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards,
+                                    uint8_t* dones, void* stream) {
+  mirl::FlappyArgs a;
+  int rc = fill_flappy(a, E, P, H, W, cell, gap, spacing, A, max_episode_steps, death_reward, actions, state, clock, slot, seed,
+                       reset_all, obs, rewards, dones);
+  if (rc) return rc;
+  const int row_q = a.P * a.plane_q;
+  int gx = (row_q + 255) / 256; if (gx > 8) gx = 8;
+  mirl::ProfScope ps("k_flappy_env_step", (double)E * (double)row_q * 16.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_flappy_env_step<false>, dim3(gx, E), dim3(256), 0, (hipStream_t)stream, a, mirl::ActorPreArgs{});
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
+extern "C" int mirl_flappy_env_step_pre(int32_t E, int32_t P, int32_t H, int32_t W, int32_t cell, int32_t gap, int32_t spacing, int32_t A,
+                                        int32_t max_episode_steps, float death_reward, const int32_t* actions, void* state,
+                                        uint64_t* clock, int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards,
+                                        uint8_t* dones, int32_t H_pre, int32_t A_pre, const int32_t* actions_pre, const float* h,
+                                        const float* c, float* xh_tail, int64_t xh_pitch, float* c_in, float* state_pack,
+                                        float* initials, float* rewards_out, uint8_t* dones_out, int32_t clip_rewards, float* ep_reward,
+                                        int32_t* ep_len, float* out_reward, int32_t* out_len, int32_t* action_counts, uint64_t* rng_step,
+                                        uint64_t step, void* stream) {
+  mirl::FlappyArgs a;
+  int rc = fill_flappy(a, E, P, H, W, cell, gap, spacing, A, max_episode_steps, death_reward, actions, state, clock, slot, seed,
+                       reset_all, obs, rewards, dones);
+  if (rc) return rc;
+  mirl::ActorPreArgs p;
+  rc = fill_pre(p, E, H_pre, A_pre, actions_pre, h, c, xh_tail, xh_pitch, c_in, state_pack, initials, rewards_out, dones_out,
+                clip_rewards, ep_reward, ep_len, out_reward, out_len, action_counts, rng_step, step);
+  if (rc) return rc;
+  const int row_q = a.P * a.plane_q;
+  int gx = (row_q + 255) / 256; if (gx > 8) gx = 8;
+  mirl::ProfScope ps("k_flappy_env_step_pre", (double)E * (double)row_q * 16.0 + (double)E * H_pre * 4.0 * 6.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_flappy_env_step<true>, dim3(gx, E), dim3(256), 0, (hipStream_t)stream, a, p);
   MIRL_LAUNCH_CHECK();
   return MIRL_OK;
 }

@@ -27,8 +27,8 @@ _EXTRA_FEATURES_KEYS = ("include_action", "include_reward", "include_timestep", 
 
 
 def make_vec_env(env, env_args, num_envs, device, seed=0):
-    """env_args["extra_features"] (true: the defaults; a dict: the wrapper's arguments) wraps 'catch' / 'synthetic-atari'
-    in acting/extra_features.ExtraFeaturesVecEnv — the reference's env_args.wrappers entry of ExtraFeaturesEnvWrapper."""
+    """env_args["extra_features"] (true: the defaults; a dict: the wrapper's arguments) wraps 'catch' / 'flappy' /
+    'synthetic-atari' in acting/extra_features.ExtraFeaturesVecEnv — the reference's env_args.wrappers entry of ExtraFeaturesEnvWrapper."""
     env_args = dict(env_args or {})
     extra = env_args.pop("extra_features", None)
     if extra is None or extra is False:
@@ -85,9 +85,19 @@ def _make_base_vec_env(env, env_args, num_envs, device, seed=0):
         if "frame_shape" in args:
             args["frame_shape"] = tuple(args["frame_shape"])
         return CatchVecEnv(num_envs, device=device, seed=seed, **args)
+    if env == "flappy":
+        # the long-episode device-native game (acting/flappy_env.py: a single HIP kernel per vector step)
+        from rltime_amd.acting.flappy_env import FlappyVecEnv
+        args = dict(env_args or {})
+        unknown = set(args) - {"frame_shape", "cell", "gap", "spacing", "n_actions", "max_episode_steps", "death_reward"}
+        if unknown:
+            raise ValueError("flappy: unknown env_args %s" % sorted(unknown))
+        if "frame_shape" in args:
+            args["frame_shape"] = tuple(args["frame_shape"])
+        return FlappyVecEnv(num_envs, device=device, seed=seed, **args)
     if env != "synthetic-atari":
         raise ValueError(
-            "rltime_amd ships the synthetic vector env ('synthetic-atari'), the device-native game 'catch', its own "
+            "rltime_amd ships the synthetic vector env ('synthetic-atari'), the device-native games 'catch' and 'flappy', its own "
             "CartPole ('CartPole-v0/-v1') and its own 'MountainCarContinuous-v0': real emulators are CPU code outside the scope of this backend (DESIGN.md)")
     from rltime_amd.acting.synthetic_env import SyntheticAtariVecEnv
     args = dict(env_args or {})
