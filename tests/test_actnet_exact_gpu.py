@@ -143,13 +143,13 @@ LSTM_SLICED = [(16, 64, 3136), (17, 512, 3136), (64, 64, 1984)]
 LSTM_RAGGED = [(16, 64, 3136), (17, 512, 3152), (64, 64, 2112)]
 
 
-def _lstm_run(xh, w, b, c_in):
-    """Three launches over one zeroed workspace -> [(h, c)] on the CPU.  xh sits in a NaN buffer 20 floats wider than K with a
+def _lstm_run(xh, w, b, c_in, pad=20):
+    """Three launches over one zeroed workspace -> [(h, c)] on the CPU.  xh sits in a NaN buffer `pad` floats wider than K with a
     NaN row behind it; w and bias are each followed by a NaN row; h and c have a NaN guard row."""
     L = _lib()
     E, K = xh.shape
     H = c_in.shape[1]
-    pitch = K + 20
+    pitch = K + pad
     xb = _nan(E + 1, pitch)
     xb[:E, :K] = xh.float().cuda()
     wb = _nan(4 * H + 1, K)

@@ -15,7 +15,10 @@ from tests import conv1p_probe as cp
 pytestmark = pytest.mark.gpu
 
 ERR_ARG, ERR_STATE = -1, -3
-SHAPES = [(1, 84, 84), (2, 84, 84), (33, 84, 84), (1025, 84, 84), (7, 36, 36), (5, 44, 52), (4, 12, 16), (6, 8, 8), (2, 100, 100)]
+# (1, 120, 80), (5, 120, 80): configs/flappy_iqn_lstm.json's frames, 29 x 19 = 551 positions = 34 tiles of 16 and 7 more; five
+# frames are one four-frame fill of the weight gradient and a tail
+FLAPPY = [(1, 120, 80), (5, 120, 80)]
+SHAPES = [(1, 84, 84), (2, 84, 84), (33, 84, 84), (1025, 84, 84), (7, 36, 36), (5, 44, 52), (4, 12, 16), (6, 8, 8), (2, 100, 100)] + FLAPPY
 
 
 def _p(t):
@@ -104,7 +107,7 @@ def test_forward_does_not_depend_on_the_launch_shape_and_flags_are_checked():
     assert torch.equal(y, big[0:1])
 
 
-@pytest.mark.parametrize("n,h,w", [(2, 84, 84), (257, 84, 84), (2050, 84, 84), (5, 44, 52)])
+@pytest.mark.parametrize("n,h,w", [(2, 84, 84), (257, 84, 84), (2050, 84, 84), (5, 44, 52)] + FLAPPY)
 def test_forward_real_weights_within_tolerance(n, h, w):
     g = torch.Generator(device="cuda").manual_seed(n)
     x = _frames(g, n, h, w)
@@ -168,7 +171,7 @@ def _cl(t):
     return t.contiguous(memory_format=torch.channels_last)
 
 
-@pytest.mark.parametrize("n,h,w", [(1, 84, 84), (2, 84, 84), (3, 36, 36), (2, 44, 52), (4, 12, 16), (3, 8, 8), (1, 100, 100)])
+@pytest.mark.parametrize("n,h,w", [(1, 84, 84), (2, 84, 84), (3, 36, 36), (2, 44, 52), (4, 12, 16), (3, 8, 8), (1, 100, 100)] + FLAPPY)
 def test_weight_gradient_integer_case_is_bit_exact(n, h, w):
     g_ = torch.Generator(device="cuda").manual_seed(n * 100 + w)
     x = _frames(g_, n, h, w)
@@ -180,7 +183,7 @@ def test_weight_gradient_integer_case_is_bit_exact(n, h, w):
         assert got.stride() == like.stride() and torch.equal(got, want)
 
 
-@pytest.mark.parametrize("n,h,w", [(5, 84, 84), (1025, 84, 84), (2051, 84, 84), (1030, 44, 52)])
+@pytest.mark.parametrize("n,h,w", [(5, 84, 84), (1025, 84, 84), (2051, 84, 84), (1030, 44, 52)] + FLAPPY)
 def test_weight_gradient_within_tolerance_and_reproducible(n, h, w):
     g_ = torch.Generator(device="cuda").manual_seed(n)
     x = _frames(g_, n, h, w)
@@ -199,7 +202,7 @@ def test_weight_gradient_within_tolerance_and_reproducible(n, h, w):
     assert err <= max(2.0 * err_lib, 2e-6), (err, err_lib)
 
 
-@pytest.mark.parametrize("n,h,w", [(2, 84, 84), (3, 36, 36), (1, 8, 8), (1027, 84, 84), (1030, 44, 52)])
+@pytest.mark.parametrize("n,h,w", [(2, 84, 84), (3, 36, 36), (1, 8, 8), (1027, 84, 84), (1030, 44, 52)] + FLAPPY)
 def test_masked_weight_gradient_equals_mask_pass_plus_weight_gradient(n, h, w):
     """mirl_conv1p_u8_wrw_masked against the two-launch form (k_relu_bwd_bias_rows, then mirl_conv1p_u8_wrw on its output):
     dW BIT-identical (the same masked values enter the same sums in the same order), db the masked gradient's column sums
@@ -243,7 +246,7 @@ def test_weight_gradient_probe_operands_are_bit_equal_to_float64(name):
 
 def test_coverage_and_refusals_before_any_launch():
     from rltime_amd._lib import lib
-    for h, w in [(84, 84), (36, 36), (44, 52), (12, 16), (8, 8), (100, 100)]:
+    for h, w in [(84, 84), (36, 36), (44, 52), (12, 16), (8, 8), (100, 100), (120, 80)]:
         assert lib.mirl_conv1p_u8_supported(h, w, 32, 8, 4) == 1, (h, w)
     for h, w, f, k, s in [(84, 84, 64, 8, 4), (84, 84, 32, 4, 4), (84, 84, 32, 8, 2), (84, 82, 32, 8, 4), (7, 84, 32, 8, 4),
                           (42, 42, 32, 8, 4), (256, 256, 32, 8, 4)]:

@@ -14,8 +14,10 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+# (1, 48, 32), (3, 48, 32): configs/flappy_dqn.json's frames, 11 x 7 output positions
+FLAPPY = [(1, 48, 32), (3, 48, 32)]
 SHAPES = [(1, 84, 84), (2, 84, 84), (3, 84, 84), (33, 84, 84), (1025, 84, 84), (7, 36, 36), (5, 44, 52), (4, 12, 16),
-          (6, 8, 8), (2, 100, 100)]
+          (6, 8, 8), (2, 100, 100)] + FLAPPY
 
 
 def _call(x, w, b, scale, flags=None):
@@ -48,7 +50,7 @@ def test_integer_weights_are_bit_exact(n, h, w):
     assert torch.equal(_call(x, wt.contiguous(memory_format=torch.channels_last), b, 1.0), want)
 
 
-@pytest.mark.parametrize("n,h,w", [(3, 84, 84), (1025, 84, 84), (5, 44, 52)])
+@pytest.mark.parametrize("n,h,w", [(3, 84, 84), (1025, 84, 84), (5, 44, 52)] + FLAPPY)
 def test_launch_shapes_agree_bitwise(n, h, w):
     g = torch.Generator(device="cuda").manual_seed(7)
     x = torch.randint(0, 256, (n, 4, h, w), dtype=torch.uint8, device="cuda", generator=g)
@@ -92,7 +94,7 @@ def test_unknown_flag_bits_are_refused_before_any_launch():
     assert not bool((y == -12345.0).any())
 
 
-@pytest.mark.parametrize("n,h,w", [(2, 84, 84), (257, 84, 84), (2050, 84, 84), (5, 44, 52)])
+@pytest.mark.parametrize("n,h,w", [(2, 84, 84), (257, 84, 84), (2050, 84, 84), (5, 44, 52)] + FLAPPY)
 def test_real_weights_within_tolerance(n, h, w):
     g = torch.Generator(device="cuda").manual_seed(n)
     x = torch.randint(0, 256, (n, 4, h, w), dtype=torch.uint8, device="cuda", generator=g)
@@ -189,7 +191,7 @@ def _wrw_reference(x, g, scale):
     return w.grad
 
 
-@pytest.mark.parametrize("n,h,w", [(1, 84, 84), (2, 84, 84), (3, 36, 36), (2, 44, 52), (4, 12, 16), (3, 8, 8), (1, 100, 100)])
+@pytest.mark.parametrize("n,h,w", [(1, 84, 84), (2, 84, 84), (3, 36, 36), (2, 44, 52), (4, 12, 16), (3, 8, 8), (1, 100, 100)] + FLAPPY)
 def test_weight_gradient_integer_case_is_bit_exact(n, h, w, wrw_pipe):
     g_ = torch.Generator(device="cuda").manual_seed(n * 100 + w)
     x = torch.randint(0, 256, (n, 4, h, w), dtype=torch.uint8, device="cuda", generator=g_)
@@ -202,7 +204,7 @@ def test_weight_gradient_integer_case_is_bit_exact(n, h, w, wrw_pipe):
         assert got.stride() == like.stride() and torch.equal(got, want)
 
 
-@pytest.mark.parametrize("n,h,w", [(5, 84, 84), (1025, 84, 84), (2051, 84, 84), (1030, 44, 52)])
+@pytest.mark.parametrize("n,h,w", [(5, 84, 84), (1025, 84, 84), (2051, 84, 84), (1030, 44, 52)] + FLAPPY)
 def test_weight_gradient_within_tolerance_and_reproducible(n, h, w, wrw_pipe):
     g_ = torch.Generator(device="cuda").manual_seed(n)
     x = torch.randint(0, 256, (n, 4, h, w), dtype=torch.uint8, device="cuda", generator=g_)
@@ -223,7 +225,7 @@ def test_weight_gradient_within_tolerance_and_reproducible(n, h, w, wrw_pipe):
         assert err <= max(2.0 * err32, 2e-6), (err, err32)
 
 
-@pytest.mark.parametrize("n,h,w", [(2, 84, 84), (3, 36, 36), (1, 8, 8), (1027, 84, 84), (1030, 44, 52)])
+@pytest.mark.parametrize("n,h,w", [(2, 84, 84), (3, 36, 36), (1, 8, 8), (1027, 84, 84), (1030, 44, 52)] + FLAPPY)
 def test_masked_weight_gradient_equals_mask_pass_plus_weight_gradient(n, h, w, wrw_pipe):
     """mirl_conv1_u8_wrw_masked: the layer's ReLU mask (y > 0, cnn.py:47-49) applied while dy is loaded and the bias
     gradient from the same pass, against the two-launch form (k_relu_bwd_bias_rows, then mirl_conv1_u8_wrw on its

@@ -89,11 +89,13 @@ def test_layer_backward_uses_it_and_matches_the_library_path(monkeypatch):
         res.append((xi.grad.clone(), conv.weight.grad.clone(), conv.bias.grad.clone()))
     for a, b, what in zip(res[0], res[1], ("dx", "dW", "db")):
         assert float((a - b).abs().max()) <= 1e-4 * float(b.abs().max()), what
-    # a 21-row input leaves a forward row uncovered: the library path must take it
-    x2 = torch.randn(3, 32, 21, 20, device="cuda").contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    # a 21-row input leaves a forward row uncovered: the library's data gradient must take it, and all three gradients are held
+    # to float64 on the forward's own ReLU mask (tests/test_flappy_shapes_gpu.py states the bounds); dx is exactly 0 on row 20
+    from tests.test_flappy_shapes_gpu import conv_layer_backward_check
     monkeypatch.setattr(fused, "_CONV2_BWD", True)
-    fused.conv_bias_relu(x2, conv).sum().backward()
-    assert x2.grad is not None and x2.grad.shape == x2.shape
+    assert lib.mirl_conv3_fwd_supported(32, 64, 4, 4, 2, 21, 20) == 1 and lib.mirl_conv_wrw_b3_supported(32, 64, 4, 4, 2, 21, 20) == 1
+    conv_layer_backward_check(monkeypatch, 32, 64, 4, 2, 3, 21, 20, ran_yes=("k_conv_wrw_b3", "k_conv_wrw_reduce"),
+                              ran_no=("k_conv2_bwd_data_b3", "k_conv2_bwd_data"), seed=2)
 
 
 # ---- the third conv layer's data gradient (64 -> 64, k 3, s 1) on the bf16 pipe --------------------------------------

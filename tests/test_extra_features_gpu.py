@@ -161,6 +161,14 @@ def _make(kind, env_kind, E, fast, exploration=None, seed=5, extra_args=None, mo
     torch.manual_seed(0)
     if env_kind == "catch":
         base = CatchVecEnv(E, frame_shape=(4, 84, 84), grid=6, n_actions=3, seed=seed)        # episodes of 5 steps
+    elif env_kind == "flappy":
+        # configs/flappy_iqn_lstm.json's game on its (1, 120, 80) frames, the time limit cut to 7 steps so that every env resets
+        from rltime_amd.acting.flappy_env import FlappyVecEnv
+        from rltime_amd.general.config import load_config
+        args = dict(load_config("flappy_iqn_lstm.json")["env_args"])
+        assert args.pop("extra_features") is True and args["frame_shape"] == [1, 120, 80]
+        args["max_episode_steps"] = 7
+        base = FlappyVecEnv(E, device="cuda", seed=seed, **args)
     else:
         # (-stack: the frame-stack contract; such an env has no capturable step, so the fast step goes through step_device)
         base = SyntheticAtariVecEnv(E, frame_shape=(4, 84, 84), n_actions=6, seed=seed, done_prob=done_prob,
@@ -244,6 +252,52 @@ def test_fast_step_takes_the_extras_and_matches_the_generic_device_path(kind, en
         assert np.array_equal(a["extra"].cpu().numpy().view(np.uint32), want.view(np.uint32)), t
         n_done += int(b["dones"].sum())
     assert n_done >= 6                                       # resets happened
+
+
+def test_fast_step_on_the_flappy_frames_matches_the_generic_device_path():
+    """test_fast_step_takes_the_extras_and_matches_the_generic_device_path on the shipped Flappy set-up: (1, 120, 80) frames +
+    extras (X = 4 padded to 16) into configs/flappy_iqn_lstm.json's own model — conv 29 x 19 -> 13 x 8 -> 11 x 6, F = 4224, LSTM
+    512, K = 4752 — dueling IQN, 4 envs, greedy, 12 steps over two get_samples calls.  Everything the env and the selection
+    produce is identical on the two paths; q-values and the stored state within that test's rtol 2e-4 / atol 2e-5."""
+    from rltime_amd.acting.fast_step import FastActingStep
+    from rltime_amd.general.config import load_config
+    from tests.test_flappy_shapes_cpu import LSTM_F, LSTM_H, LSTM_K, LSTM_X, LSTM_XP
+    E, steps = 4, 12
+    model = load_config("flappy_iqn_lstm.json")["model"]
+    outs = []
+    for fast in (True, False):
+        actor, pol, env = _make("iqn", "flappy", E, fast, model=model)
+        assert pol.model.extra_input_layer == 1
+        assert FastActingStep.supports(actor)
+        batch = actor.get_samples(E * 5)
+        more = actor.get_samples(E * (steps - 5))            # a second call: re-selection on the current input state
+        assert (actor._fast is not None and actor._fast is not False) == fast
+        if fast:
+            fs = actor._fast
+            assert (fs.X, fs.Xp, fs.F, fs.H, fs.K) == (LSTM_X, LSTM_XP, LSTM_F, LSTM_H, LSTM_K) == (env.extra_size, 16, 4224, 512, 4752)
+            assert fs.f_lstm and fs.f_conv and fs.conv_dims == (29, 19, 13, 8, 11, 6) and fs.y1.shape == (E, 32, 29, 19)
+            pad = fs.xh[:, fs.F + fs.X:fs.F + fs.Xp]
+            assert pad.numel() > 0 and torch.all(pad == 0) and torch.all(fs.wcat[:, fs.F + fs.X:fs.F + fs.Xp] == 0)
+            assert torch.equal(fs.xh[:, fs.F:fs.F + fs.X], fs.extra)
+        outs.append((batch.vector_steps + more.vector_steps, env))
+    (sa, _), (sb, env_b) = outs
+    assert len(sa) == len(sb) == steps
+    ef = _restate_for(env_b, E)
+    ef.reset()
+    n_done = 0
+    for t, (a, b) in enumerate(zip(sa, sb)):
+        assert a["frames"].shape == (E, 1, 120, 80)
+        assert torch.equal(a["frames"], b["frames"]) and torch.equal(a["dones"], b["dones"]), t
+        assert torch.equal(a["rewards"], b["rewards"]), t
+        assert torch.equal(a["actions"].cpu(), b["actions"].cpu()), t
+        np.testing.assert_allclose(a["policy"].cpu().numpy(), b["policy"].cpu().numpy(), rtol=2e-4, atol=2e-5, err_msg="q %d" % t)
+        assert torch.equal(a["initials"], b["initials"]), t
+        np.testing.assert_allclose(a["state"].cpu().numpy(), b["state"].cpu().numpy(), rtol=2e-4, atol=2e-5, err_msg="state %d" % t)
+        assert a["extra"].dtype == torch.float32 and torch.equal(a["extra"].view(torch.int32), b["extra"].view(torch.int32)), t
+        want = ef.step(b["actions"].cpu().numpy(), b["rewards"].cpu().numpy(), b["dones"].cpu().numpy())
+        assert np.array_equal(a["extra"].cpu().numpy().view(np.uint32), want.view(np.uint32)), t
+        n_done += int(b["dones"].sum())
+    assert n_done >= E                                       # the 7-step limit at the latest: every env was reset
 
 
 def _check_batch_extras(batch, ef_factory):

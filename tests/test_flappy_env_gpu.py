@@ -402,8 +402,9 @@ def test_flappy_extras_equal_the_restatement():
 def test_two_learner_iterations_on_the_shipped_recurrent_config():
     """rltime_amd.train.train on configs/flappy_iqn_lstm.json at 4 envs with warmup_steps / total_steps cut to a few hundred:
     (1, 120, 80) frames + extras through the fused acting step, the device replay and the recurrent IQN learner.  A smoke
-    test of shapes nothing else runs (conv 29 x 19 -> 13 x 8 -> 11 x 6, LSTM projection K = 4224 + 16 + 512), not a
-    learning claim."""
+    test that the pieces fit together at the config's shapes (conv 29 x 19 -> 13 x 8 -> 11 x 6, LSTM projection
+    K = 4224 + 16 + 512), not a learning claim; the kernels are held to float64 at these shapes one by one in
+    tests/test_flappy_shapes_gpu.py (tests/test_flappy_shapes_cpu.py derives the shapes and pins the gates)."""
     import random
     from rltime_amd.acting.fast_step import FastActingStep
     from rltime_amd.general.config import load_config
