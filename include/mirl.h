@@ -570,6 +570,31 @@ int mirl_conv1p_u8_wrw_masked(int64_t N, int32_t H, int32_t W, const uint8_t* x,
                               float scale, float* scratch, float* dw, int64_t ws_o, int64_t ws_h, int64_t ws_w,
                               float* db, void* stream);
 
+/* ---- the same layer from THREE-plane uint8 frames (csrc/conv_in3p.hip): Conv2d(3 -> 32, kernel 8, stride 4) on one RGB
+ * frame per step (the reference's ple_flappy_bird_iqn_lstm.json: observations (3, 120, 80)) or a three-plane history stack.
+ * Arithmetic, wpk, flags, scratch and the masked form exactly as the one-plane family above; the only difference in the
+ * signatures is the weight's channel stride:
+ *   x       uint8 [N][3][H][W]
+ *   weight  float, logical [32][3][8][8] with element strides ws_o, ws_c, ws_h, ws_w (contiguous or channels_last memory)
+ *   y       float [N][OH][OW][32] = relu(conv(x * scale, weight) + bias), NHWC
+ *   dw      float, logical [32][3][8][8] written with element strides ws_o, ws_c, ws_h, ws_w
+ * An output's summation order does not depend on N or on the launch shape; the weight gradient is a fixed partition summed
+ * in a fixed order (no float atomics, bit-identical reruns).
+ * mirl_conv1p3_u8_supported() (host logic only): F = 32, K = 8, S = 4, H >= 8, W >= 8, W % 4 == 0, H*W % 16 == 0 and
+ * the frame's three planes staged as bf16 within 64 KiB of LDS ((3, 100, 100) fits).  Anything else, a null or misaligned
+ * (16 B) pointer and N <= 0 return MIRL_ERR_ARG before anything is launched.                                       */
+int mirl_conv1p3_u8_supported(int32_t H, int32_t W, int32_t F, int32_t K, int32_t S);
+int mirl_conv1p3_u8_wpk_floats(int64_t* out);
+int mirl_conv1p3_u8_fwd(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* weight,
+                        int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w, const float* bias, float scale,
+                        float* wpk, float* y, int32_t flags, void* stream);
+int mirl_conv1p3_u8_wrw_scratch_floats(int64_t* out);
+int mirl_conv1p3_u8_wrw(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* g, float scale,
+                        float* scratch, float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w, void* stream);
+int mirl_conv1p3_u8_wrw_masked(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* dy, const float* y,
+                               float scale, float* scratch, float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h,
+                               int64_t ws_w, float* db, void* stream);
+
 /* ---- data gradient of the second conv layer (csrc/conv_mid.hip).  For the backward
  * autograd derives for `F.relu(conv(x))` (rltime/models/torch/modules/cnn.py:47-49) at
  * Conv2d(32 -> 64, kernel 4, stride 2) (configs/models/cnn_*.json), input IH x IW =
@@ -919,6 +944,22 @@ int mirl_flappy_env_step_pre(int32_t E, int32_t P, int32_t H, int32_t W, int32_t
                              float* rewards_out, uint8_t* dones_out, int32_t clip_rewards, float* ep_reward, int32_t* ep_len,
                              float* out_reward, int32_t* out_len, int32_t* action_counts, uint64_t* rng_step, uint64_t step,
                              void* stream);
+/* The same two steps with the observation in colour: P must be 3, and obs [E][3][H][W] is ONE frame — the current state's,
+ * history depth 1, so the reset frame is drawn like any other — in red, green and blue planes: background (78, 192, 202),
+ * pipe cells (84, 168, 40), the bird cell (250, 200, 30), the bird tested first.  Transition, record, Philox keying,
+ * rewards and dones are those of mirl_flappy_env_step to the bit; arguments as above.                                       */
+int mirl_flappy_env_step_rgb(int32_t E, int32_t P, int32_t H, int32_t W, int32_t cell, int32_t gap, int32_t spacing, int32_t A,
+                             int32_t max_episode_steps, float death_reward, const int32_t* actions, void* state,
+                             uint64_t* clock, int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards,
+                             uint8_t* dones, void* stream);
+int mirl_flappy_env_step_pre_rgb(int32_t E, int32_t P, int32_t H, int32_t W, int32_t cell, int32_t gap, int32_t spacing,
+                                 int32_t A, int32_t max_episode_steps, float death_reward, const int32_t* actions, void* state,
+                                 uint64_t* clock, int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards,
+                                 uint8_t* dones, int32_t H_pre, int32_t A_pre, const int32_t* actions_pre, const float* h,
+                                 const float* c, float* xh_tail, int64_t xh_pitch, float* c_in, float* state_pack,
+                                 float* initials, float* rewards_out, uint8_t* dones_out, int32_t clip_rewards,
+                                 float* ep_reward, int32_t* ep_len, float* out_reward, int32_t* out_len, int32_t* action_counts,
+                                 uint64_t* rng_step, uint64_t step, void* stream);
 /* One step of CartPole as a device-native vector env (csrc/acting.hip k_cartpole_env_step): one thread per env, float64.
  * `state` is [E] 48-byte records {double x[4] = cart position, cart velocity, pole angle, pole angular velocity; int64
  * episodes_started; int32 t; int32 pad} that the launch reads and writes IN PLACE — there is no clock and no pair of halves,

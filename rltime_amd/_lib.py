@@ -186,6 +186,12 @@ _SIGNATURES = {
     "mirl_conv1p_u8_wrw_scratch_floats": [_P(_i64)],
     "mirl_conv1p_u8_wrw": [_i64, _i32, _i32, _vp, _vp, C.c_float, _vp, _vp, _i64, _i64, _i64, _vp],
     "mirl_conv1p_u8_wrw_masked": [_i64, _i32, _i32, _vp, _vp, _vp, C.c_float, _vp, _vp, _i64, _i64, _i64, _vp, _vp],
+    "mirl_conv1p3_u8_supported": [_i32, _i32, _i32, _i32, _i32],
+    "mirl_conv1p3_u8_wpk_floats": [_P(_i64)],
+    "mirl_conv1p3_u8_fwd": [_i64, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _i64, _vp, C.c_float, _vp, _vp, _i32, _vp],
+    "mirl_conv1p3_u8_wrw_scratch_floats": [_P(_i64)],
+    "mirl_conv1p3_u8_wrw": [_i64, _i32, _i32, _vp, _vp, C.c_float, _vp, _vp, _i64, _i64, _i64, _i64, _vp],
+    "mirl_conv1p3_u8_wrw_masked": [_i64, _i32, _i32, _vp, _vp, _vp, C.c_float, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp],
     "mirl_conv2_bwd_data_supported": [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32],
     "mirl_conv2_bwd_data": [_i64, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp],
     "mirl_conv2_bwd_data_wpk_floats": [_P(_i64)],
@@ -256,6 +262,11 @@ _SIGNATURES = {
     "mirl_flappy_env_step_pre": [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _vp, _i32, _u64, _i32,
                                  _vp, _vp, _vp,
                                  _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp],
+    "mirl_flappy_env_step_rgb": [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _vp, _i32, _u64, _i32,
+                                 _vp, _vp, _vp, _vp],
+    "mirl_flappy_env_step_pre_rgb": [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _vp, _i32, _u64, _i32,
+                                     _vp, _vp, _vp,
+                                     _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp],
     "mirl_cartpole_env_step": [_i32, _i32, _vp, _vp, _u64, _i32, _vp, _vp, _vp, _vp],
     "mirl_mountaincar_env_step": [_i32, _i32, _vp, _vp, _u64, _i32, _vp, _vp, _vp, _vp],
     "mirl_actor_pre": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp,

@@ -14,7 +14,7 @@ weight concatenations, rand / randint, fills).  Here one step is
     mirl_replay_ingest        1 copy + 1 launch  frames + state + scalars + plan + tree, straight
                                                from the static buffers (no clones)
     mirl_conv1_u8_fwd         2 launches       input layer from the env's uint8 frames (mirl_conv1p_u8_fwd for
-                                               one-plane observations)
+                                               one-plane observations, mirl_conv1p3_u8_fwd for three planes)
     network                   6 launches       csrc/actnet.hip: conv 2, conv 3 (bias + ReLU in the epilogue, layer 3
                                                writes the LSTM product's input rows), [features | h] x [W_ih | W_hh]^T
                                                with the cell in the same launch, quantile embedding x features, hidden
@@ -171,7 +171,7 @@ class FastActingStep:
         _, hh, ww = obs0.shape[1:]
         k, s = c1.kernel_size[0], c1.stride[0]
         self.y1 = torch.empty((E, c1.out_channels, (hh - k) // s + 1, (ww - k) // s + 1), memory_format=torch.channels_last, **f32)
-        self.conv1_family = conv_u8_family(obs0.shape[1])        # four-plane or one-plane kernels (csrc/conv_in.hip / conv_in1p.hip)
+        self.conv1_family = conv_u8_family(obs0.shape[1])        # by plane count: csrc/conv_in.hip (4), conv_in1p.hip (1), conv_in3p.hip (3)
         self.wpk = torch.empty(self.conv1_family.wpk_floats(), **f32)
         self.xh = torch.zeros((E, K), **f32)                     # [conv features (NCHW order) | extras | zeros | masked h]
         self.extra = torch.zeros((E, X), **f32) if X else None   # the compact rows the replay ingests as `extra`

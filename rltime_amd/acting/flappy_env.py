@@ -15,7 +15,13 @@ A step is ONE kernel (csrc/acting.hip k_flappy_env_step) that applies the action
 and done; the env's state is one 16-byte record per env that lives on the device next to the step counter, both as
 pairs read / written alternately.  Like Catch's step it writes caller-owned static buffers with a fixed launch, so it
 rides in the captured rollout graph (acting/fast_step.py) — with the actions read from a static buffer bound once
-(`bind_actions`).  There is no CPU implementation."""
+(`bind_actions`).  There is no CPU implementation.
+
+`rgb=True` (the reference's ple_flappy_bird_iqn_lstm.json trains on RGB frames): frame_shape is (3, H, W) and the
+observation is ONE step's frame — the current state's, history depth 1, the reset frame drawn like any other — in red,
+green and blue planes with a fixed palette (PALETTE below; the bird still wins over a pipe).  The same kernel body
+renders it (mirl_flappy_env_step_rgb); dynamics, record, Philox keying, rewards and dones are exactly those of the
+intensity env, and the planes are NOT a history stack (`frame_stack` is False: frame_stack_dedup storage is refused)."""
 import numpy as np
 import torch
 
@@ -23,7 +29,11 @@ from rltime_amd._lib import lib, check, ptr, stream
 from rltime_amd.spaces import Box, Discrete
 
 
-def check_geometry(frame_shape, cell, gap, spacing, n_actions, max_episode_steps):
+# rgb=True: (red, green, blue) of a background, pipe and bird pixel
+PALETTE = {"background": (78, 192, 202), "pipe": (84, 168, 40), "bird": (250, 200, 30)}
+
+
+def check_geometry(frame_shape, cell, gap, spacing, n_actions, max_episode_steps, rgb=False):
     """-> (P, H, W, R, C) or a ValueError that names the rule broken (nothing is allocated before this passes)."""
     if len(tuple(frame_shape)) != 3:
         raise ValueError("flappy: frame_shape is (P, H, W)")
@@ -33,6 +43,8 @@ def check_geometry(frame_shape, cell, gap, spacing, n_actions, max_episode_steps
         raise ValueError("flappy: cell >= 1")
     if not 1 <= P <= 4:
         raise ValueError("flappy: 1 <= P <= 4 history planes (frame_shape[0] = %d)" % P)
+    if rgb and P != 3:
+        raise ValueError("flappy: rgb frames are (3, H, W), one frame in three colour planes (frame_shape[0] = %d)" % P)
     if H < 1 or W < 1 or H % s or W % s:
         raise ValueError("flappy: H %% cell == 0 and W %% cell == 0 (H = %d, W = %d, cell = %d)" % (H, W, s))
     if W % 4 or (H * W) % 16:
@@ -55,12 +67,18 @@ def check_geometry(frame_shape, cell, gap, spacing, n_actions, max_episode_steps
 
 class FlappyVecEnv:
     def __init__(self, num_envs, frame_shape=(4, 48, 32), cell=4, gap=3, spacing=4, n_actions=2, max_episode_steps=54000,
-                 death_reward=-1.0, device="cuda", seed=0):
-        P, H, W, R, C = check_geometry(frame_shape, cell, gap, spacing, n_actions, max_episode_steps)
+                 death_reward=-1.0, device="cuda", seed=0, rgb=False):
+        P, H, W, R, C = check_geometry(frame_shape, cell, gap, spacing, n_actions, max_episode_steps, rgb)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("FlappyVecEnv steps on the GPU only (csrc/acting.hip k_flappy_env_step): there is no CPU implementation")
         self.num_envs = int(num_envs)
+        self.rgb = bool(rgb)
+        if self.rgb:
+            # what the fast acting step's trusted_stack reads (frame_stack_dedup storage): colour planes are no history
+            self.frame_stack = False
+        self._step, self._step_pre = (("mirl_flappy_env_step_rgb", "mirl_flappy_env_step_pre_rgb") if self.rgb else
+                                      ("mirl_flappy_env_step", "mirl_flappy_env_step_pre"))
         self.observation_space = Box(0, 255, (P, H, W), np.uint8)
         self.action_space = Discrete(int(n_actions))
         self.rows, self.columns, self.gap, self.spacing = R, C, int(gap), int(spacing)
@@ -93,7 +111,7 @@ class FlappyVecEnv:
         """Every env restarts the episode its record numbers (0 for a new env); neither that number nor the step counter
         is advanced."""
         obs, rewards, dones = self._fresh()
-        check(lib.mirl_flappy_env_step(*self._args(obs, rewards, dones, reset_all=1), stream()), "mirl_flappy_env_step")
+        check(getattr(lib, self._step)(*self._args(obs, rewards, dones, reset_all=1), stream()), self._step)
         self._slot ^= 1
         self._started = True
         return obs
@@ -117,13 +135,13 @@ class FlappyVecEnv:
     def step_into(self, obs_out, rewards_out, dones_out):
         """obs_out uint8 [E, P, H, W], rewards_out float32 [E], dones_out uint8 [E] <- one step on the bound actions."""
         self._need_actions()
-        check(lib.mirl_flappy_env_step(*self._args(obs_out, rewards_out, dones_out), stream()), "mirl_flappy_env_step")
+        check(getattr(lib, self._step)(*self._args(obs_out, rewards_out, dones_out), stream()), self._step)
         self._slot ^= 1
 
     def step_pre(self, obs_out, rewards_out, dones_out, pre_args):
         """The env step and the actor's pre-step as ONE launch; pre_args: mirl_actor_pre's arguments from H on."""
         self._need_actions()
-        check(lib.mirl_flappy_env_step_pre(*self._args(obs_out, rewards_out, dones_out), *pre_args), "mirl_flappy_env_step_pre")
+        check(getattr(lib, self._step_pre)(*self._args(obs_out, rewards_out, dones_out), *pre_args), self._step_pre)
         self._slot ^= 1
 
     def advance_host(self):

@@ -294,8 +294,11 @@ k_catch_env_step(CatchArgs a, ActorPreArgs pre) {
 // gap top of the pipe standing there (0xFF: none) — at most ceil(P C / 256) Philox blocks per thread — and the pixel loop
 // looks columns up.  reset_all: every env restarts episode n of its old record (a zeroed record: episode 0); the clock
 // is not advanced.
+// rgb (mirl_flappy_env_step_rgb): the P = 3 planes are the red, green and blue planes of ONE frame, the current state's
+// (history depth 1: nothing is ever "before the episode", the reset frame is drawn) — background (78, 192, 202), pipe
+// (84, 168, 40), bird (250, 200, 30); the transition, the record and the draws are the same lines.
 struct FlappyArgs {
-  int P, H, W, cell, R, C, gap, spacing, max_steps, plane_q, reset_all;
+  int P, H, W, cell, R, C, gap, spacing, max_steps, plane_q, reset_all, rgb;
   float death_reward;
   const int32_t* actions; const uint4* state_in; uint4* state_out;
   const uint64_t* clock_in; uint64_t* clock_out; uint64_t seed;
@@ -342,7 +345,8 @@ k_flappy_env_step(FlappyArgs a, ActorPreArgs pre) {
     tau = 0; v = 0;
     rows = (uint32_t)(R / 2) * 0x01010101u;
   }
-  for (int i = threadIdx.x; i < a.P * C; i += 256) {
+  const int depth = a.rgb ? 1 : a.P;                    // history planes: the steps back that are drawn
+  for (int i = threadIdx.x; i < depth * C; i += 256) {
     const int k = i / C, col = i - k * C;
     const int q = col + (tau - k) - C;                  // pipe j stood in column C + j D - (tau - k)
     int top = 0xFF;
@@ -354,7 +358,10 @@ k_flappy_env_step(FlappyArgs a, ActorPreArgs pre) {
   const int W = a.W, cell = a.cell, plane_q = a.plane_q;
   uint4* dst = a.obs + (int64_t)e * a.P * plane_q;
   for (int c = blockIdx.x * 256 + threadIdx.x; c < a.P * plane_q; c += gridDim.x * 256) {
-    const int p = c / plane_q, k = a.P - 1 - p;
+    const int p = c / plane_q, k = a.rgb ? 0 : a.P - 1 - p;
+    // what a background, pipe and bird pixel is in plane p
+    const uint32_t bgv = a.rgb ? (0xCAC04Eu >> (8 * p)) & 0xFFu : 0u, pipev = a.rgb ? (0x28A854u >> (8 * p)) & 0xFFu : 128u,
+                   birdv = a.rgb ? (0x1EC8FAu >> (8 * p)) & 0xFFu : 255u;
     uint32_t w[4] = {0u, 0u, 0u, 0u};
     if (k <= tau) {
       const int o = (c - p * plane_q) * 16;             // first pixel of the chunk in its plane
@@ -365,9 +372,9 @@ k_flappy_env_step(FlappyArgs a, ActorPreArgs pre) {
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         const int top = tk[cx];
-        uint32_t val = 0u;
-        if (cx == 1 && ry == yk) val = 255u;
-        else if (top != 0xFF && (ry < top || ry >= top + g)) val = 128u;
+        uint32_t val = bgv;
+        if (cx == 1 && ry == yk) val = birdv;
+        else if (top != 0xFF && (ry < top || ry >= top + g)) val = pipev;
         w[j >> 2] |= val << (8 * (j & 3));
         if (++sx == cell) { sx = 0; ++cx; }
         if (++px == W) {                                // the chunk straddles pixel rows when W % 16 != 0
@@ -786,7 +793,8 @@ extern "C" int mirl_catch_env_step_pre(int32_t E, int32_t P, int32_t S, int32_t 
 
 static int fill_flappy(mirl::FlappyArgs& a, int32_t E, int32_t P, int32_t H, int32_t W, int32_t cell, int32_t gap, int32_t spacing,
                        int32_t A, int32_t max_episode_steps, float death_reward, const int32_t* actions, void* state, uint64_t* clock,
-                       int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards, uint8_t* dones) {
+                       int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards, uint8_t* dones, bool rgb = false) {
+  if (rgb && P != 3) return mirl::fail(MIRL_ERR_ARG, "flappy_env_step_rgb: P = 3 colour planes");
   // (E is a grid dimension; H, W <= 8192 keep every pixel index of an env's P planes in 32 bits; R, C <= 255 fit the
   // record's bytes and the LDS column table, whose 0xFF means "no pipe")
   const bool dims_ok = E > 0 && E <= 65535 && P >= 1 && P <= 4 && cell >= 1 && H >= 1 && H <= 8192 && W >= 1 && W <= 8192 &&
@@ -799,20 +807,19 @@ static int fill_flappy(mirl::FlappyArgs& a, int32_t E, int32_t P, int32_t H, int
                                     "4 <= H / cell <= 255, 3 <= W / cell <= 255, 1 <= gap < H / cell, spacing >= 2, A >= 2, "
                                     "max_episode_steps >= 1, 16-byte aligned state / clock / obs, slot 0 | 1)");
   a.P = P; a.H = H; a.W = W; a.cell = cell; a.R = R; a.C = C; a.gap = gap; a.spacing = spacing; a.max_steps = max_episode_steps;
-  a.plane_q = H * W / 16; a.reset_all = reset_all; a.death_reward = death_reward;
+  a.plane_q = H * W / 16; a.reset_all = reset_all; a.rgb = rgb ? 1 : 0; a.death_reward = death_reward;
   a.actions = actions; a.state_in = (const uint4*)state + (int64_t)slot * E; a.state_out = (uint4*)state + (int64_t)(slot ^ 1) * E;
   a.clock_in = clock + slot; a.clock_out = clock + (slot ^ 1); a.seed = seed;
   a.obs = (uint4*)obs; a.rewards = rewards; a.dones = dones;
   return MIRL_OK;
 }
 
-extern "C" int mirl_flappy_env_step(int32_t E, int32_t P, int32_t H, int32_t W, int32_t cell, int32_t gap, int32_t spacing, int32_t A,
-                                    int32_t max_episode_steps, float death_reward, const int32_t* actions, void* state,
-                                    uint64_t* clock, int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards,
-                                    uint8_t* dones, void* stream) {
+static int flappy_step(bool rgb, int32_t E, int32_t P, int32_t H, int32_t W, int32_t cell, int32_t gap, int32_t spacing, int32_t A,
+                       int32_t max_episode_steps, float death_reward, const int32_t* actions, void* state, uint64_t* clock,
+                       int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards, uint8_t* dones, void* stream) {
   mirl::FlappyArgs a;
   int rc = fill_flappy(a, E, P, H, W, cell, gap, spacing, A, max_episode_steps, death_reward, actions, state, clock, slot, seed,
-                       reset_all, obs, rewards, dones);
+                       reset_all, obs, rewards, dones, rgb);
   if (rc) return rc;
   const int row_q = a.P * a.plane_q;
   int gx = (row_q + 255) / 256; if (gx > 8) gx = 8;
@@ -822,17 +829,29 @@ extern "C" int mirl_flappy_env_step(int32_t E, int32_t P, int32_t H, int32_t W, 
   return MIRL_OK;
 }
 
-extern "C" int mirl_flappy_env_step_pre(int32_t E, int32_t P, int32_t H, int32_t W, int32_t cell, int32_t gap, int32_t spacing, int32_t A,
-                                        int32_t max_episode_steps, float death_reward, const int32_t* actions, void* state,
-                                        uint64_t* clock, int32_t slot, uint64_t seed, int32_t reset_all, uint8_t* obs, float* rewards,
-                                        uint8_t* dones, int32_t H_pre, int32_t A_pre, const int32_t* actions_pre, const float* h,
-                                        const float* c, float* xh_tail, int64_t xh_pitch, float* c_in, float* state_pack,
-                                        float* initials, float* rewards_out, uint8_t* dones_out, int32_t clip_rewards, float* ep_reward,
-                                        int32_t* ep_len, float* out_reward, int32_t* out_len, int32_t* action_counts, uint64_t* rng_step,
-                                        uint64_t step, void* stream) {
+#define MIRL_FLAPPY_ENV_ARGS                                                                                                      \
+  int32_t E, int32_t P, int32_t H, int32_t W, int32_t cell, int32_t gap, int32_t spacing, int32_t A, int32_t max_episode_steps,  \
+      float death_reward, const int32_t *actions, void *state, uint64_t *clock, int32_t slot, uint64_t seed, int32_t reset_all,  \
+      uint8_t *obs, float *rewards, uint8_t *dones
+#define MIRL_FLAPPY_ENV_PASS \
+  E, P, H, W, cell, gap, spacing, A, max_episode_steps, death_reward, actions, state, clock, slot, seed, reset_all, obs, rewards, dones
+#define MIRL_FLAPPY_PRE_ARGS                                                                                                      \
+  int32_t H_pre, int32_t A_pre, const int32_t *actions_pre, const float *h, const float *c, float *xh_tail, int64_t xh_pitch,    \
+      float *c_in, float *state_pack, float *initials, float *rewards_out, uint8_t *dones_out, int32_t clip_rewards,             \
+      float *ep_reward, int32_t *ep_len, float *out_reward, int32_t *out_len, int32_t *action_counts, uint64_t *rng_step,        \
+      uint64_t step, void *stream
+#define MIRL_FLAPPY_PRE_PASS                                                                                                 \
+  H_pre, A_pre, actions_pre, h, c, xh_tail, xh_pitch, c_in, state_pack, initials, rewards_out, dones_out, clip_rewards, ep_reward, \
+      ep_len, out_reward, out_len, action_counts, rng_step, step, stream
+
+extern "C" int mirl_flappy_env_step(MIRL_FLAPPY_ENV_ARGS, void* stream) { return flappy_step(false, MIRL_FLAPPY_ENV_PASS, stream); }
+// the same step with the observation as ONE frame in three colour planes (P = 3)
+extern "C" int mirl_flappy_env_step_rgb(MIRL_FLAPPY_ENV_ARGS, void* stream) { return flappy_step(true, MIRL_FLAPPY_ENV_PASS, stream); }
+
+static int flappy_step_pre(bool rgb, MIRL_FLAPPY_ENV_ARGS, MIRL_FLAPPY_PRE_ARGS) {
   mirl::FlappyArgs a;
   int rc = fill_flappy(a, E, P, H, W, cell, gap, spacing, A, max_episode_steps, death_reward, actions, state, clock, slot, seed,
-                       reset_all, obs, rewards, dones);
+                       reset_all, obs, rewards, dones, rgb);
   if (rc) return rc;
   mirl::ActorPreArgs p;
   rc = fill_pre(p, E, H_pre, A_pre, actions_pre, h, c, xh_tail, xh_pitch, c_in, state_pack, initials, rewards_out, dones_out,
@@ -844,6 +863,13 @@ extern "C" int mirl_flappy_env_step_pre(int32_t E, int32_t P, int32_t H, int32_t
   hipLaunchKernelGGL(mirl::k_flappy_env_step<true>, dim3(gx, E), dim3(256), 0, (hipStream_t)stream, a, p);
   MIRL_LAUNCH_CHECK();
   return MIRL_OK;
+}
+
+extern "C" int mirl_flappy_env_step_pre(MIRL_FLAPPY_ENV_ARGS, MIRL_FLAPPY_PRE_ARGS) {
+  return flappy_step_pre(false, MIRL_FLAPPY_ENV_PASS, MIRL_FLAPPY_PRE_PASS);
+}
+extern "C" int mirl_flappy_env_step_pre_rgb(MIRL_FLAPPY_ENV_ARGS, MIRL_FLAPPY_PRE_ARGS) {
+  return flappy_step_pre(true, MIRL_FLAPPY_ENV_PASS, MIRL_FLAPPY_PRE_PASS);
 }
 
 extern "C" int mirl_cartpole_env_step(int32_t E, int32_t max_episode_steps, const int32_t* actions, void* state, uint64_t seed,

@@ -1,6 +1,7 @@
-// conv_u8.hpp — what the two input-layer families share (csrc/conv_in.hip: four-plane uint8 frames, csrc/conv_in1p.hip:
-// one plane): the entry points' argument checks and packed-weights bookkeeping, the byte -> bf16 helpers, and of the two
-// bf16-pipe weight-gradient kernels everything but the frame staging loop and the tap walk.  Launch plans: host_util.hpp.
+// conv_u8.hpp — what the input-layer families share (csrc/conv_in.hip: four-plane uint8 frames, csrc/conv_in1p.hip: one
+// plane, csrc/conv_in3p.hip: three): the entry points' argument checks and packed-weights bookkeeping, the byte -> bf16
+// helpers, and of the bf16-pipe weight-gradient kernels everything but the frame staging loop and the tap walk.  Launch
+// plans: host_util.hpp.
 #pragma once
 #include "common.hpp"
 #include "split3.hpp"
@@ -21,7 +22,7 @@ inline int c1_check_args(const char* entry, int64_t N, bool pointers, bool shape
 // Which kernel variant's operand order a wpk scratch block holds, remembered per pointer (host side, one caller thread per
 // the library's contract).  packed = false: `variant` packs it now.  packed = true (flags bit 3): does it hold `variant`'s
 // image?  A block packed by another variant or the other family does not.
-enum { C1_WPK_F32 = 1, C1_WPK_BF16 = 2, C1_WPK_1P = 3 };
+enum { C1_WPK_F32 = 1, C1_WPK_BF16 = 2, C1_WPK_1P = 3, C1_WPK_3P = 4 };
 inline bool c1_wpk_holds(const void* wpk, int variant, bool packed) {
   static std::unordered_map<const void*, int> packed_by;
   if (!packed) { packed_by[wpk] = variant; return true; }

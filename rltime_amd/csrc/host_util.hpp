@@ -20,8 +20,9 @@ inline unsigned capped_grid(int64_t units, int64_t cap) { return (unsigned)(unit
 
 // ---------------------------------------------------------------------------------------------------------------
 // The input layer from uint8 frames, Conv2d(planes -> 32, kernel 8, stride 4): launch plans of csrc/conv_in.hip (four
-// planes, C1_*) and csrc/conv_in1p.hip (one plane, C1P_*).  The entry points take no buffer sizes, so the size queries
-// and the launchers both read the constants and plans below: what a query reports is what a launcher may write.
+// planes, C1_*), csrc/conv_in1p.hip (one plane, C1P_*) and csrc/conv_in3p.hip (three planes, C3P_*).  The entry points
+// take no buffer sizes, so the size queries and the launchers both read the constants and plans below: what a query
+// reports is what a launcher may write.
 constexpr int C1_PLANES = 4, C1_K = 8, C1_S = 4, C1_F = 32, C1_TAPS = C1_K * C1_K;
 constexpr int C1_DW = C1_F * C1_PLANES * C1_TAPS;   // 8192 weight-gradient elements
 constexpr int C1_WGS = 512;                         // most workgroups of a forward or weight-gradient launch (2 per CU) = most slabs
@@ -35,6 +36,15 @@ constexpr int C1P_FWD_WGS = 1024;                   // forward: most resident wo
 constexpr int C1P_FPI = 4;                          // most frames per LDS fill
 constexpr int C1P_WPK = 3 * 2 * 2 * 64 * 4;         // packed weight image in floats: [part][kh half][filter half][lane] x 16 B
 constexpr int64_t C1_SCRATCH_FLOATS = (int64_t)C1_WGS * (C1_DW + C1_F), C1P_SCRATCH_FLOATS = (int64_t)C1P_WGS * C1P_SLAB;
+constexpr int C3P_PLANES = 3, C3P_TG = C3P_PLANES * 4;   // tap groups of 16 taps: the weight gradient's accumulator tiles per filter half
+constexpr int C3P_DW = C1_F * C3P_PLANES * C1_TAPS;  // 6144 weight-gradient elements
+constexpr int C3P_SLAB = C3P_DW + C1_F;             // floats per workgroup slab: weight sums, then the bias sums (masked form)
+constexpr int C3P_WGS = 512;                        // forward and weight gradient: most workgroups (2 per CU, 2 waves per SIMD) = most slabs
+constexpr int C3P_FPI = 4;                          // most frames per LDS fill
+constexpr int C3P_FILL = 32 * 1024;                 // .. and most bytes of one: more than one frame only within this
+constexpr int C3P_WPK = 3 * 6 * 2 * 64 * 4;         // packed weight image in floats: [part][instruction q][filter half][lane] x 16 B
+constexpr size_t C3P_LDS = C1_LDS;                  // what a launch may ask for: the 64 KiB a kernel gets unasked
+constexpr int64_t C3P_SCRATCH_FLOATS = (int64_t)C3P_WGS * C3P_SLAB;
 
 inline int c1_out(int hw) { return (hw - C1_K) / C1_S + 1; }   // output rows / columns of H / W
 
@@ -59,6 +69,13 @@ inline bool c1_shape_ok(int H, int W) {
 inline bool c1p_shape_ok(int H, int W) {
   if (H < C1_K || W < C1_K || H > 4096 || W > 4096 || (W % 4) != 0 || ((H * W) % 16) != 0) return false;
   return (size_t)c1_bf_pitch(H * W, c1_out(W)) * 2 <= C1_LDS;
+}
+
+// three planes: the weight gradient stages one frame's three planes as bf16, each with its tail over-read, within C3P_LDS
+// (64 KiB: (3, 100, 100) takes 60 048 bytes, (3, 120, 80) 57 792); the forward's raw bytes are half of that
+inline bool c3p_shape_ok(int H, int W) {
+  if (H < C1_K || W < C1_K || H > 4096 || W > 4096 || (W % 4) != 0 || ((H * W) % 16) != 0) return false;
+  return (size_t)C3P_PLANES * c1_bf_pitch(H * W, c1_out(W)) * 2 <= C3P_LDS;
 }
 
 struct C1FwdPlan { int fpi, split; unsigned grid; size_t lds; };   // frames per LDS fill, workgroups per frame, launch
@@ -88,6 +105,20 @@ inline C1FwdPlan c1p_fwd_plan(int64_t N, int H, int W) {
   return {fpi, split, capped_grid((N + fpi - 1) / fpi * split, C1P_FWD_WGS), (size_t)fpi * HW};
 }
 
+inline C1FwdPlan c3p_fwd_plan(int64_t N, int H, int W) {
+  const int HW3 = C3P_PLANES * H * W, tiles = (c1_out(H) * c1_out(W) + 15) / 16;
+  // frames per LDS fill: more only once every resident workgroup has a group of its own, and within C3P_FILL
+  int fpi_max = C3P_FILL / HW3;
+  fpi_max = fpi_max < 1 ? 1 : (fpi_max > C3P_FPI ? C3P_FPI : fpi_max);
+  const int64_t fpi64 = N / C3P_WGS;
+  const int fpi = fpi64 < 1 ? 1 : (fpi64 > fpi_max ? fpi_max : (int)fpi64);
+  // few frames: `split` workgroups share one frame's tiles (at least one tile per wave)
+  const int max_split = (tiles + 3) / 4;
+  int split = N >= C3P_WGS ? 1 : (int)((C3P_WGS + N - 1) / N);
+  if (split > max_split) split = max_split;
+  return {fpi, split, capped_grid((N + fpi - 1) / fpi * split, C3P_WGS), (size_t)fpi * HW3};
+}
+
 // bf16: the bf16-pipe kernel (else the f32-pipe one, four planes only, with fpi frames per fill); pitch: halfwords per
 // plane (bf16) or bytes per plane (f32 pipe); slab: floats a workgroup writes at scratch + blockIdx.x * slab
 struct C1WrwPlan { bool bf16; int fpi, pitch, slab; unsigned grid; size_t lds; };
@@ -104,6 +135,10 @@ inline C1WrwPlan c1_wrw_plan(int64_t N, int H, int W, bool masked, bool allow_bf
 inline C1WrwPlan c1p_wrw_plan(int64_t N, int H, int W) {
   const int Pd = c1_bf_pitch(H * W, c1_out(W));
   return {true, 1, Pd, C1P_SLAB, capped_grid(N, C1P_WGS), c1_at_least_slab((size_t)Pd * 2, C1P_SLAB)};
+}
+inline C1WrwPlan c3p_wrw_plan(int64_t N, int H, int W) {
+  const int Pd = c1_bf_pitch(H * W, c1_out(W));
+  return {true, 1, Pd, C3P_SLAB, capped_grid(N, C3P_WGS), c1_at_least_slab((size_t)C3P_PLANES * Pd * 2, C3P_SLAB)};
 }
 
 }  // namespace mirl

@@ -16,8 +16,9 @@ expressions; parity tests in tests/test_fused_gpu.py compare against those):
                      (csrc/conv_in.hip): no converted copy of the frames, no separate
                      bias / ReLU pass; backward = the weight gradient from the same uint8
                      frames, ReLU mask and bias gradient in that kernel.  One-plane frames
-                     (N, 1, H, W) take the second kernel family, csrc/conv_in1p.hip; one
-                     autograd function serves both through a ConvU8Family
+                     (N, 1, H, W) take the second kernel family, csrc/conv_in1p.hip, and
+                     three-plane ones (N, 3, H, W) the third, csrc/conv_in3p.hip; one
+                     autograd function serves all through a ConvU8Family
   cos_embed          IQN cosine features (iqn.py:78-81) in one kernel
   quantile_product   x[m] * relu(phi @ Wq^T + bq)[m, n] (iqn.py:82-102) with a
                      backward that never materialises g*x / g*emb / the mask
@@ -329,10 +330,12 @@ def frames_to_f32_nhwc(x, scale):
 
 class ConvU8Family:
     """One kernel family of the input layer from uint8 frames, by plane count: what differs between csrc/conv_in.hip (four
-    planes) and csrc/conv_in1p.hip (one) above the kernels.  `call(name, ...)` runs `<prefix><name>` on the current stream."""
+    planes), csrc/conv_in1p.hip (one) and csrc/conv_in3p.hip (three) above the kernels.  `call(name, ...)` runs
+    `<prefix><name>` on the current stream."""
 
-    def __init__(self, planes, prefix, fwd_flags, fwd_packed):
+    def __init__(self, planes, prefix, fwd_flags, fwd_packed, planes_in_query=False):
         self.planes, self.prefix = planes, prefix
+        self.planes_in_query = planes_in_query   # `supported` takes the plane count first (the four-plane family's does)
         self.fwd_flags = fwd_flags          # what the autograd forward passes behind `y` to `fwd`
         self.fwd_packed = fwd_packed        # the forward that takes `flags` (bit 3: wpk already holds the packed weights)
 
@@ -342,7 +345,7 @@ class ConvU8Family:
         return (so, sc, sh, sw) if self.planes > 1 else (so, sh, sw)
 
     def supported(self, h, w, f, k, s):
-        planes = (self.planes,) if self.planes > 1 else ()
+        planes = (self.planes,) if self.planes_in_query else ()
         return bool(getattr(_lib().lib, self.prefix + "supported")(*planes, h, w, f, k, s))
 
     def wpk_floats(self):
@@ -356,7 +359,8 @@ class ConvU8Family:
         L.check(getattr(L.lib, self.prefix + name)(*args, L.stream()), self.prefix + name)
 
 
-_CONV_U8 = {4: ConvU8Family(4, "mirl_conv1_u8_", (), "fwd_ex"), 1: ConvU8Family(1, "mirl_conv1p_u8_", (0,), "fwd")}
+_CONV_U8 = {4: ConvU8Family(4, "mirl_conv1_u8_", (), "fwd_ex", planes_in_query=True), 1: ConvU8Family(1, "mirl_conv1p_u8_", (0,), "fwd"),
+            3: ConvU8Family(3, "mirl_conv1p3_u8_", (0,), "fwd")}
 
 
 def conv_u8_family(planes):
@@ -365,7 +369,7 @@ def conv_u8_family(planes):
 
 
 def conv_u8_supported(x, conv):
-    """Does the one-pass input layer (mirl_conv1_u8_fwd / mirl_conv1p_u8_fwd) cover this conv on this uint8 block?"""
+    """Does the one-pass input layer (mirl_conv1_u8_fwd / mirl_conv1p_u8_fwd / mirl_conv1p3_u8_fwd) cover this conv on this uint8 block?"""
     if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.uint8 and x.dim() == 4 and x.is_contiguous()
             and x.data_ptr() % 16 == 0 and conv.bias is not None and conv.weight.dtype == torch.float32
             and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1

@@ -89,7 +89,7 @@ def _make_base_vec_env(env, env_args, num_envs, device, seed=0):
         # the long-episode device-native game (acting/flappy_env.py: a single HIP kernel per vector step)
         from rltime_amd.acting.flappy_env import FlappyVecEnv
         args = dict(env_args or {})
-        unknown = set(args) - {"frame_shape", "cell", "gap", "spacing", "n_actions", "max_episode_steps", "death_reward"}
+        unknown = set(args) - {"frame_shape", "cell", "gap", "spacing", "n_actions", "max_episode_steps", "death_reward", "rgb"}
         if unknown:
             raise ValueError("flappy: unknown env_args %s" % sorted(unknown))
         if "frame_shape" in args:
@@ -105,9 +105,20 @@ def _make_base_vec_env(env, env_args, num_envs, device, seed=0):
     return SyntheticAtariVecEnv(num_envs, device=device, seed=seed, **args)
 
 
+def check_rgb_storage(config):
+    """frame_stack_dedup keeps ONE plane per transition and rebuilds the others from earlier transitions; the three planes of
+    an rgb Flappy frame are colours of one step, not history: refused before anything is built."""
+    history = ((config.get("training") or {}).get("args") or {}).get("history_mode") or {}
+    if (config.get("env") == "flappy" and (config.get("env_args") or {}).get("rgb", False)
+            and (history.get("args") or {}).get("frame_stack_dedup", False)):
+        raise ValueError("frame_stack_dedup: the planes of an rgb flappy frame are one step's colours, not a frame stack "
+                         "(env_args.rgb with history_mode.args.frame_stack_dedup)")
+
+
 def create_actors(config, device="cuda", device_acting=True, use_graph=False):
     """acting/create.py:4-27 for the local synchronous actor."""
     from rltime_amd.acting.actor import Actor
+    check_rgb_storage(config)
     acting = config.get("acting", {})
     n = acting.get("actor_envs", 1)
     env = make_vec_env(config.get("env"), config.get("env_args"), n, device)
