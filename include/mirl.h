@@ -1133,6 +1133,31 @@ int mirl_lstm_seq_status_device(const int32_t** p);
 int mirl_actor_head_ac(int32_t E, int32_t A, const float* logits, int64_t pitch, const float* values, const float* u,
                        int32_t greedy, int32_t* actions, float* action_log_probs, float* values_out, int32_t out_pitch,
                        void* stream);
+/* mirl_actor_head_ac drawing its own uniform (kernel k_actor_head_ac_rng): one Philox4x32-10 block per env,
+ * philox_4x32(rng_seed, *rng_step, e) with rng_step a device word, u = float(word 0 >> 8) * 2^-24 — the rule of
+ * mirl_actor_head_rng's uniform.  Everything after the draw is mirl_actor_head_ac's code, so feeding that entry the same
+ * uniforms gives the same bits.  The value of env e is read at values[e * value_pitch]: logits and value may be the columns
+ * of ONE product [E][A + 1].  rng_step is required (also with greedy, where nothing is drawn).  Limits and refusals as
+ * above: 1 <= A <= 64, pitch >= A, value_pitch >= 1, no null operand; a refusal writes nothing.                        */
+int mirl_actor_head_ac_rng(int32_t E, int32_t A, const float* logits, int64_t pitch, const float* values, int64_t value_pitch,
+                           uint64_t rng_seed, const uint64_t* rng_step, int32_t greedy, int32_t* actions,
+                           float* action_log_probs, float* values_out, int32_t out_pitch, void* stream);
+/* ONE launch moves a vector step from the acting step's static buffers into ring slot (*head_word + k) mod cap of the rings
+ * mirl_online_window reads: obs [E][obs_bytes], actions (int32, Discrete) / rewards / dones [E], the [log-probability |
+ * value] pair of env e at policy[e * policy_pitch + {0, 1}] into policy_ring [cap][E][2], and with state_f32 > 0 the packed
+ * recurrent state [E][state_f32] and initials [E] (state_f32 = 0: those four pointers are ignored).  head_word is a device
+ * int64 (vector steps stored so far), k a launch constant: the slot is decided on the device, so a captured graph replays
+ * correctly at every ring position.  One workgroup per env; 16-byte accesses where both ends of a row and its length allow,
+ * 4-byte words otherwise, single bytes for an odd observation length.  No atomics; nothing outside the slot is written.
+ * cap >= 1, k >= 0, policy_pitch >= 2.                                                                                */
+int mirl_online_append(int32_t E, int32_t cap, const int64_t* head_word, int32_t k, int64_t obs_bytes, const void* obs,
+                       const int32_t* actions, const float* rewards, const uint8_t* dones, const float* policy,
+                       int64_t policy_pitch, int32_t state_f32, const float* state, const float* initials, void* obs_ring,
+                       int32_t* actions_ring, float* rewards_ring, uint8_t* dones_ring, float* policy_ring, float* state_ring,
+                       float* initials_ring, void* stream);
+/* *head_word += steps by one thread, as a launch of its own: no workgroup of an append launch observes the word
+ * mid-update.  steps >= 0.                                                                                             */
+int mirl_online_advance(int64_t* head_word, int64_t steps, void* stream);
 /* The (T, B) training window of the on-policy history (rltime/history/online_history.py:81-120 over history.py:71-201,
  * fixed_target = True) from device rings of whole vector steps.  Ring slot s holds, for each of the E envs, what the
  * transition of that vector step stored: obs_ring [cap][E][obs_bytes] its next_state (uint8 frames or float32 vectors,

@@ -240,6 +240,10 @@ _SIGNATURES = {
     "mirl_actor_head": [_i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _f64, _vp, _vp, _vp, _vp, _vp, _vp],
     "mirl_actor_head_rng": [_i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _f64, _u64, _vp, _vp, _vp, _vp, _vp],
     "mirl_actor_head_ac": [_i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
+    "mirl_actor_head_ac_rng": [_i32, _i32, _vp, _i64, _vp, _i64, _u64, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
+    "mirl_online_append": [_i32, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                           _vp, _vp],
+    "mirl_online_advance": [_vp, _i64, _vp],
     "mirl_online_window": [_i32, _i32, _i32, _i32, _i32, _f64, _f64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
                            _vp, _vp, _vp, _vp, _vp],
     "mirl_ac_loss": [_i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _i32, _vp, _i64, _vp, _vp, _vp, _vp],

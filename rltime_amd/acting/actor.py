@@ -98,7 +98,10 @@ class GraphedStep:
 
 class Actor(ActingInterface):
     def __init__(self, vec_env, exploration_config=None, base_env_id=0, total_env_ids=None, device=False,
-                 use_graph=False):
+                 use_graph=False, fused_actor_critic=False):
+        """fused_actor_critic (config: acting.extra_args.fused_step): let an actor-critic policy act on the fused vector
+        step (acting/fast_step.py) where its shape is covered, instead of the generic device path."""
+        self._fused_actor_critic = bool(fused_actor_critic)
         self._vec_env = vec_env
         self._num_envs = vec_env.num_envs
         self._base_env_id = base_env_id
@@ -133,8 +136,11 @@ class Actor(ActingInterface):
         self._policy = actor_policy
         obs = self._vec_env.reset()
         self._reset_obs = obs
-        # (actor-critic policies take the generic device path and its GraphedStep, never the fused Q-learning step)
-        self._fast = False if hasattr(actor_policy, "actor_head_ac_raw") else None
+        # (actor-critic policies take the generic device path and its GraphedStep unless the actor opted in to the fused step)
+        ac = hasattr(actor_policy, "actor_head_ac_raw")
+        self._fast = False if ac and not self._fused_actor_critic else None
+        if ac and self._fused_actor_critic and self._device_mode:
+            self._use_graph = True         # the fused step is captured graphs throughout: the opt-in asks for them
         self.last_state = actor_policy.make_input_state(obs, np.array([True] * self._num_envs))
 
     def set_sink(self, history, clip_rewards=False):
@@ -332,17 +338,27 @@ class Actor(ActingInterface):
         keep_policy = False
         if sink is not None:
             if sink._h is None:
-                pf = self._action_space.n if sink._keep_policy else 0
+                # (the on-policy history keeps the [log-probability | value] pair, a replay the q-values)
+                pf = (2 if fs.ac else self._action_space.n) if sink._keep_policy else 0
                 sink.configure(fs.example, self._num_envs, self._base_env_id, policy_f32=pf)
                 if getattr(sink, "_dedup", False) and fs.trusted_stack and not getattr(sink, "_acting_priority_init", False):
                     sink.prime_stack(self._reset_obs[0] if isinstance(self._reset_obs, (tuple, list)) else self._reset_obs)
             keep_policy = bool(sink._policy_f32)
         out = None
-        if fs.can_rollout(iters, sink) and fs.rollout(iters, sink, keep_policy=keep_policy, clip=self.clip_rewards):
-            # the whole call — env steps, pre-step kernels, ingests, forwards — went out as ONE captured graph
+        # an on-policy call asks for a whole training window at once (DeviceOnlineHistory.needed_feed_count): rollouts of at
+        # most the episode tracker's rows each; everything else is one rollout or none
+        rows = self._tracker.ROWS
+        chunks = [iters] if not (fs.ac and iters > rows) else [rows] * (iters // rows) + ([iters % rows] if iters % rows else [])
+        done = 0
+        for n in chunks:
+            if not (fs.can_rollout(n, sink) and fs.rollout(n, sink, keep_policy=keep_policy, clip=self.clip_rewards)):
+                break
+            # the whole rollout — env steps, pre-step kernels, ingests, forwards — went out as ONE captured graph
             self._tracker.flush()
+            done += n
+        if done == iters:
             return IngestedSamples(iters * self._num_envs, self._tracker)
-        for _ in range(iters):
+        for _ in range(iters - done):
             clip = self.clip_rewards and sink is not None
             pre_done = False
             if fs.env_into and fs.env_pre and fs.tracker is not None:
@@ -379,6 +395,10 @@ class Actor(ActingInterface):
                     logging.getLogger().warning("fused acting step unavailable (%s); using the generic device path", e)
                     self._fast = False
             else:
+                if self._fused_actor_critic and hasattr(self._policy, "actor_head_ac_raw"):
+                    import logging
+                    logging.getLogger().warning("fused acting step unavailable (%s); using the generic device path",
+                                                "this actor-critic policy / env shape is not covered")
                 self._fast = False
         out, pending = None, None
         for it in range(iters):

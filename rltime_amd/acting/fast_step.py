@@ -33,6 +33,12 @@ ingest, input layer, network, head — are captured into a single HIP graph.  At
 (one rank of the 8-GPU job) the per-step host work (~320 us of launches against ~100 us of
 kernels) was what bounded the acting; the rollout graph leaves one plan upload and one graph
 launch per learner step.
+
+Actor-critic policies (A2C / PPO) take the same step when the actor opted in (acting.extra_args.fused_step):
+CNN -> FC, CNN -> LSTM or CNN -> LSTM -> FC under a Categorical head.  `_body` is the trunk followed by one of two
+heads; theirs is [FC ->] one product [logits | value] -> mirl_actor_head_ac_rng (the draw in the kernel), the
+[log-probability | value] block where the q-values are, and the sink is the on-policy history
+(history/online_device.py: one mirl_online_append launch per vector step, the ring slot decided on the device).
 """
 import os
 import ctypes as C
@@ -75,6 +81,8 @@ class FastActingStep:
         from rltime_amd.models.torch.modules import CNN, FC, LSTM
         model = pol.model
         layers = list(model.layers)
+        if hasattr(pol, "actor_head_ac_raw"):
+            return FastActingStep._parts_ac(pol, layers)
         if len(layers) == 3:
             cnn, lstm, fc = layers
             if not isinstance(lstm, LSTM) or not lstm.fused or lstm.lstm_cell.bias_ih is None:
@@ -101,6 +109,40 @@ class FastActingStep:
         return cnn, lstm, lin, dueling
 
     @staticmethod
+    def _parts_ac(pol, layers):
+        """The actor-critic shapes: [CNN, FC], [CNN, LSTM] (the heads directly on h) or [CNN, LSTM, FC] under a Categorical
+        head and a critic on the same features -> (cnn, lstm or None, the FC's Linear or None, False), else None."""
+        from rltime_amd.models.torch.modules import CNN, FC, LSTM
+        if pol.has_normal_head() or pol.value_model is not None or pol.why_not_on_device() is not None:
+            return None
+        kinds = tuple(type(layer) for layer in layers)
+        if kinds == (CNN, FC):
+            cnn, lstm, fc = layers[0], None, layers[1]
+        elif kinds == (CNN, LSTM):
+            cnn, lstm, fc = layers[0], layers[1], None
+        elif kinds == (CNN, LSTM, FC):
+            cnn, lstm, fc = layers
+        else:
+            return None
+        if lstm is not None and (not lstm.fused or lstm.lstm_cell.bias_ih is None):
+            return None
+        if pol.model.extra_input_layer is not None:
+            return None
+        lin = None
+        if fc is not None:
+            blocks = fc.layers
+            if not (fc.fuse_relu and len(blocks) == 1 and len(blocks[0]) == 1):
+                return None
+            lin = blocks[0][0]
+            if not (lin.weight.is_cuda and lin.weight.dtype == torch.float32 and lin.bias is not None):
+                return None
+        width = lin.out_features if lin is not None else lstm.num_units
+        logits, critic = pol.actor.logits_layer, pol.critic
+        if logits.in_features != width or critic.in_features != width or logits.bias is None or critic.bias is None:
+            return None
+        return cnn, lstm, lin, False
+
+    @staticmethod
     def supports(actor):
         """CNN (NHWC, input layer straight from uint8) -> [LSTM ->] one Linear+ReLU, plain or dueling head, IQN quantile
         layer (if any) injected before the last layer, epsilon-greedy or greedy."""
@@ -108,8 +150,9 @@ class FastActingStep:
         try:
             if not pol.is_cuda():
                 return False
-            if not hasattr(actor._action_space, "n") or hasattr(pol, "actor_head_ac_raw"):
-                return False                      # Box actions and actor-critic heads act on the generic device path
+            ac = hasattr(pol, "actor_head_ac_raw")
+            if not hasattr(actor._action_space, "n") or (ac and not getattr(actor, "_fused_actor_critic", False)):
+                return False                      # Box actions act on the generic device path; actor-critic heads unless opted in
             parts = FastActingStep._parts(pol)
             if parts is None:
                 return False
@@ -121,8 +164,8 @@ class FastActingStep:
             if (iqn and set(pre) != {len(pol.model.layers) - 1}) or (not iqn and pre):
                 return False
             expl = actor._exploration
-            if expl is not None and not hasattr(expl, "_device_exponents"):
-                return False
+            if not ac and expl is not None and not hasattr(expl, "_device_exponents"):
+                return False                      # (an actor-critic policy samples for itself: exploration configs are ignored)
             space = actor._vec_env.observation_space
             if pol.model.extra_input_layer is not None:
                 # the env writes the extras rows itself, into the step's static buffers (ExtraFeaturesVecEnv.write_extras)
@@ -148,7 +191,10 @@ class FastActingStep:
         # combine, so the advantage stream alone does not rank the actions — the full head is always evaluated
         self.c51 = hasattr(pol, "num_atoms")
         self.Z = pol.num_atoms if self.c51 else 1
-        self.need_q = bool(need_q) or self.c51
+        # an actor-critic policy (acting.extra_args.fused_step): Categorical head + critic as ONE product, the [E, 2] block
+        # [log-probability | value] where the Q-learning heads keep their q-values; always evaluated in full
+        self.ac = hasattr(pol, "actor_head_ac_raw")
+        self.need_q = bool(need_q) or self.c51 or self.ac
         self.cnn, self.lstm, self.fc, self.dueling = self._parts(pol)
         if isinstance(obs0, (tuple, list)):                       # (frames, extras): the extras rows are written below
             obs0 = obs0[0]
@@ -184,7 +230,7 @@ class FastActingStep:
         self.dones = torch.ones(E, dtype=torch.uint8, device=dev)
         self.gates = torch.empty((E, 4 * H), **f32)
         self.actions = torch.zeros(E, dtype=torch.int32, device=dev)
-        self.qvalues = torch.zeros((E, A), **f32)
+        self.qvalues = torch.zeros((E, 2 if self.ac else A), **f32)
         self.eps = torch.zeros((), dtype=torch.float64, device=dev)
         self.rng_step = torch.zeros(1, dtype=torch.int64, device=dev)
         self.step_no = 0
@@ -194,17 +240,27 @@ class FastActingStep:
         if self.lstm is not None:
             self.bias_sum = torch.empty(4 * H, **f32)
             self.wcat = torch.empty((4 * H, K), **f32) if not X else torch.zeros((4 * H, K), **f32)   # (padding columns stay 0)
-        h1, hv = self.fc.out_features, (pol.value_hidden_layer.out_features if self.dueling else 0)
-        self.h1 = h1
-        self.fc_w = torch.empty((h1 + hv, self.fc.in_features), **f32)
-        self.fc_b = torch.empty(h1 + hv, **f32)
-        # advantage and value outputs as ONE GEMM over the joint hidden activation: block-diagonal weights
-        self.na, self.nq = pol.out_layer.out_features, (pol.value_layer.out_features if self.dueling else 0)
-        assert self.na == A * self.Z and self.nq == (self.Z if self.dueling else 0)
-        self.out_w = torch.zeros((self.na + self.nq, h1 + hv), **f32)
-        self.out_b = torch.zeros(self.na + self.nq, **f32)
-        self.adv_w = torch.zeros((self.na, h1), **f32)           # advantage stream alone (need_q=False)
-        self.freq = (pol.embedding_range * np.pi).contiguous() if self.iqn else None
+        if self.ac:
+            # logits and value as ONE (A + 1)-column product over the last layer's output (the FC's, or h itself)
+            h1 = self.h1 = self.fc.out_features if self.fc is not None else 0
+            hv, self.na, self.nq, self.freq = 0, A, 0, None
+            if self.fc is not None:
+                self.fc_w = torch.empty((h1, self.fc.in_features), **f32)
+                self.fc_b = torch.empty(h1, **f32)
+            self.ac_w = torch.empty((A + 1, h1 or W), **f32)
+            self.ac_b = torch.empty(A + 1, **f32)
+        else:
+            h1, hv = self.fc.out_features, (pol.value_hidden_layer.out_features if self.dueling else 0)
+            self.h1 = h1
+            self.fc_w = torch.empty((h1 + hv, self.fc.in_features), **f32)
+            self.fc_b = torch.empty(h1 + hv, **f32)
+            # advantage and value outputs as ONE GEMM over the joint hidden activation: block-diagonal weights
+            self.na, self.nq = pol.out_layer.out_features, (pol.value_layer.out_features if self.dueling else 0)
+            assert self.na == A * self.Z and self.nq == (self.Z if self.dueling else 0)
+            self.out_w = torch.zeros((self.na + self.nq, h1 + hv), **f32)
+            self.out_b = torch.zeros(self.na + self.nq, **f32)
+            self.adv_w = torch.zeros((self.na, h1), **f32)           # advantage stream alone (need_q=False)
+            self.freq = (pol.embedding_range * np.pi).contiguous() if self.iqn else None
         # the network's own kernels (csrc/actnet.hip), piece by piece: each one wherever the library's *_supported query
         # takes the shape and the size gate below holds — the conv layers and the quantile product at any batch, the LSTM
         # step where mirl_act_lstm_supported says so, the head's hidden layers up to 2048 quantile rows (where they
@@ -231,7 +287,8 @@ class FastActingStep:
         self.f_lstm = self.lstm is not None and bool(lib.mirl_act_lstm_supported(E, H, K))
         D = int(self.freq.shape[0]) if self.iqn else 0
         # (the output layer in the hidden layer's epilogue selects on scalar Q values: not for C51's distributions)
-        self.f_head = not self.c51 and E * self.N <= 2048 and self.fc.in_features == W and self.dueling \
+        # (nor for the actor-critic head, which samples from the logits)
+        self.f_head = not self.c51 and not self.ac and E * self.N <= 2048 and self.fc.in_features == W and self.dueling \
             and bool(lib.mirl_act_head_supported(E, self.N, W, D, h1 + hv, self.na + self.nq))
         # the quantile product as one launch at any batch (cos features + embedding product + ReLU + feature multiply)
         self.f_embed = self.iqn and W % 16 == 0 and D % 16 == 0 and 0 < D <= 64 and E * self.N <= (1 << 24)
@@ -245,7 +302,7 @@ class FastActingStep:
             check(lib.mirl_act_lstm_workspace_bytes(E, H, K, C.byref(need)))
             self.lstm_ws = torch.zeros((need.value + 3) // 4, dtype=torch.int32, device=dev)   # zero once: the kernel restores it
         self.in_kernel_taus = self.iqn and getattr(pol, "tau_source", None) is None
-        expl = actor._exploration
+        expl = actor._exploration if not self.ac else None     # (actor-critic: exploration configs are ignored, as in the reference)
         self.expo = expl._device_exponents(actor._env_ids, dev) if expl is not None else None
         self.eps_min = float(expl.eps_min) if expl is not None else 0.0
         self.last_obs = obs0
@@ -274,7 +331,12 @@ class FastActingStep:
         self._pre(torch.zeros(E, **f32), torch.ones(E, dtype=torch.uint8, device=dev), track=False)
         if X:
             env.reset_extras(self.extra, self.xh, K, F)           # the reset rows (the same launch with dones all 1)
-        if self.lstm is not None:
+        if self.ac:
+            self.example = {"x": obs0[0].cpu().numpy()}
+            for i, layer in enumerate(pol.model.layers):
+                self.example["layer%d_state" % i] = {} if layer is not self.lstm else \
+                    {"hx": np.zeros(H, np.float32), "cx": np.zeros(H, np.float32), "initials": np.float32(1.0)}
+        elif self.lstm is not None:
             x0 = obs0[0].cpu().numpy()
             self.example = {"x": (x0, np.zeros(X, np.float32)) if X else x0, "layer0_state": {},
                             "layer1_state": {"hx": np.zeros(H, np.float32), "cx": np.zeros(H, np.float32), "initials": np.float32(1.0)},
@@ -303,6 +365,13 @@ class FastActingStep:
                 if X:
                     self.wcat[:, F:F + X].copy_(cell.weight_ih[:, F:])
                 self.wcat[:, F + self.Xp:].copy_(cell.weight_hh)
+            if self.ac:
+                dst, src = [self.ac_w[:self.A], self.ac_w[self.A:], self.ac_b[:self.A], self.ac_b[self.A:]], \
+                    [pol.actor.logits_layer.weight, pol.critic.weight, pol.actor.logits_layer.bias, pol.critic.bias]
+                if self.fc is not None:
+                    dst, src = dst + [self.fc_w, self.fc_b], src + [self.fc.weight, self.fc.bias]
+                torch._foreach_copy_(dst, [t.detach() for t in src])
+                return
             na = self.na
             # one multi-tensor copy for the head's buffers instead of a launch each (the T = 1 configs refresh every learner step)
             dst = [self.fc_w[:self.h1], self.fc_b[:self.h1], self.out_w[:na, :self.h1], self.adv_w, self.out_b[:na]]
@@ -368,7 +437,15 @@ class FastActingStep:
 
     def _body(self):
         """conv 2.. -> LSTM step -> head; reads y1 / xh tail / c_in, writes h, c, actions, qvalues."""
-        pol, E, H, F, N = self.pol, self.E, self.H, self.F, self.N
+        feat = self._trunk()
+        if self.ac:
+            self._head_ac(feat)
+        else:
+            self._head_q(feat)
+
+    def _trunk(self):
+        """conv 2.. and the LSTM step -> the head's (E, W) input rows."""
+        E, H = self.E, self.H
         if self.f_conv:
             c2, c3 = self.cnn.layers[1], self.cnn.layers[2]
             h1o, w1o, h2o, w2o, h3o, w3o = self.conv_dims
@@ -389,10 +466,25 @@ class FastActingStep:
             torch.addmm(self.bias_sum, self.xh, self.wcat.t(), out=self.gates)
             check(lib.mirl_lstm_cell_fwd(E, H, ptr(self.gates), ptr(self.c_in), None, None, None, ptr(self.h), ptr(self.c), stream()),
                   "mirl_lstm_cell_fwd")
+        return self.h if self.lstm is not None else self.xh       # (E, W) rows
+
+    def _head_ac(self, feat):
+        """The actor-critic head: [FC ->] ONE product [logits | value] -> sampling with the draw in the kernel
+        (csrc/actor_critic.hip k_actor_head_ac_rng), keyed like every other in-kernel draw of the step."""
+        E, A = self.E, self.A
+        if self.fc is not None:
+            feat = torch._addmm_activation(self.fc_b, feat, self.fc_w.t(), use_gelu=False)
+        outs = torch.addmm(self.ac_b, feat, self.ac_w.t())        # (E, A + 1)
+        check(lib.mirl_actor_head_ac_rng(E, A, ptr(outs), A + 1, C.c_void_p(outs.data_ptr() + 4 * A), A + 1, self.rng_seed,
+                                         ptr(self.rng_step), 0, ptr(self.actions), ptr(self.qvalues),
+                                         C.c_void_p(self.qvalues.data_ptr() + 4), 2, stream()), "mirl_actor_head_ac_rng")
+
+    def _head_q(self, feat):
+        """The Q-learning heads: [quantile product ->] hidden layers -> outputs -> selection; writes actions, qvalues."""
+        pol, E, N = self.pol, self.E, self.N
         greedy = self.expo is None
         eps_p, expo_p = (None, None) if greedy else (ptr(self.eps), ptr(self.expo))
-        feat = self.h if self.lstm is not None else self.xh       # (E, W) rows
-        H = self.W                                                # from here on: the head's input width
+        H = self.W                                                # the head's input width
         if self.f_embed:
             # quantile fractions -> cos features -> embedding product + ReLU -> x features: one launch at any batch
             taus = None
@@ -565,6 +657,8 @@ class FastActingStep:
                                 initials=self.initials if rec else None, policy=self.qvalues if keep_policy else None)
             self._conv1(obs, packed=True)
             self._body()
+        if hasattr(sink, "finish_planned"):
+            sink.finish_planned(iters)           # (the on-policy history: its device head word moves past the rollout)
 
     def rollout(self, iters, sink, keep_policy=False, clip=False):
         """`iters` vector steps after reselect(): the first call of a shape captures them into ONE HIP graph, every call
@@ -574,8 +668,6 @@ class FastActingStep:
         parity = env.clock_parity() if hasattr(env, "clock_parity") else 0
         # a captured env step reads a fixed clock word; the sink is keyed by its replay HANDLE (the Dev struct and plan
         # buffer baked into the graph belong to it — id() of a destroyed sink can be recycled)
-        key = (iters, bool(keep_policy), bool(clip), self._sink_key(sink), parity)
-        state = self._rollouts.setdefault(key, [0, None])
         from rltime_amd._lib import MirlError, MIRL_ERR_ARG
         try:
             sink.plan_ingest(iters, self.E)
@@ -589,6 +681,9 @@ class FastActingStep:
             logging.getLogger().warning("rollout plan refused (%s); acting per step", e)
             self.rollout_graphs = False
             return False
+        # (keyed AFTER the plan: a sink that reallocates its rings while planning has a new handle by now)
+        key = (iters, bool(keep_policy), bool(clip), self._sink_key(sink), parity)
+        state = self._rollouts.setdefault(key, [0, None])
         self.tracker.begin_rollout(iters)
         state[0] += 1
         # capture at the FIRST call of a shape: every kernel of the body has run before (the single-step graph's warm-ups,

@@ -1,10 +1,12 @@
 // actor_critic.hip — the actor-critic (A2C / PPO) part of the device path: the sampling head of a vector step, the
-// on-policy rollout window with its lambda-returns, and the loss with its gradients (include/mirl.h has the contracts).
+// on-policy rollout window with its lambda-returns, the append that fills the window's rings from the fused acting step, and
+// the loss with its gradients (include/mirl.h has the contracts).
 // Each exists for a Discrete action space (Categorical head, one int32 per action) and for a Box one (Normal head, up to 16
 // float32 components per action); what does not depend on the distribution is stated once and shared.
 // All are latency-sized: a few thousand rows of at most 64 actions.  Plain C++, float64 inside, one rounding to
 // float32 per output; no float atomics, every sum in a fixed order, so a rerun repeats the first run bit for bit.
 #include "common.hpp"
+#include "philox.hpp"
 
 namespace mirl {
 
@@ -32,18 +34,14 @@ __device__ inline float row_log_prob(const float* __restrict__ z, int a, const R
 }
 
 // ---- 1. the sampling head ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_actor_head_ac(int E, int A, const float* __restrict__ logits, long pitch,
-                                                      const float* __restrict__ values, const float* __restrict__ u, int greedy,
-                                                      int* __restrict__ actions, float* __restrict__ logp, float* __restrict__ values_out,
-                                                      int out_pitch) {
-  const int e = blockIdx.x * 64 + threadIdx.x;
-  if (e >= E) return;
-  const float* z = logits + (long)e * pitch;
+// Everything after the uniform, stated once for both kernels below: softmax pieces, inverse CDF (or the first maximum),
+// log-probability of the chosen action.
+__device__ inline int ac_head_row(const float* __restrict__ z, int A, float u, int greedy, float* __restrict__ logp) {
   const RowSoftmax r = row_softmax(z, A);
   int a = r.first;
   if (!greedy) {
     // inverse CDF without a division: the smallest a with u S < sum_{j <= a} e_j; the partial sums are formed exactly as S was
-    const double want = (double)u[e] * r.S;
+    const double want = (double)u * r.S;
     double cum = 0.0;
     a = A - 1;
     for (int j = 0; j < A; ++j) {
@@ -51,9 +49,40 @@ __global__ __launch_bounds__(64) void k_actor_head_ac(int E, int A, const float*
       if (want < cum) { a = j; break; }
     }
   }
-  actions[e] = a;
-  logp[(long)e * out_pitch] = row_log_prob(z, a, r, log(r.S));
+  *logp = row_log_prob(z, a, r, log(r.S));
+  return a;
+}
+
+__global__ __launch_bounds__(64) void k_actor_head_ac(int E, int A, const float* __restrict__ logits, long pitch,
+                                                      const float* __restrict__ values, const float* __restrict__ u, int greedy,
+                                                      int* __restrict__ actions, float* __restrict__ logp, float* __restrict__ values_out,
+                                                      int out_pitch) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= E) return;
+  float lp;
+  actions[e] = ac_head_row(logits + (long)e * pitch, A, greedy ? 0.f : u[e], greedy, &lp);
+  logp[(long)e * out_pitch] = lp;
   values_out[(long)e * out_pitch] = values[e];
+}
+
+// The same head drawing its own uniform: one Philox4x32-10 block per (step, env), the 24-bit uniform of k_actor_head
+// (csrc/acting.hip).  The value is read with a pitch of its own: logits and value may be columns of one [E][A + 1] product.
+__global__ __launch_bounds__(64) void k_actor_head_ac_rng(int E, int A, const float* __restrict__ logits, long pitch,
+                                                          const float* __restrict__ values, long value_pitch, uint64_t rng_seed,
+                                                          const uint64_t* __restrict__ rng_step, int greedy, int* __restrict__ actions,
+                                                          float* __restrict__ logp, float* __restrict__ values_out, int out_pitch) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= E) return;
+  float u = 0.f;
+  if (!greedy) {
+    uint32_t r[4];
+    philox_4x32(rng_seed, *rng_step, (uint32_t)e, r);
+    u = (float)(r[0] >> 8) * (1.0f / 16777216.0f);
+  }
+  float lp;
+  actions[e] = ac_head_row(logits + (long)e * pitch, A, u, greedy, &lp);
+  logp[(long)e * out_pitch] = lp;
+  values_out[(long)e * out_pitch] = values[(long)e * value_pitch];
 }
 
 // ---- 1b. the Normal (continuous) head: independent Gaussians over a Box action, state-independent log-std ----------------
@@ -177,6 +206,43 @@ __global__ __launch_bounds__(256) void k_online_window(WindowArgs a) {
       a.target_initials[out] = a.initials_ring[t_row];
     }
   }
+}
+
+// ---- 2b. appending one vector step to the rings the window reads ---------------------------------------------------------
+// One workgroup per env.  The slot is (*head_word + k) mod cap: the word lives on the device, so a captured launch lands in
+// the right slot at every ring position.  Nothing outside the slot is written, no atomics.
+struct AppendArgs {
+  int E, cap, k;
+  const long long* head_word;
+  long obs_bytes;
+  const unsigned char* obs; const int* actions; const float* rewards; const unsigned char* dones;
+  const float* policy; long policy_pitch;
+  int S; const float* state; const float* initials;
+  unsigned char* obs_ring; int* actions_ring; float* rewards_ring; unsigned char* dones_ring; float* policy_ring;
+  float* state_ring; float* initials_ring;
+  int obs_width, state_width;
+};
+
+__global__ __launch_bounds__(256) void k_online_append(AppendArgs a) {
+  const int e = blockIdx.x;
+  long long slot = (*a.head_word + (long long)a.k) % (long long)a.cap;
+  if (slot < 0) slot += a.cap;
+  const long row = (long)slot * a.E + e;
+  copy_row(a.obs_ring + row * a.obs_bytes, a.obs + (long)e * a.obs_bytes, a.obs_bytes, a.obs_width);
+  if (a.S) copy_row((unsigned char*)(a.state_ring + row * a.S), (const unsigned char*)(a.state + (long)e * a.S), (long)a.S * 4, a.state_width);
+  if (threadIdx.x == 0) {
+    a.actions_ring[row] = a.actions[e];
+    a.rewards_ring[row] = a.rewards[e];
+    a.dones_ring[row] = a.dones[e];
+    a.policy_ring[2 * row] = a.policy[(long)e * a.policy_pitch];
+    a.policy_ring[2 * row + 1] = a.policy[(long)e * a.policy_pitch + 1];
+    if (a.S) a.initials_ring[row] = a.initials[e];
+  }
+}
+
+// a launch of its own: no workgroup of an append launch can see the word move
+__global__ void k_online_advance(long long* head_word, long long steps) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *head_word += steps;
 }
 
 // ---- 3. the loss ---------------------------------------------------------------------------------------------------
@@ -384,6 +450,62 @@ extern "C" int mirl_actor_head_ac(int32_t E, int32_t A, const float* logits, int
   mirl::ProfScope ps("k_actor_head_ac", (double)E * (A + 6) * 4.0, (hipStream_t)stream);
   hipLaunchKernelGGL(mirl::k_actor_head_ac, dim3((E + 63) / 64), dim3(64), 0, (hipStream_t)stream, (int)E, (int)A, logits, (long)pitch, values, u,
                      (int)greedy, actions, action_log_probs, values_out, (int)out_pitch);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
+extern "C" int mirl_actor_head_ac_rng(int32_t E, int32_t A, const float* logits, int64_t pitch, const float* values, int64_t value_pitch,
+                                      uint64_t rng_seed, const uint64_t* rng_step, int32_t greedy, int32_t* actions,
+                                      float* action_log_probs, float* values_out, int32_t out_pitch, void* stream) {
+  if (E < 1 || E > (1 << 24) || A < 1 || A > 64 || pitch < A || value_pitch < 1 || !logits || !values || (greedy != 0 && greedy != 1) ||
+      !rng_step || !actions || !action_log_probs || !values_out || out_pitch < 1)
+    return mirl::fail(MIRL_ERR_ARG, "bad actor_head_ac_rng arguments (1 <= E <= 2^24, 1 <= A <= 64, pitch >= A, value_pitch >= 1, "
+                                    "greedy 0 | 1, out_pitch >= 1, no null operands)");
+  mirl::ProfScope ps("k_actor_head_ac_rng", (double)E * (A + 5) * 4.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_actor_head_ac_rng, dim3((E + 63) / 64), dim3(64), 0, (hipStream_t)stream, (int)E, (int)A, logits, (long)pitch,
+                     values, (long)value_pitch, rng_seed, rng_step, (int)greedy, actions, action_log_probs, values_out, (int)out_pitch);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
+// the widest access both ends of a row copy allow: 16 bytes, 4 bytes, else single bytes
+static int row_width(int64_t bytes, const void* a, const void* b) {
+  if (bytes % 16 == 0 && mirl::aligned16(a, b)) return 16;
+  if (bytes % 4 == 0 && (uintptr_t)a % 4 == 0 && (uintptr_t)b % 4 == 0) return 4;
+  return 1;
+}
+
+extern "C" int mirl_online_append(int32_t E, int32_t cap, const int64_t* head_word, int32_t k, int64_t obs_bytes, const void* obs,
+                                  const int32_t* actions, const float* rewards, const uint8_t* dones, const float* policy,
+                                  int64_t policy_pitch, int32_t state_f32, const float* state, const float* initials, void* obs_ring,
+                                  int32_t* actions_ring, float* rewards_ring, uint8_t* dones_ring, float* policy_ring,
+                                  float* state_ring, float* initials_ring, void* stream) {
+  if (E < 1 || E > (1 << 24) || cap < 1 || k < 0 || obs_bytes < 1 || policy_pitch < 2 || state_f32 < 0 || state_f32 > (1 << 20) ||
+      (double)cap * (double)E * (double)obs_bytes >= 9.0e18 || !head_word || !obs || !actions || !rewards || !dones || !policy ||
+      !obs_ring || !actions_ring || !rewards_ring || !dones_ring || !policy_ring)
+    return mirl::fail(MIRL_ERR_ARG, "bad online_append arguments (1 <= E <= 2^24, cap >= 1, k >= 0, obs_bytes >= 1, policy_pitch >= 2, "
+                                    "0 <= state_f32 <= 2^20, no null operands)");
+  if (state_f32 && (!state || !initials || !state_ring || !initials_ring || (uintptr_t)state % 4 || (uintptr_t)state_ring % 4))
+    return mirl::fail(MIRL_ERR_ARG, "bad online_append arguments (state_f32 > 0 needs state, initials and their rings, float32 blocks "
+                                    "on 4-byte boundaries)");
+  mirl::AppendArgs a;
+  a.E = E; a.cap = cap; a.k = k; a.head_word = (const long long*)head_word; a.obs_bytes = obs_bytes;
+  a.obs = (const unsigned char*)obs; a.actions = actions; a.rewards = rewards; a.dones = dones; a.policy = policy;
+  a.policy_pitch = policy_pitch; a.S = state_f32; a.state = state; a.initials = initials;
+  a.obs_ring = (unsigned char*)obs_ring; a.actions_ring = actions_ring; a.rewards_ring = rewards_ring; a.dones_ring = dones_ring;
+  a.policy_ring = policy_ring; a.state_ring = state_ring; a.initials_ring = initials_ring;
+  a.obs_width = row_width(obs_bytes, obs, obs_ring);
+  a.state_width = state_f32 ? row_width((int64_t)state_f32 * 4, state, state_ring) : 4;
+  mirl::ProfScope ps("k_online_append", (double)E * (2.0 * (double)obs_bytes + 8.0 * state_f32 + 40.0), (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_online_append, dim3((unsigned)E), dim3(256), 0, (hipStream_t)stream, a);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
+extern "C" int mirl_online_advance(int64_t* head_word, int64_t steps, void* stream) {
+  if (!head_word || steps < 0) return mirl::fail(MIRL_ERR_ARG, "bad online_advance arguments (head_word not null, steps >= 0)");
+  mirl::ProfScope ps("k_online_advance", 16.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_online_advance, dim3(1), dim3(1), 0, (hipStream_t)stream, (long long*)head_word, (long long)steps);
   MIRL_LAUNCH_CHECK();
   return MIRL_OK;
 }

@@ -6,6 +6,10 @@
   window    one DeviceOnlineHistory.get_train_data at T = 128, B = 16 on (4, 84, 84) uint8 frames, and the same with a
             recurrent state of S = 1024 float32 words (hx, cx of an LSTM 512) and the initials flag moved beside every row
   acting    one vector step of the device actor at 16 envs (catch_ppo.json's network, generic device path)
+  acting_sides   the same vector step, fed into the rollout window, four ways in ONE call, alternating, `--repeats` windows of
+            2 x 64 steps each: the generic device path eager and graphed (Actor.use_graph), the fused step per step
+            (acting.extra_args.fused_step with MIRL_ROLLOUT_GRAPH=0) and the fused rollout graph, 64 steps per launch — for
+            catch_ppo.json's network and for catch_ppo_lstm.json's
 
     python tools/actor_critic_probe.py [--iters 200] [--repeats 5]      -> one JSON line
 """
@@ -225,16 +229,75 @@ def acting_time(iters):
     return {"envs": E, "vector_step_us": round(us, 1)}
 
 
+def acting_sides(config, repeats, steps=64):
+    """Microseconds per vector step, get_samples + History.update, host clock around synchronised windows."""
+    import copy
+    from rltime_amd.general.config import load_config
+    from rltime_amd.history.online_device import DeviceOnlineHistory
+    from rltime_amd.policies.actor_critic import ActorCriticPolicy
+    from rltime_amd.train import create_actors
+
+    def discount(n, r, po):
+        return 0.0
+    discount.gamma, discount.lam = 0.99, 0.95
+    base = load_config(config)
+    sides, made = {}, []
+    try:
+        for name, fused, graph, env_graph in (("generic_eager", False, False, "1"), ("generic_graphed", False, True, "1"),
+                                              ("fused_per_step", True, True, "0"), ("fused_rollout", True, True, "1")):
+            cfg = copy.deepcopy(base)
+            if fused:
+                cfg["acting"]["extra_args"] = {"fused_step": True}
+            torch.manual_seed(0)
+            actors = create_actors(cfg, "cuda", use_graph=graph)
+            made.append(actors)
+            obs_space, act_space = actors.get_spaces()
+            policy = ActorCriticPolicy.create(model_config=cfg["model"], observation_space=obs_space, action_space=act_space, cuda=True)
+            actors.set_actor_policy(policy)
+            hist = DeviceOnlineHistory(nstep_target=128, nstep_train=128, max_delayed_steps=256, discount_function=discount)
+            if fused:
+                actors.set_sink(hist, clip_rewards=True)
+            E = actors.get_env_count()
+
+            def call(actors=actors, hist=hist, E=E):
+                hist.update(actors.get_samples(E * steps))
+            keep = os.environ.get("MIRL_ROLLOUT_GRAPH")
+            os.environ["MIRL_ROLLOUT_GRAPH"] = env_graph          # read when the fused step is built: the first call
+            try:
+                for _ in range(3):
+                    call()
+            finally:
+                os.environ.pop("MIRL_ROLLOUT_GRAPH") if keep is None else os.environ.__setitem__("MIRL_ROLLOUT_GRAPH", keep)
+            assert bool(actors._fast) == fused and (not fused or actors._fast.rollout_graphs == (env_graph == "1"))
+            sides[name] = (call, [])
+        for _ in range(repeats):                                  # alternating, same process
+            for name, (call, times) in sides.items():
+                times.append(_timed(call, 2) / steps)
+    finally:
+        for actors in made:
+            actors.close()
+    out = {"config": config, "envs": E, "steps_per_call": steps}
+    for name, (_, times) in sides.items():
+        out[name + "_us"] = [round(t, 1) for t in times]
+        out[name + "_us_median"] = round(sorted(times)[len(times) // 2], 1)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--only", default=None, help="acting_sides: that row alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("actor_critic_probe: no GPU visible; timings are taken on the device only")
+    if a.only == "acting_sides":
+        print(json.dumps({"acting_sides": [acting_sides(c, a.repeats) for c in ("catch_ppo.json", "catch_ppo_lstm.json")]}))
+        return
     out = {"loss": [loss_times(512, A, a.iters, a.repeats) for A in (6, 18)], "window": window_time(max(8, a.iters // 10)),
            "window_recurrent": window_time(max(8, a.iters // 10), state_f32=1024),
            "acting": acting_time(a.iters),
+           "acting_sides": [acting_sides(c, a.repeats) for c in ("catch_ppo.json", "catch_ppo_lstm.json")],
            "normal_loss": [normal_loss_times(M, 1, a.iters, a.repeats) for M in (128, 512)],
            "normal_head": [normal_head_time(E, 1, a.iters, a.repeats) for E in (128, 512)],
            "mountaincar_step": [mountaincar_step_time(E, a.iters, a.repeats) for E in (128, 512)]}
