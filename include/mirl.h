@@ -1248,6 +1248,29 @@ int mirl_ac_loss_normal(int64_t M, int32_t D, const float* mean, int64_t pitch, 
                         const float* actions, const float* targets, const float* acting_values, const float* old_log_probs,
                         double vf_coef, double entropy_factor, double clip_value, int32_t adv_norm, float* dmean, int64_t dpitch,
                         float* dlogstd, float* dvalues, float* log_probs, float* stats, void* stream);
+/* The whole acting network of an MLP Q-learning policy for one vector step, ONE launch of E workgroups (csrc/act_mlp.hip;
+ * policies/torch/dqn.py:50-87,132-148, iqn.py:67-131, exploration/epsilon_greedy.py:74-100): obs float32 [E][O] through L
+ * Linear + ReLU layers (`widths`, a HOST array of L ints) -> the W-wide feature row (L = 0: the observation); with D > 0
+ * the quantile product x[n] = relu(cos(freq tau[n]) . wq^T + bq) * f over N rows, tau = taus[e N + n] or the Philox draw
+ * of mirl_cos_embed_rng / mirl_act_embed on (seed, *rng_step, e N + n), written to taus_out [E N] when given; hid =
+ * relu(x . wfc^T + bfc), HID = [last FC (H1 units) | dueling value-hidden]; out = hid . wout^T + bout, NO = A (+ 1: the
+ * value); q[e][a] = mean_n (V + A_a - mean_a A) or mean_n A_a -> qvalues [E][A]; first maximum; epsilon-greedy as
+ * mirl_actor_head_rng (eps NULL: greedy).  need_q = 0 skips the value stream (hidden units >= H1, output column A):
+ * qvalues then holds the advantage means, which rank the actions alike.  Every weight is handed over TRANSPOSED, [K][J]
+ * row-major: lw0T [O][widths[0]], lw1T [widths[0]][widths[1]], wqT [D][W], fcT [W][HID], outT [HID][NO] (block-diagonal
+ * under a dueling head).  float32, k ascending, no atomics: a rerun repeats to the bit.  Limits (mirl_act_mlp_supported,
+ * host-only): 1 <= O <= 64, L <= 2, widths <= 256, 1 <= N <= 64, D <= 64 with D % 4 == 0 (D = 0: N = 1), HID <= 512,
+ * A <= 32, NO in {A, A + 1}, E >= 1.  mirl_act_mlp_lds_bytes: the dynamic LDS of the launch (<= 64 KB).              */
+int mirl_act_mlp_supported(int32_t E, int32_t O, int32_t L, const int32_t* widths, int32_t N, int32_t D, int32_t HID,
+                           int32_t NO, int32_t A);
+int mirl_act_mlp_lds_bytes(int32_t O, int32_t L, const int32_t* widths, int32_t N, int32_t D, int32_t HID, int32_t NO,
+                           int32_t A, int64_t* bytes);
+int mirl_act_mlp_fwd(int32_t E, int32_t O, int32_t L, const int32_t* widths, int32_t N, int32_t D, int32_t HID, int32_t NO,
+                     int32_t A, int32_t H1, int32_t need_q, const float* obs, const float* lw0T, const float* lb0,
+                     const float* lw1T, const float* lb1, const float* freq, const float* taus, const float* wqT,
+                     const float* bq, const float* fcT, const float* fcb, const float* outT, const float* outb,
+                     const double* eps, const double* expo, double eps_min, uint64_t seed, const uint64_t* rng_step,
+                     int32_t* actions, float* qvalues, float* taus_out, void* stream);
 
 #ifdef __cplusplus
 }

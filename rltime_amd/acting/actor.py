@@ -98,10 +98,14 @@ class GraphedStep:
 
 class Actor(ActingInterface):
     def __init__(self, vec_env, exploration_config=None, base_env_id=0, total_env_ids=None, device=False,
-                 use_graph=False, fused_actor_critic=False):
+                 use_graph=False, fused_mlp=False, fused_actor_critic=False):
         """fused_actor_critic (config: acting.extra_args.fused_step): let an actor-critic policy act on the fused vector
-        step (acting/fast_step.py) where its shape is covered, instead of the generic device path."""
+        step (acting/fast_step.py) where its shape is covered, instead of the generic device path.
+        fused_mlp (the same config key): let an MLP DQN / IQN policy on float32 vector observations act on the fused MLP
+        step (acting/fast_mlp_step.py) where FastActingStep declines it."""
         self._fused_actor_critic = bool(fused_actor_critic)
+        self._fused_mlp = bool(fused_mlp)
+        self._fast_cls = None          # the fused step's class once a supports() query chose one (None: FastActingStep)
         self._vec_env = vec_env
         self._num_envs = vec_env.num_envs
         self._base_env_id = base_env_id
@@ -141,6 +145,9 @@ class Actor(ActingInterface):
         self._fast = False if ac and not self._fused_actor_critic else None
         if ac and self._fused_actor_critic and self._device_mode:
             self._use_graph = True         # the fused step is captured graphs throughout: the opt-in asks for them
+        self._fast_cls = None
+        if self._fused_mlp and self._device_mode and not ac and not self._use_graph and self._mlp_step_supported():
+            self._use_graph = True         # (likewise for an MLP policy the fused MLP step covers)
         self.last_state = actor_policy.make_input_state(obs, np.array([True] * self._num_envs))
 
     def set_sink(self, history, clip_rewards=False):
@@ -313,7 +320,7 @@ class Actor(ActingInterface):
         if self._fast is not None:
             self._fast.set_need_q(need_q)
         if self._fast is None:
-            self._fast = FastActingStep(self, self._reset_obs, need_q=need_q)
+            self._fast = (self._fast_cls or FastActingStep)(self, self._reset_obs, need_q=need_q)
             if self._tracker is None:
                 from .episode_tracker import EpisodeTracker
                 self._tracker = EpisodeTracker(self._num_envs, self._action_space.n, self._policy.device())
@@ -385,7 +392,7 @@ class Actor(ActingInterface):
     def _device_steps(self, iters):
         if self._use_graph and getattr(self, "fast_step", True) and self._fast is not False:
             from .fast_step import FastActingStep
-            if self._fast is not None or FastActingStep.supports(self):
+            if self._fast is not None or FastActingStep.supports(self) or (self._fused_mlp and self._mlp_step_supported()):
                 try:
                     return self._fast_steps(iters)
                 except Exception as e:                    # e.g. graph capture refused: the generic path still works
@@ -399,6 +406,9 @@ class Actor(ActingInterface):
                     import logging
                     logging.getLogger().warning("fused acting step unavailable (%s); using the generic device path",
                                                 "this actor-critic policy / env shape is not covered")
+                elif self._fused_mlp and not hasattr(self._policy, "actor_head_ac_raw"):
+                    import logging
+                    logging.getLogger().warning("fused acting step unavailable (%s); using the generic device path", self._mlp_why_not)
                 self._fast = False
         out, pending = None, None
         for it in range(iters):
@@ -460,6 +470,14 @@ class Actor(ActingInterface):
             self._tracker.flush()
             out.episode_tracker = self._tracker
         return out
+
+    def _mlp_step_supported(self):
+        """The opt-in's query (acting/fast_mlp_step.py), asked after FastActingStep.supports declined."""
+        from .fast_mlp_step import FastMlpStep
+        self._mlp_why_not = FastMlpStep.why_not(self)
+        if self._mlp_why_not is None:
+            self._fast_cls = FastMlpStep
+        return self._mlp_why_not is None
 
     def _eps(self):
         return self._exploration._get_eps(self._progress) if self._exploration is not None else 0.0

@@ -98,7 +98,9 @@ class _ConstantEpsilon(EpsilonGreedyExplorationManager):
 
 
 class Evaluator:
-    def __init__(self, policy, env, episode_count, eps=0.0, seed=0, steps_per_launch=32):
+    def __init__(self, policy, env, episode_count, eps=0.0, seed=0, steps_per_launch=32, fused_mlp=False):
+        """fused_mlp (config: acting.extra_args.fused_step): evaluate an MLP DQN / IQN policy on float32 vector observations
+        (the device CartPole) on the fused MLP step (acting/fast_mlp_step.py); without it such a policy is refused."""
         if not hasattr(getattr(env, "action_space", None), "n"):
             raise ValueError("Evaluator: the env's action space %r is not Discrete; the evaluation is greedy (arg-max) and the "
                              "reference's has no greedy mode for a Box space either" % (getattr(env, "action_space", None),))
@@ -107,7 +109,8 @@ class Evaluator:
         if not hasattr(env, "step_device") or torch.device(getattr(env, "device", "cpu")).type != "cuda":
             raise ValueError("Evaluator: the env steps on the host; evaluation needs an env that steps on the device "
                              "('catch', 'synthetic-atari')")
-        if str(getattr(getattr(env, "observation_space", None), "dtype", "")) == "float32":
+        float_obs = str(getattr(getattr(env, "observation_space", None), "dtype", "")) == "float32"
+        if float_obs and not fused_mlp:
             raise ValueError("Evaluator: float32 vector observations (the device CartPole's MLP policies) are not covered: the "
                              "evaluation rides on the fused acting step, which takes CNN policies on uint8 frames only")
         if not 1 <= int(steps_per_launch) <= EpisodeTracker.ROWS:
@@ -117,7 +120,14 @@ class Evaluator:
         self.eps, self.seed, self.K = float(eps), int(seed), int(steps_per_launch)
         self.device = policy.device()
         self.sink = EvalSink(self.E, self.N, self.device)
-        actor = self.actor = Actor(env, device=True, use_graph=True)
+        actor = self.actor = Actor(env, device=True, use_graph=True, fused_mlp=fused_mlp)
+        if float_obs:
+            # the opt-in: the evaluation rides on the fused MLP step or not at all
+            from .fast_mlp_step import FastMlpStep
+            why = FastMlpStep.why_not(actor, policy)
+            if why is not None:
+                raise ValueError("Evaluator: fused_mlp was asked for, but the fused MLP step (acting/fast_mlp_step.py) does not "
+                                 "cover this policy / env: %s" % why)
         if self.eps:
             actor._exploration = _ConstantEpsilon(self.eps)
         actor._rng_seed = (self.seed * 0x9E3779B97F4A7C15 + 0xE7A1) & 0x7FFFFFFFFFFFFFFF

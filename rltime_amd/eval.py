@@ -62,7 +62,9 @@ def eval_policy(path, num_envs, episode_count, record=False, record_fps=60, rend
         training_step, cp_data = logger.get_checkpoint()
         policy.load_state(cp_data["policy_state"])
         t0 = time.time()
-        got = Evaluator(policy, env, episode_count, eps=eps, seed=seed).run()
+        # the run's own opt-in (acting.extra_args.fused_step): an MLP policy on float32 observations evaluates on the fused MLP step
+        fused = bool(((config.get("acting") or {}).get("extra_args") or {}).get("fused_step", False))
+        got = Evaluator(policy, env, episode_count, eps=eps, seed=seed, fused_mlp=fused).run()
         result = make_record(training_step, got, time.time() - t0)
     finally:
         env.close()

@@ -129,10 +129,12 @@ def create_actors(config, device="cuda", device_acting=True, use_graph=False):
         cuda = config.get("policy_args", {}).get("cuda", "auto")
         on_gpu = torch.cuda.is_available() if cuda == "auto" else bool(cuda)
         device_acting = on_gpu and hasattr(env, "step_device")
-    # acting.extra_args.fused_step: an actor-critic policy acts on the fused vector step (other keys stay ignored)
+    # acting.extra_args.fused_step: an actor-critic policy acts on the fused vector step, an MLP DQN / IQN policy on the fused
+    # MLP step (other keys stay ignored)
     fused = bool((acting.get("extra_args") or {}).get("fused_step", False))
     return Actor(env, exploration_config=acting.get("exploration"), device=device_acting, use_graph=use_graph,
-                 base_env_id=acting.get("env_base", 0), total_env_ids=acting.get("total_envs"), fused_actor_critic=fused)
+                 base_env_id=acting.get("env_base", 0), total_env_ids=acting.get("total_envs"), fused_mlp=fused,
+                 fused_actor_critic=fused)
 
 
 def train(config, logger=None, device="cuda", device_acting=True, data_parallel=None, use_graph=False,

@@ -202,7 +202,8 @@ class PolicyTrainer:
         env = self.eval_env_factory(self.eval_envs)
         try:
             t0 = time.time()
-            got = Evaluator(self.policy, env, self.eval_episodes, eps=self.eval_eps).run()
+            got = Evaluator(self.policy, env, self.eval_episodes, eps=self.eval_eps,
+                            fused_mlp=bool(getattr(self.actors, "_fused_mlp", False))).run()
             row = make_record(self.steps, got, time.time() - t0)
         finally:
             env.close()
