@@ -1271,6 +1271,30 @@ int mirl_act_mlp_fwd(int32_t E, int32_t O, int32_t L, const int32_t* widths, int
                      const float* bq, const float* fcT, const float* fcb, const float* outT, const float* outb,
                      const double* eps, const double* expo, double eps_min, uint64_t seed, const uint64_t* rng_step,
                      int32_t* actions, float* qvalues, float* taus_out, void* stream);
+/* The same launch for an actor-critic (A2C / PPO) MLP policy under a Categorical head (kernel k_act_mlp<true>; policies/torch/
+ * actor_critic.py:37-71): obs through the L leading layers and the last FC (HID wide, ReLU) exactly as above with N = 1,
+ * D = 0 — the same loop, k order and tiling, so the product row equals mirl_act_mlp_fwd's bit for bit on the same weights —
+ * then ONE dense product [logits | value] = hid . outT + outb, outT [HID][A + 1] = [logits_layer.weight; critic.weight]^T,
+ * outb [A + 1].  Thread 0 of env e's workgroup applies mirl_actor_head_ac_rng's head to that LDS row (one statement of code
+ * for both, csrc/ac_head.hpp): the block philox_4x32(rng_seed, *rng_step, e), u = float(word 0 >> 8) * 2^-24, the inverse
+ * CDF; with greedy = 1 nothing of that is drawn and the action is the first maximum of the logits.  Feeding logits_out to
+ * mirl_actor_head_ac_rng (pitch A + 1, value at column A) with the same seed and step word gives the same actions,
+ * log-probabilities and values, bit for bit.
+ * eps non-NULL (evaluation only; training passes NULL): per = float(max(pow(*eps, expo ? expo[e] : 1), eps_min)) as in
+ * mirl_act_mlp_fwd, uf = float(word 2 >> 8) * 2^-24 of the same block, and where uf < per the action becomes
+ * (word 3 * A) >> 32; the reported log-probability stays the sampled action's (the reference's eval does not recompute it).
+ * Outputs: actions int32 [E]; policy[e * out_pitch] = the log-probability, policy[e * out_pitch + 1] = the value
+ * (out_pitch >= 2: an [E][2] block at pitch 2); logits_out [E][A + 1], the raw product row, NULL allowed.  Nothing else
+ * reaches HBM, no atomics: a rerun repeats to the bit.  Dynamic LDS: 4 (2 x 256 + 64 + 4096 + W + HID + A + 1) bytes, under
+ * 22 KB at every limit.  Limits (mirl_act_mlp_ac_supported, host-only) = mirl_act_mlp_supported's with N = 1, D = 0,
+ * NO = A + 1: 1 <= O <= 64, L <= 2, widths <= 256, HID <= 512, 1 <= A <= 32, E >= 1.  MIRL_ERR_ARG, nothing written: a shape
+ * outside the limits, a null operand, greedy not 0 | 1, out_pitch < 2, a missing rng_step (required also with greedy).   */
+int mirl_act_mlp_ac_supported(int32_t E, int32_t O, int32_t L, const int32_t* widths, int32_t HID, int32_t A);
+int mirl_act_mlp_ac_fwd(int32_t E, int32_t O, int32_t L, const int32_t* widths, int32_t HID, int32_t A, const float* obs,
+                        const float* lw0T, const float* lb0, const float* lw1T, const float* lb1, const float* fcT,
+                        const float* fcb, const float* outT, const float* outb, const double* eps, const double* expo,
+                        double eps_min, uint64_t rng_seed, const uint64_t* rng_step, int32_t greedy, int32_t* actions,
+                        float* policy, int32_t out_pitch, float* logits_out, void* stream);
 
 #ifdef __cplusplus
 }

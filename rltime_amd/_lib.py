@@ -226,6 +226,9 @@ _SIGNATURES = {
     "mirl_act_mlp_lds_bytes": [_i32, _i32, _P(_i32), _i32, _i32, _i32, _i32, _i32, _P(_i64)],
     "mirl_act_mlp_fwd": [_i32, _i32, _i32, _P(_i32), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _u64, _vp, _vp, _vp, _vp, _vp],
+    "mirl_act_mlp_ac_supported": [_i32, _i32, _i32, _P(_i32), _i32, _i32],
+    "mirl_act_mlp_ac_fwd": [_i32, _i32, _i32, _P(_i32), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64,
+                            _u64, _vp, _i32, _vp, _vp, _i32, _vp, _vp],
     "mirl_bias_relu_rows": [_i64, _i32, _vp, _vp, _vp],
     "mirl_colsum_blocks": [_i64, _i32, _P(_i32)],
     "mirl_relu_bwd_bias_rows": [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp],

@@ -100,7 +100,8 @@ class Actor(ActingInterface):
     def __init__(self, vec_env, exploration_config=None, base_env_id=0, total_env_ids=None, device=False,
                  use_graph=False, fused_mlp=False, fused_actor_critic=False):
         """fused_actor_critic (config: acting.extra_args.fused_step): let an actor-critic policy act on the fused vector
-        step (acting/fast_step.py) where its shape is covered, instead of the generic device path.
+        step (acting/fast_step.py; an MLP policy on float32 vector observations: acting/fast_mlp_step.FastMlpAcStep) where its
+        shape is covered, instead of the generic device path.
         fused_mlp (the same config key): let an MLP DQN / IQN policy on float32 vector observations act on the fused MLP
         step (acting/fast_mlp_step.py) where FastActingStep declines it."""
         self._fused_actor_critic = bool(fused_actor_critic)
@@ -392,7 +393,7 @@ class Actor(ActingInterface):
     def _device_steps(self, iters):
         if self._use_graph and getattr(self, "fast_step", True) and self._fast is not False:
             from .fast_step import FastActingStep
-            if self._fast is not None or FastActingStep.supports(self) or (self._fused_mlp and self._mlp_step_supported()):
+            if self._fast is not None or FastActingStep.supports(self) or self._mlp_step_supported():
                 try:
                     return self._fast_steps(iters)
                 except Exception as e:                    # e.g. graph capture refused: the generic path still works
@@ -405,7 +406,7 @@ class Actor(ActingInterface):
                 if self._fused_actor_critic and hasattr(self._policy, "actor_head_ac_raw"):
                     import logging
                     logging.getLogger().warning("fused acting step unavailable (%s); using the generic device path",
-                                                "this actor-critic policy / env shape is not covered")
+                                                "this actor-critic policy / env shape is not covered: %s" % self._mlp_why_not)
                 elif self._fused_mlp and not hasattr(self._policy, "actor_head_ac_raw"):
                     import logging
                     logging.getLogger().warning("fused acting step unavailable (%s); using the generic device path", self._mlp_why_not)
@@ -472,11 +473,17 @@ class Actor(ActingInterface):
         return out
 
     def _mlp_step_supported(self):
-        """The opt-in's query (acting/fast_mlp_step.py), asked after FastActingStep.supports declined."""
-        from .fast_mlp_step import FastMlpStep
-        self._mlp_why_not = FastMlpStep.why_not(self)
+        """The opt-ins' query (acting/fast_mlp_step.py), asked after FastActingStep.supports declined: fused_mlp for a DQN /
+        IQN policy, fused_actor_critic for an actor-critic one."""
+        from .fast_mlp_step import FastMlpAcStep, FastMlpStep
+        ac = hasattr(self._policy, "actor_head_ac_raw")
+        self._mlp_why_not = None
+        if not (self._fused_actor_critic if ac else self._fused_mlp):
+            return False
+        cls = FastMlpAcStep if ac else FastMlpStep
+        self._mlp_why_not = cls.why_not(self)
         if self._mlp_why_not is None:
-            self._fast_cls = FastMlpStep
+            self._fast_cls = cls
         return self._mlp_why_not is None
 
     def _eps(self):

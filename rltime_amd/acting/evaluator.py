@@ -99,8 +99,11 @@ class _ConstantEpsilon(EpsilonGreedyExplorationManager):
 
 class Evaluator:
     def __init__(self, policy, env, episode_count, eps=0.0, seed=0, steps_per_launch=32, fused_mlp=False):
-        """fused_mlp (config: acting.extra_args.fused_step): evaluate an MLP DQN / IQN policy on float32 vector observations
-        (the device CartPole) on the fused MLP step (acting/fast_mlp_step.py); without it such a policy is refused."""
+        """fused_mlp (config: acting.extra_args.fused_step): evaluate an MLP policy on float32 vector observations (the device
+        CartPole) on the fused MLP step (acting/fast_mlp_step.py); without it such a policy is refused.  A DQN / IQN policy
+        acts greedily under the epsilon remap; an actor-critic (A2C / PPO) policy acts by SAMPLING from its Categorical head,
+        as the reference's eval does (eval.py:124, actor_predict without force_best), under the same fixed-epsilon remap
+        (FastMlpAcStep: words 2 and 3 of the step's Philox block)."""
         if not hasattr(getattr(env, "action_space", None), "n"):
             raise ValueError("Evaluator: the env's action space %r is not Discrete; the evaluation is greedy (arg-max) and the "
                              "reference's has no greedy mode for a Box space either" % (getattr(env, "action_space", None),))
@@ -120,11 +123,13 @@ class Evaluator:
         self.eps, self.seed, self.K = float(eps), int(seed), int(steps_per_launch)
         self.device = policy.device()
         self.sink = EvalSink(self.E, self.N, self.device)
-        actor = self.actor = Actor(env, device=True, use_graph=True, fused_mlp=fused_mlp)
+        ac_mlp = float_obs and hasattr(policy, "actor_head_ac_raw")
+        actor = self.actor = Actor(env, device=True, use_graph=True, fused_mlp=fused_mlp, fused_actor_critic=ac_mlp)
+        actor._ac_eps_remap = ac_mlp           # (training never remaps an actor-critic policy's actions; the evaluation does)
         if float_obs:
             # the opt-in: the evaluation rides on the fused MLP step or not at all
-            from .fast_mlp_step import FastMlpStep
-            why = FastMlpStep.why_not(actor, policy)
+            from .fast_mlp_step import FastMlpAcStep, FastMlpStep
+            why = (FastMlpAcStep if ac_mlp else FastMlpStep).why_not(actor, policy)
             if why is not None:
                 raise ValueError("Evaluator: fused_mlp was asked for, but the fused MLP step (acting/fast_mlp_step.py) does not "
                                  "cover this policy / env: %s" % why)

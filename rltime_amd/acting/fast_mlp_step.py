@@ -15,7 +15,11 @@ network alone.  Everything around the network is fast_step.FastActingStep's code
 the sink protocol, the rollout capture (a whole get_samples call as ONE graph), the Philox keying and the MIRL_ROLLOUT_*
 switches.  This class replaces the constructor, `refresh` (the kernel reads TRANSPOSED weight copies, [K][J] row-major,
 so that a wave's lanes read consecutive output units; rebuilt once per weight version), `_conv1` (there is no input
-layer: a foreign observation is staged into the static input block) and `_body` (the one launch)."""
+layer: a foreign observation is staged into the static input block) and `_body` (the one launch).
+
+FastMlpAcStep is the same step for an actor-critic (A2C / PPO) MLP policy under a Categorical head: mirl_act_mlp_ac_fwd as
+the one launch, the [log-probability | value] block where the q-values are, the on-policy history as the sink
+(Actor(fused_actor_critic=True), the same config key)."""
 import ctypes as C
 import os
 
@@ -27,10 +31,12 @@ from .fast_step import FastActingStep
 
 
 class FastMlpStep(FastActingStep):
+    AC = False                                   # FastMlpAcStep below: the actor-critic head on the same trunk
+
     @staticmethod
-    def _mlp_parts(pol):
-        """-> (leading Linears, the last layer's Linear, dueling) for a model of one to three FC modules of a single
-        Linear + ReLU each, else a string that says what is in the way."""
+    def _fc_stack(pol):
+        """-> the Linears of a model of one to three FC modules of a single Linear + ReLU each, else a string that says what
+        is in the way."""
         from rltime_amd.models.torch.modules import FC
         model = pol.model
         layers = list(model.layers)
@@ -47,6 +53,14 @@ class FastMlpStep(FastActingStep):
             if not (lin.weight.is_cuda and lin.weight.dtype == torch.float32 and lin.bias is not None):
                 return "an FC module's Linear is not float32 on the GPU with a bias"
             lins.append(lin)
+        return lins
+
+    @staticmethod
+    def _mlp_parts(pol):
+        """-> (leading Linears, the last layer's Linear, dueling) for a model `_fc_stack` takes, else its reason."""
+        lins = FastMlpStep._fc_stack(pol)
+        if isinstance(lins, str):
+            return lins
         dueling = getattr(pol, "value_layer", None) is not None
         if dueling and pol._fused_tail_layer() is not lins[-1]:
             return "the dueling value stream does not read the last layer's input"
@@ -113,9 +127,9 @@ class FastMlpStep(FastActingStep):
     def __init__(self, actor, obs0, need_q=True):
         self.actor = actor
         pol = self.pol = actor._policy
-        self.c51 = self.ac = False
+        self.c51, self.ac = False, self.AC
         self.Z = 1
-        self.need_q = bool(need_q)
+        self.need_q = bool(need_q) or self.ac
         self.leading, self.fc, self.dueling = self._mlp_parts(pol)
         self.lstm = self.cnn = None
         self.iqn = hasattr(pol, "num_sampling_quantiles")
@@ -139,7 +153,7 @@ class FastMlpStep(FastActingStep):
         self.rewards = torch.zeros(E, **f32)
         self.dones = torch.ones(E, dtype=torch.uint8, device=dev)
         self.actions = torch.zeros(E, dtype=torch.int32, device=dev)
-        self.qvalues = torch.zeros((E, A), **f32)
+        self.qvalues = torch.zeros((E, 2 if self.ac else A), **f32)      # actor-critic: [log-probability | value]
         self.eps = torch.zeros((), dtype=torch.float64, device=dev)
         self.rng_step = torch.zeros(1, dtype=torch.int64, device=dev)
         self.step_no = 0
@@ -156,7 +170,9 @@ class FastMlpStep(FastActingStep):
         self.freq = (pol.embedding_range * np.pi).contiguous() if self.iqn else None
         self.taus = torch.zeros(E * self.N, **f32) if self.iqn else None      # a test's tau_source is staged here
         self.in_kernel_taus = self.iqn and getattr(pol, "tau_source", None) is None
-        expl = actor._exploration
+        # (an actor-critic policy samples for itself: exploration configs are ignored, as in the reference and in fast_step.py;
+        # only the evaluator asks for its fixed epsilon's remap, acting/evaluator.py)
+        expl = actor._exploration if (not self.ac or getattr(actor, "_ac_eps_remap", False)) else None
         self.expo = expl._device_exponents(actor._env_ids, dev) if expl is not None else None
         self.eps_min = float(expl.eps_min) if expl is not None else 0.0
         self.last_obs = obs0
@@ -224,3 +240,107 @@ class FastMlpStep(FastActingStep):
             ptr(pol.quantile_layer.bias) if quant else None, ptr(self.fcT), ptr(self.fc_b), ptr(self.outT), ptr(self.out_b),
             None if greedy else ptr(self.eps), None if greedy else ptr(self.expo), self.eps_min, self.rng_seed, ptr(self.rng_step),
             ptr(self.actions), ptr(self.qvalues), None, stream()), "mirl_act_mlp_fwd")
+
+
+class FastMlpAcStep(FastMlpStep):
+    """The same step for an actor-critic (A2C / PPO) MLP policy under a Categorical head (cartpole_ppo / cartpole_a2c:
+    4 -> 64 -> 64 -> [2 logits | value]), opt-in through acting.extra_args.fused_step (Actor(fused_actor_critic=True)).
+
+    The one launch is mirl_act_mlp_ac_fwd (csrc/act_mlp.hip k_act_mlp<true>): the leading layers, the last FC, ONE product
+    [logits | value] over outT = [logits_layer.weight; critic.weight]^T, and on that row the sampling head of
+    k_actor_head_ac_rng with its Philox draw — the block where the Q-learning step keeps its q-values is [E, 2] =
+    [log-probability | value], and the sink is the on-policy history (history/online_device.py: one mirl_online_append per
+    vector step, the float32 observation handed over as its bytes).  Per vector step: env step, mirl_actor_pre, the append,
+    the network — four launches, four nodes per step of a captured rollout.  The pre-step, the sink protocol, the rollout
+    capture, the MIRL_ROLLOUT_* switches and the Philox keying are inherited unchanged."""
+    AC = True
+
+    @staticmethod
+    def _mlp_parts(pol):
+        """-> (leading Linears, the last FC's Linear, False), else a string that says what is in the way."""
+        parts = FastMlpStep._fc_stack(pol)
+        if isinstance(parts, str):
+            return parts
+        last = parts[-1]
+        logits, critic = pol.actor.logits_layer, pol.critic
+        if logits.in_features != last.out_features or critic.in_features != last.out_features or critic.out_features != 1:
+            return "the logits layer and the critic do not both read the last FC module"
+        if logits.bias is None or critic.bias is None:
+            return "the logits layer or the critic has no bias"
+        return parts[:-1], last, False
+
+    @staticmethod
+    def _shape(pol, parts, E, A):
+        """FastMlpStep._shape's tuple with N = 1, D = 0, NO = A + 1: (E, O, L, widths, 1, 0, HID, A + 1, A)."""
+        leading, last, _ = parts
+        O = leading[0].in_features if leading else last.in_features
+        widths = (C.c_int32 * 2)(*([lin.out_features for lin in leading] + [0, 0])[:2])
+        return (E, O, len(leading), widths, 1, 0, last.out_features, A + 1, A)
+
+    @staticmethod
+    def _ac_args(shape):
+        """The arguments of mirl_act_mlp_ac_supported: (E, O, L, widths, HID, A)."""
+        return shape[:4] + (shape[6], shape[8])
+
+    @staticmethod
+    def why_not(actor, pol=None):
+        """None when the step covers this actor's policy and env, else the reason as a string."""
+        pol = pol if pol is not None else actor._policy
+        try:
+            if not hasattr(pol, "actor_head_ac_raw"):
+                return "the policy is not an actor-critic policy"
+            if not hasattr(actor._action_space, "n") or pol.has_normal_head():
+                return "the action space is not Discrete"
+            if pol.why_not_on_device() is not None:
+                return pol.why_not_on_device()
+            if not getattr(pol, "is_cuda", lambda: False)():
+                return "the policy is not on the GPU"
+            parts = FastMlpAcStep._mlp_parts(pol)
+            if isinstance(parts, str):
+                return parts
+            if pol.model.layer_pre_processors:
+                return "the model has layer pre-processors"
+            space = actor._vec_env.observation_space
+            if hasattr(space, "spaces") or str(getattr(space, "dtype", "")) != "float32" or len(tuple(space.shape)) != 1:
+                return "the observation space is not a float32 vector"
+            if not hasattr(actor._vec_env, "step_device"):
+                return "the env does not step on the device"
+            shape = FastMlpAcStep._shape(pol, parts, actor._num_envs, actor._action_space.n)
+            if shape[1] != int(space.shape[0]):
+                return "the first layer does not read the observation"
+            if pol.actor.logits_layer.out_features != shape[8]:
+                return "the logits layer does not have one output per action"
+            if not lib.mirl_act_mlp_ac_supported(*FastMlpAcStep._ac_args(shape)):
+                return "mirl_act_mlp_ac_supported refuses the shape (E, O, L, widths, HID, A) = %r" % (
+                    shape[:3] + (list(shape[3])[:shape[2]], shape[6], shape[8]),)
+            return None
+        except Exception as e:                           # a policy this code does not know: not covered
+            return "%s: %s" % (type(e).__name__, e)
+
+    @staticmethod
+    def supports(actor):
+        return FastMlpAcStep.why_not(actor) is None
+
+    def set_need_q(self, need_q):
+        pass                                             # the [log-probability | value] pair is always evaluated
+
+    def refresh(self):
+        pol, A = self.pol, self.A
+        with torch.no_grad():
+            dst = [w for w in self.lwT] + [self.fcT, self.fc_b, self.outT[:, :A], self.outT[:, A:], self.out_b[:A], self.out_b[A:]]
+            src = [lin.weight.t() for lin in self.leading] + [self.fc.weight.t(), self.fc.bias, pol.actor.logits_layer.weight.t(),
+                                                              pol.critic.weight.t(), pol.actor.logits_layer.bias, pol.critic.bias]
+            for d, s in zip(dst, src):
+                d.copy_(s.detach())
+
+    def _body(self):
+        """The whole network and the sampling head: reads x_in, writes actions and the [log-probability | value] block."""
+        lead = self.leading
+        remap = self.expo is not None                    # the evaluator's fixed epsilon; training passes none
+        check(lib.mirl_act_mlp_ac_fwd(
+            *self._ac_args(self.shape), ptr(self.x_in),
+            ptr(self.lwT[0]) if len(lead) >= 1 else None, ptr(lead[0].bias) if len(lead) >= 1 else None,
+            ptr(self.lwT[1]) if len(lead) >= 2 else None, ptr(lead[1].bias) if len(lead) >= 2 else None,
+            ptr(self.fcT), ptr(self.fc_b), ptr(self.outT), ptr(self.out_b),
+            ptr(self.eps) if remap else None, ptr(self.expo) if remap else None, self.eps_min, self.rng_seed, ptr(self.rng_step),
+            0, ptr(self.actions), ptr(self.qvalues), 2, None, stream()), "mirl_act_mlp_ac_fwd")

@@ -35,8 +35,16 @@
 // anything.  The kernel is a latency chain of four or five products; what a workgroup waits for is the first tile of
 // each (served by L2 after the first workgroup touched it: the shipped IQN weights are 50 KB) and the LDS reads of the
 // k loop (one weight + RB broadcast inputs per RB multiply-adds), not HBM bandwidth.
+//
+// The actor-critic form (mirl_act_mlp_ac_fwd, k_act_mlp<true>; cartpole_ppo / cartpole_a2c: 4 -> 64 -> 64 -> [2 logits | value],
+// rltime/policies/torch/actor_critic.py:37-71) is the same trunk with N = 1, D = 0 — every product dense_rb<1>, as a policy
+// without a quantile layer runs it — one dense output product [logits | value] (NO = A + 1), and as its tail the sampling head
+// of k_actor_head_ac_rng (ac_head.hpp: one statement for both) on the LDS row, by thread 0.  One row: the LDS block is
+// 4.6 K floats + W + HID + A + 1, under 22 KB at every limit; the occupancy and latency reasoning above carries over unchanged
+// (E workgroups on 256 CUs, a chain of three or four products).
 #include "common.hpp"
 #include "philox.hpp"
+#include "ac_head.hpp"
 
 namespace mirl {
 
@@ -48,6 +56,8 @@ struct ActMlpArgs {
   const double* eps; const double* expo; double eps_min;
   uint64_t seed; const uint64_t* step;
   int32_t* actions; float* qvalues; float* taus_out;
+  // the actor-critic tail (k_act_mlp<true>): qvalues is the [log-probability | value] block, out_pitch floats per env
+  float* logits_out; int greedy, out_pitch;
   int E, O, L, w0, w1, W, N, D, HID, NO, A, hid_run, no_run, CH, has_val;
 };
 
@@ -117,6 +127,10 @@ __device__ __forceinline__ void dense_rb(const float* in, int in_pitch, int R, i
   }
 }
 
+// AC = false: the Q-learning tail below (dueling combine, mean over the quantile rows, first maximum, epsilon-greedy).
+// AC = true: the actor-critic tail — the one row [logits | value] goes through ac_head_row (ac_head.hpp), the statement
+// k_actor_head_ac and k_actor_head_ac_rng share.  Everything before the tail is the same code for both.
+template <bool AC>
 __global__ void __launch_bounds__(256)
 k_act_mlp(ActMlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -190,6 +204,29 @@ k_act_mlp(ActMlpArgs a) {
     }
   }
 
+  if constexpr (AC) {
+    // k_actor_head_ac_rng (actor_critic.hip) on the LDS row [A logits | value]: the raw row for whoever asked, then thread 0
+    // draws the block (seed, *step, e), samples (or takes the first maximum) and writes the action and the policy pair
+    const int A = a.A, NO = a.NO;
+    if (a.logits_out && tid < NO) a.logits_out[(int64_t)e * NO + tid] = outs[tid];
+    if (tid != 0) return;
+    uint32_t r[4] = {0u, 0u, 0u, 0u};
+    if (!a.greedy || a.eps) philox_4x32(a.seed, *a.step, (uint32_t)e, r);
+    const float u = a.greedy ? 0.f : (float)(r[0] >> 8) * (1.0f / 16777216.0f);
+    float lp;
+    int act = ac_head_row(outs, A, u, a.greedy, &lp);
+    if (a.eps) {
+      // the evaluation's epsilon remap on words 2 and 3 of the same block; the log-probability stays the sampled action's
+      const double pe = pow(*a.eps, a.expo ? a.expo[e] : 1.0);
+      const float per = (float)(pe > a.eps_min ? pe : a.eps_min);
+      const float uf = (float)(r[2] >> 8) * (1.0f / 16777216.0f);
+      if (uf < per) act = (int)(((uint64_t)r[3] * (uint64_t)A) >> 32);
+    }
+    a.actions[e] = act;
+    a.qvalues[(int64_t)e * a.out_pitch] = lp;
+    a.qvalues[(int64_t)e * a.out_pitch + 1] = outs[A];
+    return;
+  }
   // k_actor_head (acting.hip) on the LDS rows, by the first wave: V + A - mean_a A, mean over the rows, first maximum,
   // epsilon-greedy on one Philox block per (step, env)
   if (tid >= 64) return;
@@ -283,6 +320,7 @@ extern "C" int mirl_act_mlp_fwd(int32_t E, int32_t O, int32_t L, const int32_t* 
   a.freq = freq; a.taus = taus; a.wqT = wqT; a.bq = bq; a.fcT = fcT; a.fcb = fcb; a.outT = outT; a.outb = outb;
   a.eps = eps; a.expo = expo; a.eps_min = eps_min; a.seed = seed; a.step = rng_step;
   a.actions = actions; a.qvalues = qvalues; a.taus_out = D > 0 ? taus_out : nullptr;
+  a.logits_out = nullptr; a.greedy = 0; a.out_pitch = 0;
   a.E = E; a.O = O; a.L = L; a.w0 = L >= 1 ? widths[0] : 0; a.w1 = L >= 2 ? widths[1] : 0;
   a.W = L ? widths[L - 1] : O; a.N = N; a.D = D; a.HID = HID; a.NO = NO; a.A = A;
   // need_q = 0 under a dueling head: the value stream's hidden units and its output column are not evaluated (out_w is
@@ -295,9 +333,44 @@ extern "C" int mirl_act_mlp_fwd(int32_t E, int32_t O, int32_t L, const int32_t* 
   const size_t lds = 4 * (size_t)act_mlp_lds_floats(a.W, N, D, HID, NO, a.CH);
   hipStream_t st = (hipStream_t)stream;
   const double wfloats = (double)O * a.w0 + (double)a.w0 * a.w1 + (double)D * a.W + (double)a.W * HID + (double)HID * NO;
-  if (lds > 65536) { int rc = raise_lds_limit(k_act_mlp, lds); if (rc) return rc; }
+  if (lds > 65536) { int rc = raise_lds_limit(k_act_mlp<false>, lds); if (rc) return rc; }
   ProfScope ps("k_act_mlp", 4.0 * (wfloats + (double)E * (O + A + 1)), st);
-  hipLaunchKernelGGL(k_act_mlp, dim3(E), dim3(256), lds, st, a);
+  hipLaunchKernelGGL(k_act_mlp<false>, dim3(E), dim3(256), lds, st, a);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
+// ---- the actor-critic form: the same trunk, [logits | value] as the one output product, the sampling head on its row -------
+extern "C" int mirl_act_mlp_ac_supported(int32_t E, int32_t O, int32_t L, const int32_t* widths, int32_t HID, int32_t A) {
+  return mirl_act_mlp_supported(E, O, L, widths, 1, 0, HID, A + 1, A);
+}
+
+extern "C" int mirl_act_mlp_ac_fwd(int32_t E, int32_t O, int32_t L, const int32_t* widths, int32_t HID, int32_t A, const float* obs,
+                                   const float* lw0T, const float* lb0, const float* lw1T, const float* lb1, const float* fcT,
+                                   const float* fcb, const float* outT, const float* outb, const double* eps, const double* expo,
+                                   double eps_min, uint64_t rng_seed, const uint64_t* rng_step, int32_t greedy, int32_t* actions,
+                                   float* policy, int32_t out_pitch, float* logits_out, void* stream) {
+  if (!mirl_act_mlp_ac_supported(E, O, L, widths, HID, A))
+    return fail(MIRL_ERR_ARG, "act_mlp_ac_fwd: unsupported shape (O <= 64, L <= 2 layers of <= 256, HID <= 512, 1 <= A <= 32)");
+  if ((greedy != 0 && greedy != 1) || out_pitch < 2) return fail(MIRL_ERR_ARG, "act_mlp_ac_fwd: greedy 0 | 1, out_pitch >= 2");
+  if (!obs || !fcT || !fcb || !outT || !outb || !rng_step || !actions || !policy || (L >= 1 && (!lw0T || !lb0)) ||
+      (L >= 2 && (!lw1T || !lb1)))
+    return fail(MIRL_ERR_ARG, "act_mlp_ac_fwd: null operand (the step word is required, also with greedy)");
+  ActMlpArgs a;
+  a.obs = obs; a.lwT[0] = lw0T; a.lb[0] = lb0; a.lwT[1] = lw1T; a.lb[1] = lb1;
+  a.freq = nullptr; a.taus = nullptr; a.wqT = nullptr; a.bq = nullptr; a.fcT = fcT; a.fcb = fcb; a.outT = outT; a.outb = outb;
+  a.eps = eps; a.expo = expo; a.eps_min = eps_min; a.seed = rng_seed; a.step = rng_step;
+  a.actions = actions; a.qvalues = policy; a.taus_out = nullptr;
+  a.logits_out = logits_out; a.greedy = greedy; a.out_pitch = out_pitch;
+  a.E = E; a.O = O; a.L = L; a.w0 = L >= 1 ? widths[0] : 0; a.w1 = L >= 2 ? widths[1] : 0;
+  a.W = L ? widths[L - 1] : O; a.N = 1; a.D = 0; a.HID = HID; a.NO = A + 1; a.A = A;
+  a.hid_run = HID; a.no_run = A + 1; a.has_val = 0;
+  a.CH = 1;                                // one row: 4.6 K floats + W + HID + A + 1, under 22 KB at every limit
+  const size_t lds = 4 * (size_t)act_mlp_lds_floats(a.W, 1, 0, HID, A + 1, a.CH);
+  hipStream_t st = (hipStream_t)stream;
+  const double wfloats = (double)O * a.w0 + (double)a.w0 * a.w1 + (double)a.W * HID + (double)HID * (A + 1);
+  ProfScope ps("k_act_mlp_ac", 4.0 * (wfloats + (double)E * (O + 3 + (logits_out ? A + 1 : 0))), st);
+  hipLaunchKernelGGL(k_act_mlp<true>, dim3(E), dim3(256), lds, st, a);
   MIRL_LAUNCH_CHECK();
   return MIRL_OK;
 }

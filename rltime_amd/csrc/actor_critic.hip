@@ -7,52 +7,13 @@
 // float32 per output; no float atomics, every sum in a fixed order, so a rerun repeats the first run bit for bit.
 #include "common.hpp"
 #include "philox.hpp"
+#include "ac_head.hpp"
 
 namespace mirl {
 
-// ---- the softmax pieces both the head and the loss use: the SAME sequence of operations in both --------------------
-// zmax = max_j z_j (float32 compare, first maximum), d_j = double(z_j) - double(zmax) (exact), e_j = exp(d_j),
-// S = sum_j e_j in ascending j, log-probability of action a = d_a - log(S), rounded once to float32.
-struct RowSoftmax { float zmax; int first; double S, W; };    // W = sum_j e_j d_j (the loss's entropy needs it)
-
-__device__ inline RowSoftmax row_softmax(const float* __restrict__ z, int A) {
-  RowSoftmax r;
-  r.zmax = z[0]; r.first = 0;
-  for (int j = 1; j < A; ++j) { const float v = z[j]; if (v > r.zmax) { r.zmax = v; r.first = j; } }
-  r.S = 0.0; r.W = 0.0;
-  for (int j = 0; j < A; ++j) {
-    const double d = (double)z[j] - (double)r.zmax;
-    const double e = exp(d);
-    r.S += e;
-    r.W += e * d;
-  }
-  return r;
-}
-
-__device__ inline float row_log_prob(const float* __restrict__ z, int a, const RowSoftmax& r, double logS) {
-  return (float)(((double)z[a] - (double)r.zmax) - logS);
-}
-
 // ---- 1. the sampling head ------------------------------------------------------------------------------------------
-// Everything after the uniform, stated once for both kernels below: softmax pieces, inverse CDF (or the first maximum),
-// log-probability of the chosen action.
-__device__ inline int ac_head_row(const float* __restrict__ z, int A, float u, int greedy, float* __restrict__ logp) {
-  const RowSoftmax r = row_softmax(z, A);
-  int a = r.first;
-  if (!greedy) {
-    // inverse CDF without a division: the smallest a with u S < sum_{j <= a} e_j; the partial sums are formed exactly as S was
-    const double want = (double)u * r.S;
-    double cum = 0.0;
-    a = A - 1;
-    for (int j = 0; j < A; ++j) {
-      cum += exp((double)z[j] - (double)r.zmax);
-      if (want < cum) { a = j; break; }
-    }
-  }
-  *logp = row_log_prob(z, a, r, log(r.S));
-  return a;
-}
-
+// Everything after the uniform is ac_head_row (ac_head.hpp): softmax pieces, inverse CDF (or the first maximum),
+// log-probability of the chosen action — shared with the fused MLP acting step (csrc/act_mlp.hip).
 __global__ __launch_bounds__(64) void k_actor_head_ac(int E, int A, const float* __restrict__ logits, long pitch,
                                                       const float* __restrict__ values, const float* __restrict__ u, int greedy,
                                                       int* __restrict__ actions, float* __restrict__ logp, float* __restrict__ values_out,

@@ -9,7 +9,11 @@
   acting_sides   the same vector step, fed into the rollout window, four ways in ONE call, alternating, `--repeats` windows of
             2 x 64 steps each: the generic device path eager and graphed (Actor.use_graph), the fused step per step
             (acting.extra_args.fused_step with MIRL_ROLLOUT_GRAPH=0) and the fused rollout graph, 64 steps per launch — for
-            catch_ppo.json's network and for catch_ppo_lstm.json's
+            catch_ppo.json's network, for catch_ppo_lstm.json's and for the MLP of cartpole_ppo_device.json (the fused sides
+            are then acting/fast_mlp_step.FastMlpAcStep: the whole network as one launch); `--configs` narrows the list
+  iteration   (`--only iteration`) wall time of one learner iteration (32 vector steps of acting at 16 envs + 16 minibatch
+            updates) of cartpole_ppo_device.json and of cartpole_ppo_fused.json, alternating in one call, `--repeats` runs each:
+            from the `total.seconds` of the runs' own log rows, the first 20 iterations (start-up, captures) left out
 
     python tools/actor_critic_probe.py [--iters 200] [--repeats 5]      -> one JSON line
 """
@@ -283,21 +287,56 @@ def acting_sides(config, repeats, steps=64):
     return out
 
 
+ACTING_CONFIGS = ("catch_ppo.json", "catch_ppo_lstm.json", "cartpole_ppo_device.json")
+
+
+def iteration_times(repeats, iters=120, log_iters=20):
+    """Milliseconds per learner iteration of the two CartPole PPO configs, steady state: (seconds at the last log row -
+    seconds at the first) / the iterations between them."""
+    import tempfile
+    from rltime_amd.general.config import load_config
+    from rltime_amd.train import train_from_config
+    names = ("cartpole_ppo_device.json", "cartpole_ppo_fused.json")
+    times = {n: [] for n in names}
+    for r in range(repeats):
+        for name in names:
+            cfg = load_config(name)
+            per_iter = cfg["acting"]["actor_envs"] * cfg["training"]["args"]["nstep_train"]
+            with tempfile.TemporaryDirectory() as tmp:
+                train_from_config(name, log_dir=tmp, log_name="run", seed=1 + r,
+                                  conf_update={"training": {"args": {"total_steps": per_iter * iters, "log_freq": per_iter * log_iters}}})
+                torch.cuda.synchronize()
+                rows = [json.loads(line) for line in open(os.path.join(tmp, "run", "train.json"))]
+            secs = [row["total"]["seconds"] for row in rows]
+            assert len(secs) == iters // log_iters, len(secs)
+            times[name].append((secs[-1] - secs[0]) / (iters - log_iters) * 1e3)
+    out = {"iterations": iters - log_iters, "steps_per_iteration": per_iter}
+    for name, t in times.items():
+        out[name + "_ms"] = [round(x, 2) for x in t]
+        out[name + "_ms_median"] = round(sorted(t)[len(t) // 2], 2)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--only", default=None, help="acting_sides: that row alone")
+    ap.add_argument("--only", default=None, help="acting_sides | iteration: that row alone")
+    ap.add_argument("--configs", default=",".join(ACTING_CONFIGS), help="acting_sides: the configs, comma-separated")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("actor_critic_probe: no GPU visible; timings are taken on the device only")
+    configs = [c for c in a.configs.split(",") if c]
     if a.only == "acting_sides":
-        print(json.dumps({"acting_sides": [acting_sides(c, a.repeats) for c in ("catch_ppo.json", "catch_ppo_lstm.json")]}))
+        print(json.dumps({"acting_sides": [acting_sides(c, a.repeats) for c in configs]}))
+        return
+    if a.only == "iteration":
+        print(json.dumps({"iteration": iteration_times(a.repeats)}))
         return
     out = {"loss": [loss_times(512, A, a.iters, a.repeats) for A in (6, 18)], "window": window_time(max(8, a.iters // 10)),
            "window_recurrent": window_time(max(8, a.iters // 10), state_f32=1024),
            "acting": acting_time(a.iters),
-           "acting_sides": [acting_sides(c, a.repeats) for c in ("catch_ppo.json", "catch_ppo_lstm.json")],
+           "acting_sides": [acting_sides(c, a.repeats) for c in configs],
            "normal_loss": [normal_loss_times(M, 1, a.iters, a.repeats) for M in (128, 512)],
            "normal_head": [normal_head_time(E, 1, a.iters, a.repeats) for E in (128, 512)],
            "mountaincar_step": [mountaincar_step_time(E, a.iters, a.repeats) for E in (128, 512)]}
