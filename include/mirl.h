@@ -534,7 +534,7 @@ int mirl_conv1_u8_wrw_masked(int64_t N, int32_t H, int32_t W, const uint8_t* x, 
                              float* scratch, float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w,
                              float* db, void* stream);
 
-/* ---- the same input layer from ONE-plane frames (csrc/conv_in1p.hip): the reference's recurrent set-up
+/* ---- the same input layer from ONE-plane frames (csrc/conv_in_rows.hip): the reference's recurrent set-up
  * (configs/atari_iqn_lstm.json with env_wrappers/atari_lstm.json, "stack": 1) feeds Conv2d(1 -> 32, kernel 8,
  * stride 4) with unstacked (1, H, W) uint8 observations.  A second kernel family, because the 4-plane one gives an
  * MFMA k-group to a plane; here a k-group is a kernel row.  bf16 matrix pipe with an f32 result: pixels are exact in
@@ -570,7 +570,7 @@ int mirl_conv1p_u8_wrw_masked(int64_t N, int32_t H, int32_t W, const uint8_t* x,
                               float scale, float* scratch, float* dw, int64_t ws_o, int64_t ws_h, int64_t ws_w,
                               float* db, void* stream);
 
-/* ---- the same layer from THREE-plane uint8 frames (csrc/conv_in3p.hip): Conv2d(3 -> 32, kernel 8, stride 4) on one RGB
+/* ---- the same layer from THREE-plane uint8 frames (csrc/conv_in_rows.hip): Conv2d(3 -> 32, kernel 8, stride 4) on one RGB
  * frame per step (the reference's ple_flappy_bird_iqn_lstm.json: observations (3, 120, 80)) or a three-plane history stack.
  * Arithmetic, wpk, flags, scratch and the masked form exactly as the one-plane family above; the only difference in the
  * signatures is the weight's channel stride:

@@ -217,7 +217,7 @@ class FastActingStep:
         _, hh, ww = obs0.shape[1:]
         k, s = c1.kernel_size[0], c1.stride[0]
         self.y1 = torch.empty((E, c1.out_channels, (hh - k) // s + 1, (ww - k) // s + 1), memory_format=torch.channels_last, **f32)
-        self.conv1_family = conv_u8_family(obs0.shape[1])        # by plane count: csrc/conv_in.hip (4), conv_in1p.hip (1), conv_in3p.hip (3)
+        self.conv1_family = conv_u8_family(obs0.shape[1])        # by plane count: csrc/conv_in.hip (4), conv_in_rows.hip (1, 3)
         self.wpk = torch.empty(self.conv1_family.wpk_floats(), **f32)
         self.xh = torch.zeros((E, K), **f32)                     # [conv features (NCHW order) | extras | zeros | masked h]
         self.extra = torch.zeros((E, X), **f32) if X else None   # the compact rows the replay ingests as `extra`

@@ -7,7 +7,7 @@ HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="$HERE/../librltime_hip.so"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function ${MIRL_EXTRA_HIPCC_FLAGS:-}"
-UNITS="replay qmath c51 lstm lstm_seq lstm_extras convert nnops acting actnet conv_in conv_in1p conv_in3p conv_mid gemm3 conv3 conv_wrw optim actor_critic act_mlp"
+UNITS="replay qmath c51 lstm lstm_seq lstm_extras convert nnops acting actnet conv_in conv_in_rows conv_mid gemm3 conv3 conv_wrw optim actor_critic act_mlp"
 newest_hdr=$(ls -t "$HERE"/*.h "$HERE"/*.hpp "$HERE"/../../include/*.h "$HERE/build.sh" | head -1)
 pids=()
 objs=()

@@ -37,7 +37,7 @@
 // The layer's input needs no gradient; its weight gradient (k_conv1_u8_wrw, further
 // down in this file) reads the same uint8 frames.  Launch plans and size constants
 // (C1_*): csrc/host_util.hpp; what this family shares with the one-plane one
-// (csrc/conv_in1p.hip) on the device and in the entry points: csrc/conv_u8.hpp.
+// (csrc/conv_in_rows.hip) on the device and in the entry points: csrc/conv_u8.hpp.
 // Autograd wiring: rltime_amd/models/torch/fused.py:_ConvU8 through its four-plane family.
 #include "conv_u8.hpp"
 #include <stdlib.h>

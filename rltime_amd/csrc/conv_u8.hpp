@@ -1,7 +1,7 @@
-// conv_u8.hpp — what the input-layer families share (csrc/conv_in.hip: four-plane uint8 frames, csrc/conv_in1p.hip: one
-// plane, csrc/conv_in3p.hip: three): the entry points' argument checks and packed-weights bookkeeping, the byte -> bf16
-// helpers, and of the bf16-pipe weight-gradient kernels everything but the frame staging loop and the tap walk.  Launch
-// plans: host_util.hpp.
+// conv_u8.hpp — what the input-layer families share (csrc/conv_in.hip: four-plane uint8 frames, csrc/conv_in_rows.hip:
+// one and three planes): the entry points' argument checks and packed-weights bookkeeping, the byte -> bf16 helpers, and
+// of the bf16-pipe weight-gradient kernels everything but the frame staging loop and the tap walk.  Launch plans:
+// host_util.hpp.
 #pragma once
 #include "common.hpp"
 #include "split3.hpp"

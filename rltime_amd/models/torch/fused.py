@@ -16,8 +16,8 @@ expressions; parity tests in tests/test_fused_gpu.py compare against those):
                      (csrc/conv_in.hip): no converted copy of the frames, no separate
                      bias / ReLU pass; backward = the weight gradient from the same uint8
                      frames, ReLU mask and bias gradient in that kernel.  One-plane frames
-                     (N, 1, H, W) take the second kernel family, csrc/conv_in1p.hip, and
-                     three-plane ones (N, 3, H, W) the third, csrc/conv_in3p.hip; one
+                     (N, 1, H, W) take the second kernel family, csrc/conv_in_rows.hip, and
+                     three-plane ones (N, 3, H, W) its P = 3 instance; one
                      autograd function serves all through a ConvU8Family
   cos_embed          IQN cosine features (iqn.py:78-81) in one kernel
   quantile_product   x[m] * relu(phi @ Wq^T + bq)[m, n] (iqn.py:82-102) with a
@@ -330,7 +330,7 @@ def frames_to_f32_nhwc(x, scale):
 
 class ConvU8Family:
     """One kernel family of the input layer from uint8 frames, by plane count: what differs between csrc/conv_in.hip (four
-    planes), csrc/conv_in1p.hip (one) and csrc/conv_in3p.hip (three) above the kernels.  `call(name, ...)` runs
+    planes) and csrc/conv_in_rows.hip (one and three) above the kernels.  `call(name, ...)` runs
     `<prefix><name>` on the current stream."""
 
     def __init__(self, planes, prefix, fwd_flags, fwd_packed, planes_in_query=False):

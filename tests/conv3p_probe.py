@@ -1,4 +1,4 @@
-"""Part-probing operands for the three-plane input layer (csrc/conv_in3p.hip), in the manner of tests/conv1p_probe.py: a
+"""Part-probing operands for the three-plane input layer (csrc/conv_in_rows.hip), in the manner of tests/conv1p_probe.py: a
 uint8 pixel is exact in ONE bf16 part, the other operand (w * scale in the forward, g in the weight gradient) is split three
 ways, so hi.x, mid.x and lo.x are all the products there are.  The operands below populate all three parts at EVERY element
 of the split operand, with every part positive in the element's unit, and stay exact in f32 in any summation order: float64

@@ -1,4 +1,4 @@
-"""GPU: the input layer from ONE-plane uint8 frames (csrc/conv_in1p.hip) through its C entry points, against the reference's
+"""GPU: the input layer from ONE-plane uint8 frames (csrc/conv_in_rows.hip) through its C entry points, against the reference's
 expression for the layer, rltime/models/torch/modules/cnn.py:44-49 at Conv2d(1 -> 32, kernel 8, stride 4) — the shape of
 configs/atari_iqn_lstm.json with env_wrappers/atari_lstm.json ("stack": 1).  Integer operands make every sum exact in f32 in
 any order, so indexing is checked BIT-exactly against float64; the operands of tests/conv1p_probe.py do the same with all

@@ -1,4 +1,4 @@
-"""GPU: one-plane frames through the layers above the kernels of csrc/conv_in1p.hip — the CNN module and its autograd function
+"""GPU: one-plane frames through the layers above the kernels of csrc/conv_in_rows.hip — the CNN module and its autograd function
 (models/torch/fused.py), the fast acting step and its captured rollout (acting/fast_step.py), and the train loop on the shipped
 configs/catch_iqn_lstm_stack1.json: the reference's recurrent set-up on unstacked frames (configs/atari_iqn_lstm.json with
 env_wrappers/atari_lstm.json, "stack": 1)."""

@@ -1,5 +1,5 @@
 """CPU: the part-probing operands of tests/conv1p_probe.py are what tests/test_conv1p_gpu.py needs them to be.  For exactly
-the operands the GPU tests send through csrc/conv_in1p.hip:
+the operands the GPU tests send through csrc/conv_in_rows.hip:
 
   1. all terms of an output are integers of the output's unit and sum |terms| < 2^24 of it, so every partial sum in any order
      is an f32 number; three shuffled f32 summation orders are followed term by term and every prefix equals float64's;

@@ -1,4 +1,4 @@
-"""GPU: the input layer from THREE-plane uint8 frames (csrc/conv_in3p.hip) through its C entry points, against the reference's
+"""GPU: the input layer from THREE-plane uint8 frames (csrc/conv_in_rows.hip) through its C entry points, against the reference's
 expression for the layer, rltime/models/torch/modules/cnn.py:44-49 at Conv2d(3 -> 32, kernel 8, stride 4) — the shape of
 configs/ple_flappy_bird_iqn_lstm.json (one RGB frame per step).  Integer operands make every sum exact in f32 in any order,
 so indexing is checked BIT-exactly against float64; the operands of tests/conv3p_probe.py do the same with all three bf16

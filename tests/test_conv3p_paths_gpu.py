@@ -1,4 +1,4 @@
-"""GPU: three-plane frames through the layers above the kernels of csrc/conv_in3p.hip — the CNN module and its autograd function
+"""GPU: three-plane frames through the layers above the kernels of csrc/conv_in_rows.hip — the CNN module and its autograd function
 (models/torch/fused.py), the fast acting step, its captured rollout and the fused evaluation (acting/fast_step.py,
 acting/evaluator.py) on Flappy in colour, and the train loop on the shipped configs/flappy_iqn_lstm_rgb.json: the reference's
 ple_flappy_bird_iqn_lstm.json set-up, one (3, 120, 80) RGB frame per step."""

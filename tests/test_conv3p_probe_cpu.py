@@ -1,4 +1,4 @@
-"""CPU: the three-plane input layer (csrc/conv_in3p.hip) as far as it can be held without a device.
+"""CPU: the three-plane input layer (csrc/conv_in_rows.hip) as far as it can be held without a device.
 
 The part-probing operands of tests/conv3p_probe.py are what tests/test_conv3p_gpu.py needs them to be.  For exactly the
 operands the GPU tests send through the kernels:

@@ -1,4 +1,4 @@
-"""Timing probe for the input layer on three-plane frames (csrc/conv_in3p.hip) against the path such frames took before the
+"""Timing probe for the input layer on three-plane frames (csrc/conv_in_rows.hip) against the path such frames took before the
 family existed: conversion (csrc/convert.hip) + library convolution + bias / ReLU pass forward, mask + bias-gradient pass +
 the library's weight gradient backward (CNN(direct_u8=False)), and for acting the generic device path (no fused step, no
 rollout graph).  The former path is run from this tree by taking the three-plane entry out of fused._CONV_U8 for the
