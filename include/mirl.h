@@ -416,6 +416,33 @@ int mirl_lstm_seq_bwd_supported(int32_t T, int32_t B, int32_t H);
 int mirl_lstm_seq_bwd_workspace_bytes(int32_t B, int32_t H, int64_t* bytes);
 int mirl_lstm_seq_bwd(int32_t T, int32_t B, int32_t H, float* gates, const float* w_hh, const float* c_all,
                       const float* cm, const float* d_out, const float* keep, void* workspace, void* stream);
+/* The MULTI-SAMPLE sequence (IQNPolicy(injection_layer=1): the quantile layer in front of the LSTM, merge mode
+ * "inner" of rltime/models/torch/modules/lstm.py:83-116) as one launch per time step (csrc/lstm_multi.hip): B stored
+ * states, N samples per state, rows ordered (t, b, n).  Every step
+ *   hin_b = h_b keep[t][b], cin_b = c_b keep[t][b], r_b = hin_b W_hh^T                     (B rows, f32 MFMA)
+ *   a = gates[t][b][n] + r_b; c_n = sig(a_f) cin_b + sig(a_i) tanh(a_g); out[t][b][n] = h_n = sig(a_o) tanh(c_n)
+ *   h_b = mean_n h_n, c_b = mean_n c_n                                                      (ascending n, in one lane)
+ * gates [T][B][N][4H] holds the input projection + both biases on entry (gate order i, f, g, o); with need_grad it
+ * holds the activated gates on exit, without it is only read.  h0 / c0 [B][H] are the states before step 0 (keep[0]
+ * is applied inside), keep [T][B] = 1 - initials, out [T][B][N][H].  hm / cm [T+1][B][H] receive the masked inputs of
+ * every step (row T = the unmasked final state) and carry the state from launch to launch; h_last / c_last [B][H]
+ * (both or neither) receive the final state alone.  The T launches are enqueued on `stream` in order; nothing is
+ * allocated, nothing waits, no workgroup depends on another of its launch.
+ * Shapes (mirl_lstm_ms_supported, host logic): T >= 1, B >= 1, 2 <= N <= 64, H % 16 == 0, 16 <= H <= 1024; every
+ * device pointer but keep 16-byte aligned.  Everything else is MIRL_ERR_ARG.                                      */
+int mirl_lstm_ms_supported(int32_t T, int32_t B, int32_t N, int32_t H);
+int mirl_lstm_ms_fwd(int32_t T, int32_t B, int32_t N, int32_t H, float* gates, const float* w_hh, const float* h0,
+                     const float* c0, const float* keep, float* out, float* hm, float* cm, float* h_last,
+                     float* c_last, int32_t need_grad, void* stream);
+/* Its backward sweep, t = T-1 .. 0, one launch per step (the final state is not differentiable, as in the ops above):
+ * gates holds the activated gates on entry and d loss / d pre-activation on exit, cm as the forward wrote it, d_out
+ * [T][B][N][H] the gradient of `out`.  Step t forms dh_b = (S[t+1][b] W_hh) keep[t+1][b] (f32 MFMA over K = 4H), adds
+ * dh_b / N to every sample's output gradient, rebuilds c_n from the gates and cm[t], and writes
+ * S[t][b] = sum_n d pre-activation [T][B][4H] — so that dW_hh = sum_t S[t]^T hm[t] — in ascending n without atomics:
+ * reruns are bit-identical.  dc_ws [B][H] carries d loss / d cin from step to step and dh_ws [B][H] receives each
+ * step's dh_b; neither needs initialising, both are private to the call until the stream has passed it.          */
+int mirl_lstm_ms_bwd(int32_t T, int32_t B, int32_t N, int32_t H, float* gates, const float* w_hh, const float* cm,
+                     const float* d_out, const float* keep, float* S, float* dh_ws, float* dc_ws, void* stream);
 /* Backward of one step: gates holds the activated gates on entry and
  * d loss / d pre-activation on exit; d_out [B][H] = grad of this step's output h
  * (NULL = 0); dh_rec / dc_rec = grads w.r.t. the next step's masked inputs

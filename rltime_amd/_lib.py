@@ -164,6 +164,9 @@ _SIGNATURES = {
     "mirl_lstm_seq_bwd_workspace_bytes": [_i32, _i32, _P(_i64)],
     "mirl_lstm_seq_bwd": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mirl_lstm_cell_bwd": [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
+    "mirl_lstm_ms_supported": [_i32, _i32, _i32, _i32],
+    "mirl_lstm_ms_fwd": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
+    "mirl_lstm_ms_bwd": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mirl_lstm_extras_supported": [_i64, _i64, _i32],
     "mirl_lstm_extras_add": [_i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
     "mirl_lstm_extras_wgrad_workspace_bytes": [_i64, _i64, _i32, _P(_i64)],

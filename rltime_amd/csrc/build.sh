@@ -7,7 +7,9 @@ HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="$HERE/../librltime_hip.so"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function ${MIRL_EXTRA_HIPCC_FLAGS:-}"
-UNITS="replay qmath c51 lstm lstm_seq lstm_extras convert nnops acting actnet conv_in conv_in_rows conv_mid gemm3 conv3 conv_wrw optim actor_critic act_mlp"
+UNITS="replay qmath c51 lstm lstm_seq lstm_multi lstm_extras convert nnops acting actnet conv_in conv_in_rows conv_mid gemm3 conv3 conv_wrw optim actor_critic act_mlp"
+# units compiled without packed-f32 VALU instructions (scalar v_add / v_mul / v_fma for their float4 arithmetic)
+NO_PK_F32="lstm_multi"
 newest_hdr=$(ls -t "$HERE"/*.h "$HERE"/*.hpp "$HERE"/../../include/*.h "$HERE/build.sh" | head -1)
 pids=()
 objs=()
@@ -15,7 +17,9 @@ for u in $UNITS; do
   [ -f "$HERE/$u.hip" ] || continue
   objs+=("$HERE/$u.o")
   if [ ! -f "$HERE/$u.o" ] || [ "$HERE/$u.hip" -nt "$HERE/$u.o" ] || [ "$newest_hdr" -nt "$HERE/$u.o" ]; then
-    "$HIPCC" $FLAGS -c "$HERE/$u.hip" -o "$HERE/$u.o" &
+    extra=""
+    case " $NO_PK_F32 " in *" $u "*) extra="-Xclang -target-feature -Xclang -packed-fp32-ops" ;; esac
+    "$HIPCC" $FLAGS $extra -c "$HERE/$u.hip" -o "$HERE/$u.o" &
     pids+=($!)
   fi
 done

@@ -22,6 +22,12 @@ columns are added by csrc/lstm_extras.hip), and the time loop over it is
 
 The weight gradients of W_ih and W_hh are one GEMM each over all timesteps after the
 backward sweep.
+
+lstm_sequence_multi is the multi-sample form (IQNPolicy(injection_layer=1): the quantile layer in front of the LSTM,
+merge mode "inner"): B stored states, N samples each, rows ordered (t, b, n).  All N samples of a sequence enter a step
+with the same merged state, so the recurrent product has B rows and only the cell runs over B N; the mean over the
+samples stays in one lane.  One launch per step and direction (csrc/lstm_multi.hip), ordered by the stream: no
+residency assumption, nothing for check_status() to report.
 """
 import ctypes as C
 import os
@@ -307,6 +313,62 @@ class _LSTMSequenceFromProjection(torch.autograd.Function):
         d_whh = gemm3.grad_weight(gates.reshape(T * B, G), hm[:T].reshape(T * B, H)) if ctx.needs_input_grad[1] else None
         d_wx = extras_wgrad(gates.reshape(T * B, G), extra) if extra is not None and ctx.needs_input_grad[7] else None
         return gates, d_whh, None, None, None, None, None, d_wx
+
+
+def multi_supported(T, B, N, H):
+    """Does csrc/lstm_multi.hip take T steps of B sequences with N samples each and H units?"""
+    return bool(lib.mirl_lstm_ms_supported(T, B, N, H))
+
+
+class _LSTMSequenceMulti(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, bias, h0, c0, keep, n_samples, track=True):
+        # x (T*B*N, I), rows (t, b, n); h0 / c0 (B, H); keep (T, B) from the UNREPEATED initials
+        T, B = keep.shape
+        N, H = n_samples, w_hh.shape[1]
+        dev = x.device
+        x = x.float()
+        w = w_hh.float().contiguous()
+        keep = keep.float().contiguous()
+        need_grad = track and any(ctx.needs_input_grad[:4])
+        gates = gemm3.linear_fwd(x, w_ih.float(), bias.float().contiguous())          # (T*B*N, 4H), one GEMM
+        out = torch.empty((T, B, N, H), dtype=torch.float32, device=dev)
+        hm = torch.empty((T + 1, B, H), dtype=torch.float32, device=dev)              # masked step inputs; row T = final state
+        cm = torch.empty((T + 1, B, H), dtype=torch.float32, device=dev)
+        h0, c0 = h0.float().contiguous(), c0.float().contiguous()                     # held until the launches are enqueued
+        check(lib.mirl_lstm_ms_fwd(T, B, N, H, ptr(gates), ptr(w), ptr(h0), ptr(c0), ptr(keep), ptr(out), ptr(hm), ptr(cm),
+                                   None, None, 1 if need_grad else 0, stream()), "mirl_lstm_ms_fwd")
+        if need_grad:
+            ctx.save_for_backward(x, w_ih, gates, cm, hm, keep, w)
+            ctx.n_samples = N
+        h_last, c_last = hm[T], cm[T]
+        ctx.mark_non_differentiable(h_last, c_last)
+        return out.view(T, B * N, H), h_last, c_last
+
+    @staticmethod
+    def backward(ctx, d_out, _dh, _dc):
+        x, w_ih, gates, cm, hm, keep, w = ctx.saved_tensors
+        T, B = keep.shape
+        N, H = ctx.n_samples, w.shape[1]
+        dev = gates.device
+        d_out = d_out.float().contiguous()
+        S = torch.empty((T, B, 4 * H), dtype=torch.float32, device=dev)               # sum over samples of d pre-activation
+        dh_ws = torch.empty((B, H), dtype=torch.float32, device=dev)
+        dc_ws = torch.empty((B, H), dtype=torch.float32, device=dev)
+        check(lib.mirl_lstm_ms_bwd(T, B, N, H, ptr(gates), ptr(w), ptr(cm), ptr(d_out), ptr(keep), ptr(S), ptr(dh_ws), ptr(dc_ws),
+                                   stream()), "mirl_lstm_ms_bwd")
+        dg = gates                                            # now d loss / d pre-activation (T*B*N, 4H)
+        d_x = gemm3.grad_input(dg, w_ih.float()) if ctx.needs_input_grad[0] else None
+        d_wih = gemm3.grad_weight(dg, x) if ctx.needs_input_grad[1] else None
+        d_whh = gemm3.grad_weight(S.reshape(T * B, 4 * H), hm[:T].reshape(T * B, H)) if ctx.needs_input_grad[2] else None
+        d_b = dg.sum(0) if ctx.needs_input_grad[3] else None
+        return d_x, d_wih, d_whh, d_b, None, None, None, None, None
+
+
+def lstm_sequence_multi(x, w_ih, w_hh, bias, h0, c0, keep, n_samples):
+    """x (T*B*N, I), rows ordered (t, b, n) -> (out (T, B*N, H), h_T (B, H), c_T (B, H)): every sample's output and the
+    merged (mean over the samples) final state; keep (T, B) = 1 - initials of the B sequences."""
+    return _LSTMSequenceMulti.apply(x, w_ih, w_hh, bias, h0, c0, keep, n_samples, torch.is_grad_enabled())
 
 
 def lstm_sequence_from_projection(gx, w_hh, h0, c0, keep, extra=None, w_x=None):

@@ -258,9 +258,18 @@ class LSTM(BaseModule):
         hx = hx.reshape(timesteps, batch // multi, self.num_units)[0]
         cx = cx.reshape(timesteps, batch // multi, self.num_units)[0]
         assert initials.shape == ((batch * timesteps) // multi,)
+        cell = self.lstm_cell
+        if x.is_cuda and multi > 1 and self.fused and self.multi_sample_merge_mode == "inner" and not n_extra:
+            # IQN before the LSTM: B states, B * multi rows; one HIP launch per step (csrc/lstm_multi.hip)
+            from .lstm_seq import lstm_sequence_multi, multi_supported
+            if multi_supported(timesteps, batch // multi, multi, self.num_units) and cell.weight_hh.data_ptr() % 16 == 0:
+                out, h_last, c_last = lstm_sequence_multi(
+                    x, w_ih, cell.weight_hh, cell.bias_ih + cell.bias_hh, hx, cx,
+                    (1 - initials).reshape(timesteps, batch // multi), multi)
+                self.last_state = (h_last.detach(), c_last.detach())
+                return out.reshape(timesteps * batch, self.num_units)
         if multi > 1:
             initials = initials.repeat_interleave(multi, dim=0)
-        cell = self.lstm_cell
         if x.is_cuda and multi == 1 and self.fused:
             # MI355X path: one GEMM + one fused HIP kernel per step (lstm_seq.py)
             from .lstm_seq import lstm_sequence
