@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.lstm_multi_restate import I, inputs as _inputs, loop64 as _loop64
+
 pytestmark = pytest.mark.gpu
 
 OUT_TOL = dict(rtol=1e-4, atol=2e-5)
@@ -14,35 +16,6 @@ GRAD_TOL = dict(rtol=1e-3, atol=2e-5)
 # one step / one sequence (idle waves, idle rows); odd N, ragged row tile; across a row tile at the recommended N = 8;
 # the default N = 32; the full K loops with S staged in chunks
 SHAPES = [(1, 1, 2, 16), (3, 5, 3, 32), (4, 17, 8, 64), (2, 33, 32, 128), (3, 16, 8, 512)]
-I = 24
-
-
-def _inputs(T, B, N, H):
-    g = torch.Generator().manual_seed(1000 * T + 10 * B + N)
-    p = dict(x=torch.randn(T * B * N, I, generator=g), w_ih=torch.randn(4 * H, I, generator=g) / I ** 0.5,
-             w_hh=torch.randn(4 * H, H, generator=g) / H ** 0.5, bias=torch.randn(4 * H, generator=g) * 0.1)
-    h0, c0 = torch.randn(B, H, generator=g) * 0.5, torch.randn(B, H, generator=g)
-    keep = (torch.rand(T, B, generator=g) > 0.25).float()
-    keep[0, 0] = keep[T // 2, B // 2] = 0.0                 # a reset at t = 0 and one in mid-sequence ...
-    keep[0, B - 1] = float(B > 1)                           # ... that the other rows do not share
-    up = torch.randn(T, B * N, H, generator=g)
-    return p, h0, c0, keep, up
-
-
-def _loop64(p, h0, c0, keep, N):
-    """The reference's inner-mode loop on float64 leaves: (out (T, B*N, H), h_T, c_T)."""
-    T, B = keep.shape
-    gx = (p["x"] @ p["w_ih"].t() + p["bias"]).reshape(T, B, N, -1)
-    h, c, out = h0.double(), c0.double(), []
-    for t in range(T):
-        k = keep[t].double().unsqueeze(1)
-        hin, cin = h * k, c * k
-        gi, gf, gg, go = (gx[t] + (hin @ p["w_hh"].t()).unsqueeze(1)).chunk(4, dim=-1)
-        cn = torch.sigmoid(gf) * cin.unsqueeze(1) + torch.sigmoid(gi) * torch.tanh(gg)
-        hn = torch.sigmoid(go) * torch.tanh(cn)
-        out.append(hn.reshape(B * N, -1))
-        h, c = hn.mean(1), cn.mean(1)
-    return torch.stack(out), h, c
 
 
 @pytest.mark.parametrize("T,B,N,H", SHAPES)
