@@ -657,6 +657,70 @@ def run_network64_pin():
 
 
 # --------------------------------------------------------------------------
+# The same pin for the layout with the quantile layer BEFORE the LSTM (the float64 anchor of
+# tests/test_iqn_pre_lstm_ab_gpu.py): the reference's IQNPolicy.create(..., injection_layer=1) — its LSTM runs B * N rows
+# over B stored states in merge mode "inner" (modules/lstm.py:83-116) — and Net64(injection_layer=1) on the same weights,
+# frames, stored state, initials and quantile fractions.  Beside the outputs and the gradients of a fixed linear
+# functional, the merged final state the reference leaves on its LSTM layer (lstm.py:120).
+# --------------------------------------------------------------------------
+def run_network64_pre_lstm_pin():
+    import io
+    import gym
+    from rltime.policies.torch.iqn import IQNPolicy
+    from oracle.network64 import Net64
+    layers = [{"type": "cnn", "args": {"layers": [{"filters": 16, "kernel": 4, "stride": 2}, {"filters": 16, "kernel": 3, "stride": 1}]}},
+              {"type": "lstm", "args": {"num_units": 32}}, {"type": "fc", "args": {"fc_size": 32}}]
+    T, B, A, N, H = 6, 5, 3, 3, 32
+    torch.manual_seed(242)
+    pol = IQNPolicy.create(model_config={"type": "sequential", "args": {"layer_configs": layers}},
+                           observation_space=gym.spaces.Box(0, 255, (3, 16, 16), dtype=np.uint8),
+                           action_space=gym.spaces.Discrete(A), cuda=False, dueling=True, embedding_dim=8, num_sampling_quantiles=N,
+                           injection_layer=1)
+    assert pol.quantile_layer.out_features == 400 and pol.model.layers[1].multi_sample_merge_mode == "inner"
+    f = io.BytesIO()
+    torch.save(pol.state_dict(), f)
+    g = torch.Generator().manual_seed(29)
+    x = torch.randint(0, 256, (T, B, 3, 16, 16), generator=g, dtype=torch.uint8)
+    hx, cx = torch.randn(T, B, H, generator=g) * 0.5, torch.randn(T, B, H, generator=g) * 0.5
+    initials = (torch.rand(T, B, generator=g) < 1.0 / 3.0).float()
+    initials[0] = 0.0                                                # the stored state of every sequence is consumed
+    assert 0.2 <= float(initials[1:].mean()) <= 0.5
+    weight = torch.randn(T * B, N, A, generator=g)
+    state = {"x": x.reshape(T * B, 3, 16, 16).numpy(), "layer0_state": {}, "layer2_state": {},
+             "layer1_state": {"hx": hx.reshape(T * B, H).numpy(), "cx": cx.reshape(T * B, H).numpy(),
+                              "initials": initials.reshape(T * B).numpy()}}
+    torch.manual_seed(277)
+    z, taus = pol.predict(state, T)                                  # the reference's float32 forward
+    assert z.shape == (T * B, N, A) and taus.shape == (T * B * N,)
+    last_h, last_c = (s.detach().clone() for s in pol.model.layers[1].last_state)      # merged over the N samples
+    assert last_h.shape == (B, H)
+    pol.zero_grad()
+    (z * weight).sum().backward()
+    ref_grads = {k: v.grad.detach().clone() for k, v in pol.named_parameters()}
+    net = Net64(pol.state_dict(), [2, 1], N, "cpu", injection_layer=1)
+    z64 = net.predict(x, hx[0], cx[0], initials, taus, T)
+    names = list(net.params())
+    g64 = dict(zip(names, torch.autograd.grad((z64 * weight.double()).sum(), [net.p[k] for k in names])))
+    worst = float((z64.detach().float() - z.detach()).abs().max() / z.detach().abs().max())
+    assert worst <= 1e-5, worst
+    for got, want in zip(net.last_state, (last_h, last_c)):
+        rel = float((got.float() - want).abs().max() / want.abs().max())
+        assert rel <= 1e-5, rel
+        worst = max(worst, rel)
+    for k, gr in ref_grads.items():
+        rel = float((g64[k].float() - gr).abs().max() / (gr.abs().max() + 1e-12))
+        assert rel <= 1e-4, (k, rel)
+        worst = max(worst, rel)
+    out = {"state_dict": np.frombuffer(f.getvalue(), dtype=np.uint8), "x": x.numpy(), "hx": hx.numpy(), "cx": cx.numpy(),
+           "initials": initials.numpy(), "taus": taus.numpy(), "weight": weight.numpy(), "z": z.detach().numpy(),
+           "last_hx": last_h.numpy(), "last_cx": last_c.numpy()}
+    for k, gr in ref_grads.items():
+        out["grad." + k] = gr.numpy()
+    np.savez_compressed(os.path.join(HERE, "network64_pre_lstm_pin.npz"), **out)
+    print("network64 pre-LSTM pin: reference float32 vs Net64 float64, worst relative deviation %.2e" % worst)
+
+
+# --------------------------------------------------------------------------
 # End-to-end pin: the reference's own training loop (DQN + LSTM + prioritized
 # sequence replay + burn-in + double-Q, CPU) on a scripted actor stream ->
 # per-learner-step loss / grad-norm series.  The GPU test replays the same
@@ -1121,6 +1185,7 @@ if __name__ == "__main__":
     run_qmath_cases()
     run_model_cases()
     run_network64_pin()
+    run_network64_pre_lstm_pin()
     run_e2e_case()
     run_e2e_iqn_case()
     run_e2e_iqn_case(E2E_IQN_WIDE, "e2e_iqn_lstm_per_wide.npz")

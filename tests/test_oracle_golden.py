@@ -134,3 +134,54 @@ def test_network64_is_pinned_to_the_reference_network():
         assert float((g.float() - want).abs().max() / (want.abs().max() + 1e-12)) <= 1e-4, k
         checked += 1
     assert checked == sum(1 for k in fx.files if k.startswith("grad.")) >= 12
+
+
+def test_network64_pre_lstm_is_pinned_to_the_reference_network():
+    """Net64(injection_layer=1) — the quantile layer before the LSTM, the float64 anchor of
+    tests/test_iqn_pre_lstm_ab_gpu.py — against the reference's own IQNPolicy.create(..., injection_layer=1) run in float32
+    on the CPU (fixture written by tests/golden/generate.py run_network64_pre_lstm_pin from the imported reference; it holds
+    the reference's FLOAT32 run): outputs and the merged final state the reference leaves on its LSTM layer within 1e-5,
+    gradients of a fixed linear functional within 1e-4 of the parameter's largest entry — the bars of the pin above.
+    Then the two conditions tests/test_iqn_pre_lstm_ab_gpu.py relies on, on Net64 alone at its seed and every (B, N) it runs:
+    no ReLU unit of the training pass within float32 rounding of zero, and a smallest double-Q margin of at least 1e-3."""
+    import io
+    from oracle.network64 import Net64
+    from tests import iqn_pre_lstm_case as case
+    fx = np.load(os.path.join(GOLDEN, "network64_pre_lstm_pin.npz"))
+    sd = torch.load(io.BytesIO(fx["state_dict"].tobytes()), map_location="cpu", weights_only=True)
+    T, B = fx["x"].shape[:2]
+    N = fx["z"].shape[1]
+    assert (T, B, N, fx["z"].shape[2]) == (6, 5, 3, 3) and fx["hx"].shape == (T, B, 32)
+    ini = torch.from_numpy(fx["initials"])
+    assert not ini[0].any() and 0.2 <= float(ini[1:].mean()) <= 0.5
+    net = Net64(sd, [2, 1], N, "cpu", injection_layer=1)
+    z64 = net.predict(torch.from_numpy(fx["x"]), torch.from_numpy(fx["hx"])[0], torch.from_numpy(fx["cx"])[0], ini,
+                      torch.from_numpy(fx["taus"]), T)
+    z = torch.from_numpy(fx["z"])
+    assert z64.shape == z.shape == (T * B, N, z.shape[2])
+    assert float((z64.detach().float() - z).abs().max() / z.abs().max()) <= 1e-5
+    for got, key in zip(net.last_state, ("last_hx", "last_cx")):
+        want = torch.from_numpy(fx[key])
+        assert got.shape == want.shape == (B, 32)
+        assert float((got.float() - want).abs().max() / want.abs().max()) <= 1e-5, key
+    names = list(net.params())
+    grads = torch.autograd.grad((z64 * torch.from_numpy(fx["weight"]).double()).sum(), [net.p[k] for k in names])
+    checked = 0
+    for k, g in zip(names, grads):
+        want = torch.from_numpy(fx["grad." + k])
+        assert float((g.float() - want).abs().max() / (want.abs().max() + 1e-12)) <= 1e-4, k
+        checked += 1
+    assert checked == sum(1 for k in fx.files if k.startswith("grad.")) == 18
+    # the default layout on the same weights is another network: the pin above does not hold by accident
+    other = Net64(sd, [2, 1], N, "cpu")
+    assert not other.pre_lstm
+    assert {b for b, _ in case.CASES} == set(case.BATCHES) == {5, 17} and case.CASES[:2] == ((5, 3), (17, 3))
+    for b, n in case.CASES:
+        ref, _, _ = case.float64_eval(b, n)
+        print("B = %d, N = %d: relu_near_zero %d, smallest double-Q margin %.3e" % (b, n, ref["relu_near_zero"], ref["min_double_q_margin"]))
+        assert ref["relu_near_zero"] == 0, (b, n, ref["relu_near_zero"])
+        assert ref["min_double_q_margin"] >= 1e-3, (b, n, ref["min_double_q_margin"])
+        assert ref["targets"].shape == (case.T * b, n) and ref["state_P"][0].shape == (b, case.H)
+        # the row-P state is zeroed exactly where a reset sits at row P (sequence 0 among them)
+        reset = case.batch(b)["initials"][case.P] != 0
+        assert reset[0] and torch.equal(ref["state_P"][0].abs().sum(1) == 0, reset)
