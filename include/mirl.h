@@ -1246,6 +1246,19 @@ int mirl_online_window_box(int32_t T, int32_t B, int32_t E, int32_t cap, int32_t
                            int32_t pol_pitch, float* returns, float* nsteps, float* target_masks, void* actions,
                            float* action_log_probs, float* values, void* states, void* target_states, int32_t action_words,
                            void* stream);
+/* mirl_online_append with vector actions: actions [E][action_words] and actions_ring [cap][E][action_words] — the layout
+ * mirl_online_window_box reads — are opaque 4-byte words (the float32 components of a Box action), word w of env e moved by
+ * lane w of its workgroup; everything else is mirl_online_append's, which is this entry with action_words = 1 — one kernel
+ * body.  1 <= action_words <= 16.                                                                                      */
+int mirl_online_append_box(int32_t E, int32_t cap, const int64_t* head_word, int32_t k, int64_t obs_bytes, const void* obs,
+                           const void* actions, const float* rewards, const uint8_t* dones, const float* policy,
+                           int64_t policy_pitch, int32_t state_f32, const float* state, const float* initials, void* obs_ring,
+                           void* actions_ring, float* rewards_ring, uint8_t* dones_ring, float* policy_ring, float* state_ring,
+                           float* initials_ring, int32_t action_words, void* stream);
+/* The episode statistics' share of a vector step with Box actions (where a Discrete space has its histogram,
+ * policy_trainer.py:148-160): sums[d] += sum_e double(actions[e][d]) for d < D, e ascending, and sums[D] += E, the
+ * transitions counted.  sums is float64 [D + 1] on the device; ONE workgroup, no atomics.  1 <= E <= 2^24, 1 <= D <= 16. */
+int mirl_box_action_sums(int32_t E, int32_t D, const float* actions, double* sums, void* stream);
 /* mirl_online_window_box for a recurrent policy: every stored next_state also carries its recurrent state, state_ring
  * [cap][E][state_f32] float32 (hx, cx of each recurrent layer, in the order the caller packed them) and its initials flag,
  * initials_ring [cap][E] float32 (1 = that next_state opens an episode).  For every batch row (t, b) both are read from
@@ -1322,6 +1335,28 @@ int mirl_act_mlp_ac_fwd(int32_t E, int32_t O, int32_t L, const int32_t* widths, 
                         const float* fcb, const float* outT, const float* outb, const double* eps, const double* expo,
                         double eps_min, uint64_t rng_seed, const uint64_t* rng_step, int32_t greedy, int32_t* actions,
                         float* policy, int32_t out_pitch, float* logits_out, void* stream);
+/* The same launch for an actor-critic MLP policy under a Normal head over a Box action of D components (kernel
+ * k_act_mlp<true, true>; policies/torch/distributions/normal.py:9-36): the trunk and the ONE dense output product exactly as
+ * mirl_act_mlp_ac_fwd with A = D — [mean_0 .. mean_{D-1} | value] = hid . outT + outb, outT [HID][D + 1] =
+ * [mean_layer.weight; critic.weight]^T — so raw_out equals that entry's logits_out on the same operands bit for bit.
+ * The standard-normal draws are made in the launch: lane p < ceil(D / 2) of env e takes the block
+ * philox_4x32(rng_seed ^ 0xB0C5, *rng_step, 8 e + p) and forms, in float64, u1 = ((word 0 >> 8) + 1) * 2^-24 in (0, 1],
+ * u2 = (word 1 >> 8) * 2^-24, r = sqrt(-2 log u1), eps[2p] = float32(r cos(2 pi u2)), eps[2p + 1] = float32(r sin(2 pi u2));
+ * an odd D drops the last sine, words 2 and 3 are unused.  24-bit uniforms: |eps| <= sqrt(48 ln 2) ~ 5.77.  Thread 0 of
+ * the env's workgroup then applies mirl_actor_head_normal's head (one statement of code for both, csrc/ac_head.hpp) to the
+ * LDS row and the draws with logstd [D]: feeding raw_out (pitch D + 1, values gathered from column D) and eps_out to
+ * mirl_actor_head_normal gives the same actions, log-probabilities and values, bit for bit.  There is no greedy mode.
+ * Outputs: actions float32 [E][D]; policy[e * out_pitch] = the log-probability, policy[e * out_pitch + 1] = the value
+ * (out_pitch >= 2); raw_out [E][D + 1] and eps_out [E][D], NULL allowed.  Nothing else reaches HBM, no atomics: a rerun on
+ * the same step word repeats to the bit.  Limits (mirl_act_mlp_normal_supported, host-only) = mirl_act_mlp_ac_supported's
+ * trunk with 1 <= D <= 16.  MIRL_ERR_ARG, nothing written: a shape outside the limits, a null operand (logstd and rng_step
+ * included), out_pitch < 2.                                                                                            */
+int mirl_act_mlp_normal_supported(int32_t E, int32_t O, int32_t L, const int32_t* widths, int32_t HID, int32_t D);
+int mirl_act_mlp_normal_fwd(int32_t E, int32_t O, int32_t L, const int32_t* widths, int32_t HID, int32_t D, const float* obs,
+                            const float* lw0T, const float* lb0, const float* lw1T, const float* lb1, const float* fcT,
+                            const float* fcb, const float* outT, const float* outb, const float* logstd, uint64_t rng_seed,
+                            const uint64_t* rng_step, float* actions, float* policy, int32_t out_pitch, float* raw_out,
+                            float* eps_out, void* stream);
 
 #ifdef __cplusplus
 }

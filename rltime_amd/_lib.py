@@ -232,6 +232,9 @@ _SIGNATURES = {
     "mirl_act_mlp_ac_supported": [_i32, _i32, _i32, _P(_i32), _i32, _i32],
     "mirl_act_mlp_ac_fwd": [_i32, _i32, _i32, _P(_i32), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64,
                             _u64, _vp, _i32, _vp, _vp, _i32, _vp, _vp],
+    "mirl_act_mlp_normal_supported": [_i32, _i32, _i32, _P(_i32), _i32, _i32],
+    "mirl_act_mlp_normal_fwd": [_i32, _i32, _i32, _P(_i32), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp,
+                                _vp, _vp, _i32, _vp, _vp, _vp],
     "mirl_bias_relu_rows": [_i64, _i32, _vp, _vp, _vp],
     "mirl_colsum_blocks": [_i64, _i32, _P(_i32)],
     "mirl_relu_bwd_bias_rows": [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
@@ -253,6 +256,9 @@ _SIGNATURES = {
     "mirl_actor_head_ac_rng": [_i32, _i32, _vp, _i64, _vp, _i64, _u64, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
     "mirl_online_append": [_i32, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                            _vp, _vp],
+    "mirl_online_append_box": [_i32, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                               _vp, _i32, _vp],
+    "mirl_box_action_sums": [_i32, _i32, _vp, _vp, _vp],
     "mirl_online_advance": [_vp, _i64, _vp],
     "mirl_online_window": [_i32, _i32, _i32, _i32, _i32, _f64, _f64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
                            _vp, _vp, _vp, _vp, _vp],

@@ -103,8 +103,14 @@ class Actor(ActingInterface):
         step (acting/fast_step.py; an MLP policy on float32 vector observations: acting/fast_mlp_step.FastMlpAcStep) where its
         shape is covered, instead of the generic device path.
         fused_mlp (the same config key): let an MLP DQN / IQN policy on float32 vector observations act on the fused MLP
-        step (acting/fast_mlp_step.py) where FastActingStep declines it."""
+        step (acting/fast_mlp_step.py) where FastActingStep declines it.
+        The attribute fused_normal (the same config key; train.create_actors sets it before the policy arrives): let an
+        actor-critic MLP policy under a Normal head over Box actions act on FastMlpNormalStep.  A switch of its own, as
+        fused_mlp is: fused_actor_critic alone keeps meaning the Categorical steps and declines a Box action space with its
+        reason."""
         self._fused_actor_critic = bool(fused_actor_critic)
+        self.fused_normal = False
+        self._ac_opted = False         # set with the policy (set_actor_policy)
         self._fused_mlp = bool(fused_mlp)
         self._fast_cls = None          # the fused step's class once a supports() query chose one (None: FastActingStep)
         self._vec_env = vec_env
@@ -143,8 +149,10 @@ class Actor(ActingInterface):
         self._reset_obs = obs
         # (actor-critic policies take the generic device path and its GraphedStep unless the actor opted in to the fused step)
         ac = hasattr(actor_policy, "actor_head_ac_raw")
-        self._fast = False if ac and not self._fused_actor_critic else None
-        if ac and self._fused_actor_critic and self._device_mode:
+        # the actor-critic opt-in that bears on this policy: fused_normal for a Normal head, fused_actor_critic for any
+        self._ac_opted = self._fused_actor_critic or (self.fused_normal and ac and actor_policy.has_normal_head())
+        self._fast = False if ac and not self._ac_opted else None
+        if ac and self._ac_opted and self._device_mode:
             self._use_graph = True         # the fused step is captured graphs throughout: the opt-in asks for them
         self._fast_cls = None
         if self._fused_mlp and self._device_mode and not ac and not self._use_graph and self._mlp_step_supported():
@@ -323,8 +331,11 @@ class Actor(ActingInterface):
         if self._fast is None:
             self._fast = (self._fast_cls or FastActingStep)(self, self._reset_obs, need_q=need_q)
             if self._tracker is None:
-                from .episode_tracker import EpisodeTracker
-                self._tracker = EpisodeTracker(self._num_envs, self._action_space.n, self._policy.device())
+                from .episode_tracker import BoxEpisodeTracker, EpisodeTracker
+                if hasattr(self._action_space, "n"):
+                    self._tracker = EpisodeTracker(self._num_envs, self._action_space.n, self._policy.device())
+                else:                   # Box actions (FastMlpNormalStep): the component sums instead of the histogram
+                    self._tracker = BoxEpisodeTracker(self._num_envs, int(np.prod(self._action_space.shape)), self._policy.device())
             self._fast.tracker = self._tracker
             if getattr(self, "_fast_restore", None) is not None:
                 self._fast.set_state(self._fast_restore)
@@ -348,7 +359,9 @@ class Actor(ActingInterface):
             if sink._h is None:
                 # (the on-policy history keeps the [log-probability | value] pair, a replay the q-values)
                 pf = (2 if fs.ac else self._action_space.n) if sink._keep_policy else 0
-                sink.configure(fs.example, self._num_envs, self._base_env_id, policy_f32=pf)
+                # (a Box action's trailing shape goes to the one sink that stores vector actions, the on-policy history)
+                box = {"action_shape": tuple(fs.actions.shape[1:])} if fs.actions.dim() > 1 else {}
+                sink.configure(fs.example, self._num_envs, self._base_env_id, policy_f32=pf, **box)
                 if getattr(sink, "_dedup", False) and fs.trusted_stack and not getattr(sink, "_acting_priority_init", False):
                     sink.prime_stack(self._reset_obs[0] if isinstance(self._reset_obs, (tuple, list)) else self._reset_obs)
             keep_policy = bool(sink._policy_f32)
@@ -403,7 +416,7 @@ class Actor(ActingInterface):
                     logging.getLogger().warning("fused acting step unavailable (%s); using the generic device path", e)
                     self._fast = False
             else:
-                if self._fused_actor_critic and hasattr(self._policy, "actor_head_ac_raw"):
+                if self._ac_opted and hasattr(self._policy, "actor_head_ac_raw"):
                     import logging
                     logging.getLogger().warning("fused acting step unavailable (%s); using the generic device path",
                                                 "this actor-critic policy / env shape is not covered: %s" % self._mlp_why_not)
@@ -474,13 +487,14 @@ class Actor(ActingInterface):
 
     def _mlp_step_supported(self):
         """The opt-ins' query (acting/fast_mlp_step.py), asked after FastActingStep.supports declined: fused_mlp for a DQN /
-        IQN policy, fused_actor_critic for an actor-critic one."""
-        from .fast_mlp_step import FastMlpAcStep, FastMlpStep
+        IQN policy, fused_actor_critic for an actor-critic one, fused_normal for one under a Normal head."""
+        from .fast_mlp_step import FastMlpAcStep, FastMlpNormalStep, FastMlpStep
         ac = hasattr(self._policy, "actor_head_ac_raw")
         self._mlp_why_not = None
-        if not (self._fused_actor_critic if ac else self._fused_mlp):
+        if not (self._ac_opted if ac else self._fused_mlp):
             return False
-        cls = FastMlpAcStep if ac else FastMlpStep
+        normal = ac and self.fused_normal and self._policy.has_normal_head()
+        cls = FastMlpStep if not ac else FastMlpNormalStep if normal else FastMlpAcStep
         self._mlp_why_not = cls.why_not(self)
         if self._mlp_why_not is None:
             self._fast_cls = cls

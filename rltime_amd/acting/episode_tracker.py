@@ -130,6 +130,11 @@ class BoxEpisodeTracker(EpisodeTracker):
         self.action_sums[:self.D] += actions_f32.reshape(self.E, self.D).sum(dim=0, dtype=torch.float64)
         self.action_sums[self.D] += self.E
 
+    def add_actions(self, actions_f32):
+        """The fused step's share of step() (acting/fast_mlp_step.FastMlpNormalStep, whose pre-step kernel does the episode
+        part): the same sums as ONE fixed launch on the step's static action buffer, capturable into a rollout graph."""
+        check(lib.mirl_box_action_sums(self.E, self.D, ptr(actions_f32), ptr(self.action_sums), stream()), "mirl_box_action_sums")
+
     def take_action_counts(self):
         return []
 

@@ -19,7 +19,9 @@ layer: a foreign observation is staged into the static input block) and `_body` 
 
 FastMlpAcStep is the same step for an actor-critic (A2C / PPO) MLP policy under a Categorical head: mirl_act_mlp_ac_fwd as
 the one launch, the [log-probability | value] block where the q-values are, the on-policy history as the sink
-(Actor(fused_actor_critic=True), the same config key)."""
+(Actor(fused_actor_critic=True), the same config key).  FastMlpNormalStep is that step under a Normal head over a Box action
+space (mountaincar_continuous_ppo): mirl_act_mlp_normal_fwd, the standard-normal draws inside the launch, float32 [E, D]
+actions appended by mirl_online_append_box."""
 import ctypes as C
 import os
 
@@ -124,6 +126,15 @@ class FastMlpStep(FastActingStep):
         step_device, epsilon-greedy or greedy, and a shape mirl_act_mlp_supported takes."""
         return FastMlpStep.why_not(actor) is None
 
+    @staticmethod
+    def _action_count(actor):
+        """A: the head's outputs beside the value (FastMlpNormalStep: the components of a Box action)."""
+        return actor._action_space.n
+
+    def _new_actions(self):
+        """The static action buffer the head writes and the env reads (FastMlpNormalStep: float32 [E, D])."""
+        return torch.zeros(self.E, dtype=torch.int32, device=self.dev)
+
     def __init__(self, actor, obs0, need_q=True):
         self.actor = actor
         pol = self.pol = actor._policy
@@ -135,7 +146,7 @@ class FastMlpStep(FastActingStep):
         self.iqn = hasattr(pol, "num_sampling_quantiles")
         dev = self.dev = pol.device()
         E = self.E = actor._num_envs
-        A = self.A = actor._action_space.n
+        A = self.A = self._action_count(actor)
         self.shape = self._shape(pol, (self.leading, self.fc, self.dueling), E, A)
         _, self.O, self.L, self.widths, self.N, self.D, self.HID, self.NO, _ = self.shape
         # no recurrent layer, no extras: the inherited pre-step, ingest and resume code see empty blocks
@@ -152,7 +163,7 @@ class FastMlpStep(FastActingStep):
         self.initials = torch.ones(E, **f32)
         self.rewards = torch.zeros(E, **f32)
         self.dones = torch.ones(E, dtype=torch.uint8, device=dev)
-        self.actions = torch.zeros(E, dtype=torch.int32, device=dev)
+        self.actions = self._new_actions()
         self.qvalues = torch.zeros((E, 2 if self.ac else A), **f32)      # actor-critic: [log-probability | value]
         self.eps = torch.zeros((), dtype=torch.float64, device=dev)
         self.rng_step = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -258,15 +269,20 @@ class FastMlpAcStep(FastMlpStep):
     @staticmethod
     def _mlp_parts(pol):
         """-> (leading Linears, the last FC's Linear, False), else a string that says what is in the way."""
+        return FastMlpAcStep._ac_parts(pol, pol.actor.logits_layer, "logits layer")
+
+    @staticmethod
+    def _ac_parts(pol, head, name):
+        """_mlp_parts for the head Linear `head` (the logits layer, or FastMlpNormalStep's mean layer) beside the critic."""
         parts = FastMlpStep._fc_stack(pol)
         if isinstance(parts, str):
             return parts
         last = parts[-1]
-        logits, critic = pol.actor.logits_layer, pol.critic
-        if logits.in_features != last.out_features or critic.in_features != last.out_features or critic.out_features != 1:
-            return "the logits layer and the critic do not both read the last FC module"
-        if logits.bias is None or critic.bias is None:
-            return "the logits layer or the critic has no bias"
+        critic = pol.critic
+        if head.in_features != last.out_features or critic.in_features != last.out_features or critic.out_features != 1:
+            return "the %s and the critic do not both read the last FC module" % name
+        if head.bias is None or critic.bias is None:
+            return "the %s or the critic has no bias" % name
         return parts[:-1], last, False
 
     @staticmethod
@@ -324,12 +340,16 @@ class FastMlpAcStep(FastMlpStep):
     def set_need_q(self, need_q):
         pass                                             # the [log-probability | value] pair is always evaluated
 
+    def _head_linear(self):
+        """The Linear whose rows stand beside the critic's in outT (FastMlpNormalStep: the Normal head's mean layer)."""
+        return self.pol.actor.logits_layer
+
     def refresh(self):
-        pol, A = self.pol, self.A
+        pol, A, head = self.pol, self.A, self._head_linear()
         with torch.no_grad():
             dst = [w for w in self.lwT] + [self.fcT, self.fc_b, self.outT[:, :A], self.outT[:, A:], self.out_b[:A], self.out_b[A:]]
-            src = [lin.weight.t() for lin in self.leading] + [self.fc.weight.t(), self.fc.bias, pol.actor.logits_layer.weight.t(),
-                                                              pol.critic.weight.t(), pol.actor.logits_layer.bias, pol.critic.bias]
+            src = [lin.weight.t() for lin in self.leading] + [self.fc.weight.t(), self.fc.bias, head.weight.t(),
+                                                              pol.critic.weight.t(), head.bias, pol.critic.bias]
             for d, s in zip(dst, src):
                 d.copy_(s.detach())
 
@@ -344,3 +364,100 @@ class FastMlpAcStep(FastMlpStep):
             ptr(self.fcT), ptr(self.fc_b), ptr(self.outT), ptr(self.out_b),
             ptr(self.eps) if remap else None, ptr(self.expo) if remap else None, self.eps_min, self.rng_seed, ptr(self.rng_step),
             0, ptr(self.actions), ptr(self.qvalues), 2, None, stream()), "mirl_act_mlp_ac_fwd")
+
+
+class FastMlpNormalStep(FastMlpAcStep):
+    """The same step for an actor-critic MLP policy under a Normal head over a Box action space (mountaincar_continuous_ppo:
+    2 -> 64 -> 64 -> [mean | value]), under the same opt-in.
+
+    The one launch is mirl_act_mlp_normal_fwd (csrc/act_mlp.hip k_act_mlp<true, true>): the trunk of the Categorical form, ONE
+    product [means | value] over outT = [mean_layer.weight; critic.weight]^T, the standard-normal draws made INSIDE the launch
+    (Philox + Box-Muller, keyed by the step word like every other draw of the step: no torch.randn launch, and a captured
+    rollout carries its own randomness) and k_actor_head_normal's head on the LDS row.  `actions` is a static float32 [E, D]
+    buffer the env reads (bind_actions) and the on-policy history appends as D words per transition (mirl_online_append_box).
+    The episode statistics: the pre-step kernel counts rewards and lengths and takes no actions (its histogram is a Discrete
+    space's); the component sums of the actions just executed stay on the device through ONE small launch after it
+    (BoxEpisodeTracker.add_actions, mirl_box_action_sums) — a vector step is env step, pre-step, action sums, append, network:
+    FIVE launches, five nodes per step of a captured rollout.  The pre-step, the sink protocol, the rollout capture, the
+    MIRL_ROLLOUT_* switches and the step word are inherited unchanged."""
+
+    @staticmethod
+    def _action_count(actor):
+        return int(np.prod(actor._action_space.shape))
+
+    def _new_actions(self):
+        return torch.zeros((self.E, self.A), dtype=torch.float32, device=self.dev)
+
+    @staticmethod
+    def _mlp_parts(pol):
+        """-> (leading Linears, the last FC's Linear, False), else a string that says what is in the way."""
+        return FastMlpAcStep._ac_parts(pol, pol.actor.mean_layer, "mean layer")
+
+    @staticmethod
+    def why_not(actor, pol=None):
+        """None when the step covers this actor's policy and env, else the reason as a string."""
+        pol = pol if pol is not None else actor._policy
+        try:
+            if not hasattr(pol, "actor_head_ac_raw") or not pol.has_normal_head():
+                return "the policy is not an actor-critic policy with a Normal head"
+            if pol.why_not_on_device() is not None:
+                return pol.why_not_on_device()
+            if not getattr(pol, "is_cuda", lambda: False)():
+                return "the policy is not on the GPU"
+            if getattr(actor, "_ac_eps_remap", False):
+                return "an epsilon remap redraws a Discrete action: there is none for a Box action space"
+            parts = FastMlpNormalStep._mlp_parts(pol)
+            if isinstance(parts, str):
+                return parts
+            if pol.model.layer_pre_processors:
+                return "the model has layer pre-processors"
+            space = actor._vec_env.observation_space
+            if hasattr(space, "spaces") or str(getattr(space, "dtype", "")) != "float32" or len(tuple(space.shape)) != 1:
+                return "the observation space is not a float32 vector"
+            if not (hasattr(actor._vec_env, "step_device") and hasattr(actor._vec_env, "bind_actions")):
+                return "the env does not step on the device from a bound action buffer"
+            D = FastMlpNormalStep._action_count(actor)
+            shape = FastMlpAcStep._shape(pol, parts, actor._num_envs, D)
+            if shape[1] != int(space.shape[0]):
+                return "the first layer does not read the observation"
+            if pol.actor.mean_layer.out_features != D or pol.actor.logstd.numel() != D:
+                return "the mean layer does not have one output per action component"
+            if not lib.mirl_act_mlp_normal_supported(*FastMlpAcStep._ac_args(shape)):
+                return "mirl_act_mlp_normal_supported refuses the shape (E, O, L, widths, HID, D) = %r" % (
+                    shape[:3] + (list(shape[3])[:shape[2]], shape[6], shape[8]),)
+            return None
+        except Exception as e:                           # a policy this code does not know: not covered
+            return "%s: %s" % (type(e).__name__, e)
+
+    @staticmethod
+    def supports(actor):
+        return FastMlpNormalStep.why_not(actor) is None
+
+    def _head_linear(self):
+        return self.pol.actor.mean_layer
+
+    def refresh(self):
+        super().refresh()
+        if not hasattr(self, "logstd"):                  # (the constructor's first refresh)
+            self.logstd = torch.empty(self.A, dtype=torch.float32, device=self.dev)
+        self.logstd.copy_(self.pol.actor.logstd.detach().reshape(-1))
+
+    def _pre_args(self, tr, row, clip):
+        """The pre-step counts no actions (A = 0, no action pointer): its histogram is a Discrete space's."""
+        a = super()._pre_args(tr, row, clip)
+        return a[:1] + (0, None) + a[3:]
+
+    def _pre(self, rewards, dones_u8, track=True, clip=False, row=None):
+        super()._pre(rewards, dones_u8, track=track, clip=clip, row=row)
+        if track and self.tracker is not None:
+            self.tracker.add_actions(self.actions)       # still the actions just executed: the head overwrites them later
+
+    def _body(self):
+        """The whole network, the draws and the Normal head: reads x_in, writes actions and the [log-probability | value] block."""
+        lead = self.leading
+        check(lib.mirl_act_mlp_normal_fwd(
+            *self._ac_args(self.shape), ptr(self.x_in),
+            ptr(self.lwT[0]) if len(lead) >= 1 else None, ptr(lead[0].bias) if len(lead) >= 1 else None,
+            ptr(self.lwT[1]) if len(lead) >= 2 else None, ptr(lead[1].bias) if len(lead) >= 2 else None,
+            ptr(self.fcT), ptr(self.fc_b), ptr(self.outT), ptr(self.out_b), ptr(self.logstd), self.rng_seed, ptr(self.rng_step),
+            ptr(self.actions), ptr(self.qvalues), 2, None, None, stream()), "mirl_act_mlp_normal_fwd")

@@ -42,6 +42,25 @@
 // of k_actor_head_ac_rng (ac_head.hpp: one statement for both) on the LDS row, by thread 0.  One row: the LDS block is
 // 4.6 K floats + W + HID + A + 1, under 22 KB at every limit; the occupancy and latency reasoning above carries over unchanged
 // (E workgroups on 256 CUs, a chain of three or four products).
+//
+// The Normal form (mirl_act_mlp_normal_fwd, k_act_mlp<true, true>; mountaincar_continuous_ppo: 2 -> 64 -> 64 -> [mean | value],
+// rltime/policies/torch/distributions/normal.py:9-36) is the actor-critic trunk again — N = 1, D_quant = 0, every product
+// dense_rb<1>, ONE dense output product [mean_0 .. mean_{D-1} | value] over outT = [mean_layer.weight; critic.weight]^T
+// (HID x (D + 1), no zero block), the row left in LDS — under a tail that samples a Box action of D <= 16 components:
+//   draws    lanes p < ceil(D / 2) of the first wave take ONE Philox4x32-10 block each, keyed (seed ^ 0xB0C5, *step, 8 e + p):
+//            a key of its own beside the Categorical head's (seed, *step, e) and the quantile draw's seed ^ 0x7A5, and 8 lanes
+//            per env so that no two envs share a block.  Words 0 and 1 become two standard normals by Box-Muller in float64:
+//            u1 = ((w0 >> 8) + 1) / 2^24 in (0, 1], u2 = (w1 >> 8) / 2^24 in [0, 1), r = sqrt(-2 log u1),
+//            eps[2p] = float32(r cos(2 pi u2)), eps[2p + 1] = float32(r sin(2 pi u2)) — one rounding each; an odd D drops the
+//            last sine, words 2 and 3 are never used.  The uniforms have 24 bits: u1 >= 2^-24 bounds |eps| by
+//            sqrt(48 ln 2) ~ 5.77 (a float32 torch.randn reaches about 5.4 in 2^24 draws: the tails are cut where nothing
+//            is observed in a run).  The draws are made at the top of the kernel, while the observation load is in flight,
+//            into the 64-float LDS row the quantile fractions have in the Q-learning form (unused at D_quant = 0).
+//   head     after the last product's barrier thread 0 applies normal_head_row (ac_head.hpp: ONE statement for this tail and
+//            k_actor_head_normal) to the LDS row and the LDS draws, components in ascending d.
+// HBM sees the float32 actions [E][D], the [log-probability | value] block, and for tests the raw row and the draws.
+// The draw inside the launch removes the generic path's torch.randn launch and lets a captured rollout carry its own
+// randomness.  LDS, occupancy and latency: the actor-critic form's.
 #include "common.hpp"
 #include "philox.hpp"
 #include "ac_head.hpp"
@@ -58,6 +77,8 @@ struct ActMlpArgs {
   int32_t* actions; float* qvalues; float* taus_out;
   // the actor-critic tail (k_act_mlp<true>): qvalues is the [log-probability | value] block, out_pitch floats per env
   float* logits_out; int greedy, out_pitch;
+  // the Normal tail (k_act_mlp<true, true>): A is the number of action components, logits_out the raw [means | value] row
+  const float* logstd; float* box_actions; float* eps_out;
   int E, O, L, w0, w1, W, N, D, HID, NO, A, hid_run, no_run, CH, has_val;
 };
 
@@ -130,9 +151,14 @@ __device__ __forceinline__ void dense_rb(const float* in, int in_pitch, int R, i
 // AC = false: the Q-learning tail below (dueling combine, mean over the quantile rows, first maximum, epsilon-greedy).
 // AC = true: the actor-critic tail — the one row [logits | value] goes through ac_head_row (ac_head.hpp), the statement
 // k_actor_head_ac and k_actor_head_ac_rng share.  Everything before the tail is the same code for both.
-template <bool AC>
+// AC = true, NORMAL = true: the Normal tail — the draws at the top (below), normal_head_row on the row [means | value].
+constexpr uint64_t kNormalDrawTag = 0xB0C5ull;
+constexpr double kTwoPi = 6.283185307179586;      // 2 pi, correctly rounded
+
+template <bool AC, bool NORMAL = false>
 __global__ void __launch_bounds__(256)
 k_act_mlp(ActMlpArgs a) {
+  static_assert(AC || !NORMAL, "the Normal tail sits on the actor-critic trunk");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* fa = lds;                       // [256]
   float* fb = fa + 256;                  // [256]
@@ -146,7 +172,29 @@ k_act_mlp(ActMlpArgs a) {
   const bool quant = a.D > 0;
 
   // the observation and the quantile fractions
-  if (tid < a.O) fa[tid] = a.obs[(int64_t)e * a.O + tid];
+  if constexpr (NORMAL) {
+    // the Normal tail's draws, under the observation's load: lane p makes components 2p and 2p + 1 of env e (file header)
+    const float ob = tid < a.O ? a.obs[(int64_t)e * a.O + tid] : 0.f;
+    const int D = a.A;
+    if (2 * tid < D) {
+      uint32_t rn[4];
+      philox_4x32(a.seed ^ kNormalDrawTag, *a.step, (uint32_t)e * 8u + (uint32_t)tid, rn);
+      const double u1 = ((double)(rn[0] >> 8) + 1.0) * (1.0 / 16777216.0);
+      const double u2 = (double)(rn[1] >> 8) * (1.0 / 16777216.0);
+      const double rad = sqrt(-2.0 * log(u1)), ang = kTwoPi * u2;
+      const float z0 = (float)(rad * cos(ang));
+      tau[2 * tid] = z0;
+      if (a.eps_out) a.eps_out[(int64_t)e * D + 2 * tid] = z0;
+      if (2 * tid + 1 < D) {
+        const float z1 = (float)(rad * sin(ang));
+        tau[2 * tid + 1] = z1;
+        if (a.eps_out) a.eps_out[(int64_t)e * D + 2 * tid + 1] = z1;
+      }
+    }
+    if (tid < a.O) fa[tid] = ob;
+  } else {
+    if (tid < a.O) fa[tid] = a.obs[(int64_t)e * a.O + tid];
+  }
   if (quant && tid < a.N) {
     const int m = e * a.N + tid;
     float t;
@@ -204,7 +252,19 @@ k_act_mlp(ActMlpArgs a) {
     }
   }
 
-  if constexpr (AC) {
+  if constexpr (NORMAL) {
+    // k_actor_head_normal (actor_critic.hip) on the LDS row [D means | value] and the LDS draws: the raw row for whoever
+    // asked, then thread 0 forms the action and writes it with the policy pair (the last product's barrier also covers
+    // the draws, written before the first one)
+    const int D = a.A, NO = a.NO;
+    if (a.logits_out && tid < NO) a.logits_out[(int64_t)e * NO + tid] = outs[tid];
+    if (tid != 0) return;
+    float lp;
+    normal_head_row(outs, D, a.logstd, tau, a.box_actions + (int64_t)e * D, &lp);
+    a.qvalues[(int64_t)e * a.out_pitch] = lp;
+    a.qvalues[(int64_t)e * a.out_pitch + 1] = outs[D];
+    return;
+  } else if constexpr (AC) {
     // k_actor_head_ac_rng (actor_critic.hip) on the LDS row [A logits | value]: the raw row for whoever asked, then thread 0
     // draws the block (seed, *step, e), samples (or takes the first maximum) and writes the action and the policy pair
     const int A = a.A, NO = a.NO;
@@ -321,6 +381,7 @@ extern "C" int mirl_act_mlp_fwd(int32_t E, int32_t O, int32_t L, const int32_t* 
   a.eps = eps; a.expo = expo; a.eps_min = eps_min; a.seed = seed; a.step = rng_step;
   a.actions = actions; a.qvalues = qvalues; a.taus_out = D > 0 ? taus_out : nullptr;
   a.logits_out = nullptr; a.greedy = 0; a.out_pitch = 0;
+  a.logstd = nullptr; a.box_actions = nullptr; a.eps_out = nullptr;
   a.E = E; a.O = O; a.L = L; a.w0 = L >= 1 ? widths[0] : 0; a.w1 = L >= 2 ? widths[1] : 0;
   a.W = L ? widths[L - 1] : O; a.N = N; a.D = D; a.HID = HID; a.NO = NO; a.A = A;
   // need_q = 0 under a dueling head: the value stream's hidden units and its output column are not evaluated (out_w is
@@ -341,6 +402,28 @@ extern "C" int mirl_act_mlp_fwd(int32_t E, int32_t O, int32_t L, const int32_t* 
 }
 
 // ---- the actor-critic form: the same trunk, [logits | value] as the one output product, the sampling head on its row -------
+// what both actor-critic forms hand the kernel: the trunk's operands, N = 1, D_quant = 0, NO = A + 1 in one dense product, the
+// policy block; every tail-specific field cleared (A: actions of a Categorical head, components of a Normal one)
+static void fill_ac_trunk(ActMlpArgs& a, int32_t E, int32_t O, int32_t L, const int32_t* widths, int32_t HID, int32_t A, const float* obs,
+                          const float* lw0T, const float* lb0, const float* lw1T, const float* lb1, const float* fcT, const float* fcb,
+                          const float* outT, const float* outb, uint64_t rng_seed, const uint64_t* rng_step, float* policy,
+                          int32_t out_pitch, float* raw_out) {
+  a.obs = obs; a.lwT[0] = lw0T; a.lb[0] = lb0; a.lwT[1] = lw1T; a.lb[1] = lb1;
+  a.freq = nullptr; a.taus = nullptr; a.wqT = nullptr; a.bq = nullptr; a.fcT = fcT; a.fcb = fcb; a.outT = outT; a.outb = outb;
+  a.eps = nullptr; a.expo = nullptr; a.eps_min = 0.0; a.seed = rng_seed; a.step = rng_step;
+  a.actions = nullptr; a.qvalues = policy; a.taus_out = nullptr;
+  a.logits_out = raw_out; a.greedy = 0; a.out_pitch = out_pitch;
+  a.logstd = nullptr; a.box_actions = nullptr; a.eps_out = nullptr;
+  a.E = E; a.O = O; a.L = L; a.w0 = L >= 1 ? widths[0] : 0; a.w1 = L >= 2 ? widths[1] : 0;
+  a.W = L ? widths[L - 1] : O; a.N = 1; a.D = 0; a.HID = HID; a.NO = A + 1; a.A = A;
+  a.hid_run = HID; a.no_run = A + 1; a.has_val = 0;
+  a.CH = 1;                                // one row: 4.6 K floats + W + HID + A + 1, under 22 KB at every limit
+}
+
+static double ac_weight_floats(const ActMlpArgs& a) {
+  return (double)a.O * a.w0 + (double)a.w0 * a.w1 + (double)a.W * a.HID + (double)a.HID * a.NO;
+}
+
 extern "C" int mirl_act_mlp_ac_supported(int32_t E, int32_t O, int32_t L, const int32_t* widths, int32_t HID, int32_t A) {
   return mirl_act_mlp_supported(E, O, L, widths, 1, 0, HID, A + 1, A);
 }
@@ -357,20 +440,43 @@ extern "C" int mirl_act_mlp_ac_fwd(int32_t E, int32_t O, int32_t L, const int32_
       (L >= 2 && (!lw1T || !lb1)))
     return fail(MIRL_ERR_ARG, "act_mlp_ac_fwd: null operand (the step word is required, also with greedy)");
   ActMlpArgs a;
-  a.obs = obs; a.lwT[0] = lw0T; a.lb[0] = lb0; a.lwT[1] = lw1T; a.lb[1] = lb1;
-  a.freq = nullptr; a.taus = nullptr; a.wqT = nullptr; a.bq = nullptr; a.fcT = fcT; a.fcb = fcb; a.outT = outT; a.outb = outb;
-  a.eps = eps; a.expo = expo; a.eps_min = eps_min; a.seed = rng_seed; a.step = rng_step;
-  a.actions = actions; a.qvalues = policy; a.taus_out = nullptr;
-  a.logits_out = logits_out; a.greedy = greedy; a.out_pitch = out_pitch;
-  a.E = E; a.O = O; a.L = L; a.w0 = L >= 1 ? widths[0] : 0; a.w1 = L >= 2 ? widths[1] : 0;
-  a.W = L ? widths[L - 1] : O; a.N = 1; a.D = 0; a.HID = HID; a.NO = A + 1; a.A = A;
-  a.hid_run = HID; a.no_run = A + 1; a.has_val = 0;
-  a.CH = 1;                                // one row: 4.6 K floats + W + HID + A + 1, under 22 KB at every limit
+  fill_ac_trunk(a, E, O, L, widths, HID, A, obs, lw0T, lb0, lw1T, lb1, fcT, fcb, outT, outb, rng_seed, rng_step, policy, out_pitch,
+                logits_out);
+  a.eps = eps; a.expo = expo; a.eps_min = eps_min;
+  a.actions = actions; a.greedy = greedy;
   const size_t lds = 4 * (size_t)act_mlp_lds_floats(a.W, 1, 0, HID, A + 1, a.CH);
   hipStream_t st = (hipStream_t)stream;
-  const double wfloats = (double)O * a.w0 + (double)a.w0 * a.w1 + (double)a.W * HID + (double)HID * (A + 1);
-  ProfScope ps("k_act_mlp_ac", 4.0 * (wfloats + (double)E * (O + 3 + (logits_out ? A + 1 : 0))), st);
+  ProfScope ps("k_act_mlp_ac", 4.0 * (ac_weight_floats(a) + (double)E * (O + 3 + (logits_out ? A + 1 : 0))), st);
   hipLaunchKernelGGL(k_act_mlp<true>, dim3(E), dim3(256), lds, st, a);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
+// ---- the Normal form: the actor-critic trunk, [means | value] as the one output product, draws and head in the launch ---------
+extern "C" int mirl_act_mlp_normal_supported(int32_t E, int32_t O, int32_t L, const int32_t* widths, int32_t HID, int32_t D) {
+  if (D < 1 || D > kMaxBoxDims) return 0;
+  return mirl_act_mlp_supported(E, O, L, widths, 1, 0, HID, D + 1, D);
+}
+
+extern "C" int mirl_act_mlp_normal_fwd(int32_t E, int32_t O, int32_t L, const int32_t* widths, int32_t HID, int32_t D, const float* obs,
+                                       const float* lw0T, const float* lb0, const float* lw1T, const float* lb1, const float* fcT,
+                                       const float* fcb, const float* outT, const float* outb, const float* logstd, uint64_t rng_seed,
+                                       const uint64_t* rng_step, float* actions, float* policy, int32_t out_pitch, float* raw_out,
+                                       float* eps_out, void* stream) {
+  if (!mirl_act_mlp_normal_supported(E, O, L, widths, HID, D))
+    return fail(MIRL_ERR_ARG, "act_mlp_normal_fwd: unsupported shape (O <= 64, L <= 2 layers of <= 256, HID <= 512, 1 <= D <= 16)");
+  if (out_pitch < 2) return fail(MIRL_ERR_ARG, "act_mlp_normal_fwd: out_pitch >= 2");
+  if (!obs || !fcT || !fcb || !outT || !outb || !logstd || !rng_step || !actions || !policy || (L >= 1 && (!lw0T || !lb0)) ||
+      (L >= 2 && (!lw1T || !lb1)))
+    return fail(MIRL_ERR_ARG, "act_mlp_normal_fwd: null operand (logstd and the step word are required)");
+  ActMlpArgs a;
+  fill_ac_trunk(a, E, O, L, widths, HID, D, obs, lw0T, lb0, lw1T, lb1, fcT, fcb, outT, outb, rng_seed, rng_step, policy, out_pitch,
+                raw_out);
+  a.logstd = logstd; a.box_actions = actions; a.eps_out = eps_out;
+  const size_t lds = 4 * (size_t)act_mlp_lds_floats(a.W, 1, 0, HID, D + 1, a.CH);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps("k_act_mlp_normal", 4.0 * (ac_weight_floats(a) + (double)E * (O + D + 2 + (raw_out ? D + 1 : 0) + (eps_out ? D : 0)) + D), st);
+  hipLaunchKernelGGL((k_act_mlp<true, true>), dim3(E), dim3(256), lds, st, a);
   MIRL_LAUNCH_CHECK();
   return MIRL_OK;
 }

@@ -47,37 +47,30 @@ __global__ __launch_bounds__(64) void k_actor_head_ac_rng(int E, int A, const fl
 }
 
 // ---- 1b. the Normal (continuous) head: independent Gaussians over a Box action, state-independent log-std ----------------
-// (policies/torch/distributions/normal.py:9-36).  The pieces the head and the loss share, the SAME sequence of operations in
-// both: component d of an action a (float32) under N(mean_d, exp(logstd_d)) contributes
-//   -(a_d - mean_d)^2 / (2 exp(2 logstd_d)) - logstd_d - log(2 pi) / 2
-// to the joint log-probability, the contributions added in ascending d and the sum rounded once to float32.
-constexpr int kMaxBoxDims = 16;
-constexpr double kHalfLog2Pi = 0.9189385332046727;      // log(2 pi) / 2, correctly rounded
-
-__device__ inline double normal_log_prob_term(double a, double mean, double logstd) {
-  const double diff = a - mean;
-  return -(diff * diff) / (2.0 * exp(2.0 * logstd)) - logstd - kHalfLog2Pi;
-}
-
-// One thread per env.  a_d = float32(mean_d + exp(logstd_d) eps_d) with eps the caller's standard-normal draws (the kernel
-// is deterministic); the log-probability is that of the ROUNDED action — torch evaluates log_prob of the sampled float32
-// tensor, and the learner later sees that tensor.
+// One thread per env on normal_head_row (ac_head.hpp: the row's arithmetic, kMaxBoxDims, normal_log_prob_term — shared with
+// the loss below and with the fused MLP acting step, csrc/act_mlp.hip); eps are the caller's standard-normal draws.
 __global__ __launch_bounds__(64) void k_actor_head_normal(int E, int D, const float* __restrict__ mean, long pitch,
                                                           const float* __restrict__ logstd, const float* __restrict__ values,
                                                           const float* __restrict__ eps, float* __restrict__ actions,
                                                           float* __restrict__ logp, float* __restrict__ values_out, int out_pitch) {
   const int e = blockIdx.x * 64 + threadIdx.x;
   if (e >= E) return;
-  const float* m = mean + (long)e * pitch;
-  double lp = 0.0;
-  for (int d = 0; d < D; ++d) {
-    const double ls = (double)logstd[d];
-    const float a = (float)((double)m[d] + exp(ls) * (double)eps[(long)e * D + d]);
-    actions[(long)e * D + d] = a;
-    lp += normal_log_prob_term((double)a, (double)m[d], ls);
-  }
-  logp[(long)e * out_pitch] = (float)lp;
+  float lp;
+  normal_head_row(mean + (long)e * pitch, D, logstd, eps + (long)e * D, actions + (long)e * D, &lp);
+  logp[(long)e * out_pitch] = lp;
   values_out[(long)e * out_pitch] = values[e];
+}
+
+// What the episode statistics keep for a Box action space where a Discrete one has its histogram: sums[d] += sum_e
+// actions[e][d] in float64, e ascending, and sums[D] += E (the transitions counted).  ONE workgroup, thread d owns component
+// d: no atomics, a rerun repeats to the bit.
+__global__ __launch_bounds__(64) void k_box_action_sums(int E, int D, const float* __restrict__ actions, double* __restrict__ sums) {
+  const int d = threadIdx.x;
+  if (d > D) return;
+  if (d == D) { sums[D] += (double)E; return; }
+  double s = 0.0;
+  for (int e = 0; e < E; ++e) s += (double)actions[(long)e * D + d];
+  sums[d] += s;
 }
 
 // ---- 2. the on-policy window ---------------------------------------------------------------------------------------
@@ -171,9 +164,10 @@ __global__ __launch_bounds__(256) void k_online_window(WindowArgs a) {
 
 // ---- 2b. appending one vector step to the rings the window reads ---------------------------------------------------------
 // One workgroup per env.  The slot is (*head_word + k) mod cap: the word lives on the device, so a captured launch lands in
-// the right slot at every ring position.  Nothing outside the slot is written, no atomics.
+// the right slot at every ring position.  Nothing outside the slot is written, no atomics.  An action is `action_words`
+// opaque 4-byte words, as in the window: one int32, or the float32 components of a Box action (lane w moves word w).
 struct AppendArgs {
-  int E, cap, k;
+  int E, cap, k, action_words;
   const long long* head_word;
   long obs_bytes;
   const unsigned char* obs; const int* actions; const float* rewards; const unsigned char* dones;
@@ -191,8 +185,9 @@ __global__ __launch_bounds__(256) void k_online_append(AppendArgs a) {
   const long row = (long)slot * a.E + e;
   copy_row(a.obs_ring + row * a.obs_bytes, a.obs + (long)e * a.obs_bytes, a.obs_bytes, a.obs_width);
   if (a.S) copy_row((unsigned char*)(a.state_ring + row * a.S), (const unsigned char*)(a.state + (long)e * a.S), (long)a.S * 4, a.state_width);
+  if ((int)threadIdx.x < a.action_words)
+    a.actions_ring[row * a.action_words + threadIdx.x] = a.actions[(long)e * a.action_words + threadIdx.x];
   if (threadIdx.x == 0) {
-    a.actions_ring[row] = a.actions[e];
     a.rewards_ring[row] = a.rewards[e];
     a.dones_ring[row] = a.dones[e];
     a.policy_ring[2 * row] = a.policy[(long)e * a.policy_pitch];
@@ -436,29 +431,62 @@ static int row_width(int64_t bytes, const void* a, const void* b) {
   return 1;
 }
 
+// both append entries: mirl_online_append is action_words = 1
+static int online_append(const char* name, int32_t E, int32_t cap, const int64_t* head_word, int32_t k, int64_t obs_bytes,
+                         const void* obs, const void* actions, int32_t action_words, const float* rewards, const uint8_t* dones,
+                         const float* policy, int64_t policy_pitch, int32_t state_f32, const float* state, const float* initials,
+                         void* obs_ring, void* actions_ring, float* rewards_ring, uint8_t* dones_ring, float* policy_ring,
+                         float* state_ring, float* initials_ring, void* stream) {
+  if (E < 1 || E > (1 << 24) || cap < 1 || k < 0 || obs_bytes < 1 || policy_pitch < 2 || state_f32 < 0 || state_f32 > (1 << 20) ||
+      action_words < 1 || action_words > mirl::kMaxBoxDims ||
+      (double)cap * (double)E * (double)obs_bytes >= 9.0e18 || !head_word || !obs || !actions || !rewards || !dones || !policy ||
+      !obs_ring || !actions_ring || !rewards_ring || !dones_ring || !policy_ring)
+    return mirl::fail(MIRL_ERR_ARG, std::string("bad ") + name + " arguments (1 <= E <= 2^24, cap >= 1, k >= 0, obs_bytes >= 1, "
+                                    "policy_pitch >= 2, 0 <= state_f32 <= 2^20, 1 <= action_words <= 16, no null operands)");
+  if (state_f32 && (!state || !initials || !state_ring || !initials_ring || (uintptr_t)state % 4 || (uintptr_t)state_ring % 4))
+    return mirl::fail(MIRL_ERR_ARG, std::string("bad ") + name + " arguments (state_f32 > 0 needs state, initials and their rings, "
+                                    "float32 blocks on 4-byte boundaries)");
+  mirl::AppendArgs a;
+  a.E = E; a.cap = cap; a.k = k; a.action_words = action_words; a.head_word = (const long long*)head_word; a.obs_bytes = obs_bytes;
+  a.obs = (const unsigned char*)obs; a.actions = (const int*)actions; a.rewards = rewards; a.dones = dones; a.policy = policy;
+  a.policy_pitch = policy_pitch; a.S = state_f32; a.state = state; a.initials = initials;
+  a.obs_ring = (unsigned char*)obs_ring; a.actions_ring = (int*)actions_ring; a.rewards_ring = rewards_ring; a.dones_ring = dones_ring;
+  a.policy_ring = policy_ring; a.state_ring = state_ring; a.initials_ring = initials_ring;
+  a.obs_width = row_width(obs_bytes, obs, obs_ring);
+  a.state_width = state_f32 ? row_width((int64_t)state_f32 * 4, state, state_ring) : 4;
+  mirl::ProfScope ps("k_online_append", (double)E * (2.0 * (double)obs_bytes + 8.0 * state_f32 + 32.0 + 8.0 * action_words),
+                     (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_online_append, dim3((unsigned)E), dim3(256), 0, (hipStream_t)stream, a);
+  MIRL_LAUNCH_CHECK();
+  return MIRL_OK;
+}
+
 extern "C" int mirl_online_append(int32_t E, int32_t cap, const int64_t* head_word, int32_t k, int64_t obs_bytes, const void* obs,
                                   const int32_t* actions, const float* rewards, const uint8_t* dones, const float* policy,
                                   int64_t policy_pitch, int32_t state_f32, const float* state, const float* initials, void* obs_ring,
                                   int32_t* actions_ring, float* rewards_ring, uint8_t* dones_ring, float* policy_ring,
                                   float* state_ring, float* initials_ring, void* stream) {
-  if (E < 1 || E > (1 << 24) || cap < 1 || k < 0 || obs_bytes < 1 || policy_pitch < 2 || state_f32 < 0 || state_f32 > (1 << 20) ||
-      (double)cap * (double)E * (double)obs_bytes >= 9.0e18 || !head_word || !obs || !actions || !rewards || !dones || !policy ||
-      !obs_ring || !actions_ring || !rewards_ring || !dones_ring || !policy_ring)
-    return mirl::fail(MIRL_ERR_ARG, "bad online_append arguments (1 <= E <= 2^24, cap >= 1, k >= 0, obs_bytes >= 1, policy_pitch >= 2, "
-                                    "0 <= state_f32 <= 2^20, no null operands)");
-  if (state_f32 && (!state || !initials || !state_ring || !initials_ring || (uintptr_t)state % 4 || (uintptr_t)state_ring % 4))
-    return mirl::fail(MIRL_ERR_ARG, "bad online_append arguments (state_f32 > 0 needs state, initials and their rings, float32 blocks "
-                                    "on 4-byte boundaries)");
-  mirl::AppendArgs a;
-  a.E = E; a.cap = cap; a.k = k; a.head_word = (const long long*)head_word; a.obs_bytes = obs_bytes;
-  a.obs = (const unsigned char*)obs; a.actions = actions; a.rewards = rewards; a.dones = dones; a.policy = policy;
-  a.policy_pitch = policy_pitch; a.S = state_f32; a.state = state; a.initials = initials;
-  a.obs_ring = (unsigned char*)obs_ring; a.actions_ring = actions_ring; a.rewards_ring = rewards_ring; a.dones_ring = dones_ring;
-  a.policy_ring = policy_ring; a.state_ring = state_ring; a.initials_ring = initials_ring;
-  a.obs_width = row_width(obs_bytes, obs, obs_ring);
-  a.state_width = state_f32 ? row_width((int64_t)state_f32 * 4, state, state_ring) : 4;
-  mirl::ProfScope ps("k_online_append", (double)E * (2.0 * (double)obs_bytes + 8.0 * state_f32 + 40.0), (hipStream_t)stream);
-  hipLaunchKernelGGL(mirl::k_online_append, dim3((unsigned)E), dim3(256), 0, (hipStream_t)stream, a);
+  return online_append("online_append", E, cap, head_word, k, obs_bytes, obs, actions, 1, rewards, dones, policy, policy_pitch,
+                       state_f32, state, initials, obs_ring, actions_ring, rewards_ring, dones_ring, policy_ring, state_ring,
+                       initials_ring, stream);
+}
+
+extern "C" int mirl_online_append_box(int32_t E, int32_t cap, const int64_t* head_word, int32_t k, int64_t obs_bytes, const void* obs,
+                                      const void* actions, const float* rewards, const uint8_t* dones, const float* policy,
+                                      int64_t policy_pitch, int32_t state_f32, const float* state, const float* initials,
+                                      void* obs_ring, void* actions_ring, float* rewards_ring, uint8_t* dones_ring,
+                                      float* policy_ring, float* state_ring, float* initials_ring, int32_t action_words,
+                                      void* stream) {
+  return online_append("online_append_box", E, cap, head_word, k, obs_bytes, obs, actions, action_words, rewards, dones, policy,
+                       policy_pitch, state_f32, state, initials, obs_ring, actions_ring, rewards_ring, dones_ring, policy_ring,
+                       state_ring, initials_ring, stream);
+}
+
+extern "C" int mirl_box_action_sums(int32_t E, int32_t D, const float* actions, double* sums, void* stream) {
+  if (E < 1 || E > (1 << 24) || D < 1 || D > mirl::kMaxBoxDims || !actions || !sums)
+    return mirl::fail(MIRL_ERR_ARG, "bad box_action_sums arguments (1 <= E <= 2^24, 1 <= D <= 16, no null operands)");
+  mirl::ProfScope ps("k_box_action_sums", (double)E * D * 4.0 + 16.0 * (D + 1), (hipStream_t)stream);
+  hipLaunchKernelGGL(mirl::k_box_action_sums, dim3(1), dim3(64), 0, (hipStream_t)stream, (int)E, (int)D, actions, sums);
   MIRL_LAUNCH_CHECK();
   return MIRL_OK;
 }

@@ -223,9 +223,15 @@ class DeviceOnlineHistory:
             self._h.renew()
 
     # -- the fused acting step's sink ---------------------------------------------------------
-    def configure(self, example_state, num_envs, env_base=0, policy_f32=2):
+    def configure(self, example_state, num_envs, env_base=0, policy_f32=2, action_shape=()):
         """The fused actor's set-up call, before its first vector step: the shapes the generic route learns from its first
-        DeviceSamples come from the example next_state pytree.  Discrete actions, no extras."""
+        DeviceSamples come from the example next_state pytree.  action_shape: () = one int32 per action (Discrete), (D,) =
+        the float32 components of a Box action, kept as D opaque words per transition as on the generic route.  No extras."""
+        action_shape = tuple(int(n) for n in action_shape)
+        words = int(np.prod(action_shape)) if action_shape else 1
+        if not 1 <= words <= 16:
+            raise ValueError("DeviceOnlineHistory: actions are integers [E] or float32 [E, D] with D <= 16, not a trailing shape %s"
+                             % (action_shape,))
         if policy_f32 != 2:
             raise ValueError("DeviceOnlineHistory stores the [log-probability | value] pair of every transition: policy_f32 "
                              "must be 2, not %r" % (policy_f32,))
@@ -242,10 +248,11 @@ class DeviceOnlineHistory:
             self.num_envs, self.env_base = int(num_envs), int(env_base)
             self._obs_shape, self._obs_dtype, self._obs_bytes = tuple(x.shape), obs_dtype, int(x.nbytes)
             self._device = torch.device("cuda", torch.cuda.current_device())
-            self._action_shape, self._action_dtype, self._action_words = (), torch.int32, 1
+            self._action_shape, self._action_words = action_shape, words
+            self._action_dtype = torch.float32 if action_shape else torch.int32
             self._head_word = torch.zeros(1, dtype=torch.int64, device=self._device)
         elif (self.num_envs, self.env_base, self._obs_shape, self._obs_dtype, self._action_shape, self._layout.state_f32) != \
-                (int(num_envs), int(env_base), tuple(x.shape), obs_dtype, (), lay.state_f32):
+                (int(num_envs), int(env_base), tuple(x.shape), obs_dtype, action_shape, lay.state_f32):
             raise ValueError("DeviceOnlineHistory: the fused actor's vector steps do not match the ones already stored")
         self._policy_f32, self._fused = 2, True
         if self._h is None:
@@ -267,8 +274,6 @@ class DeviceOnlineHistory:
     def _append(self, k, frames, actions, rewards, dones, state, initials, policy):
         from rltime_amd._lib import lib, check, ptr as p, stream
         E, S, r = self.num_envs, self._layout.state_f32 if self._layout.recurrent else 0, self._rings
-        if self._action_shape:
-            raise ValueError("DeviceOnlineHistory: Box actions are fed through update(DeviceSamples), not the fused step")
         if policy is None or tuple(policy.shape) != (E, 2) or policy.dtype != torch.float32 or policy.stride(1) != 1:
             raise ValueError("DeviceOnlineHistory: every vector step carries its float32 [E, 2] = [log-probability | value] block")
         if S and (state is None or initials is None or tuple(state.shape) != (E, S) or tuple(initials.shape) != (E,)):
@@ -279,16 +284,19 @@ class DeviceOnlineHistory:
                              "pytree has no recurrent layer for")
         dense = [frames, actions, rewards, dones] + ([state, initials] if S else [])
         if frames.numel() * frames.element_size() != E * self._obs_bytes or not all(t.is_contiguous() for t in dense) or \
-                (actions.dtype, rewards.dtype, dones.dtype) != (torch.int32, torch.float32, torch.uint8) or \
-                any(tuple(t.shape) != (E,) for t in (actions, rewards, dones)) or (S and state.dtype != initials.dtype) or \
+                (actions.dtype, rewards.dtype, dones.dtype) != (self._action_dtype, torch.float32, torch.uint8) or \
+                tuple(actions.shape) != (E,) + self._action_shape or \
+                any(tuple(t.shape) != (E,) for t in (rewards, dones)) or (S and state.dtype != initials.dtype) or \
                 (S and state.dtype != torch.float32):
-            raise ValueError("DeviceOnlineHistory: a vector step is contiguous frames [E, ...], int32 actions, float32 rewards "
-                             "and uint8 dones [E]")
-        check(lib.mirl_online_append(E, self.capacity, p(self._head_word), int(k), self._obs_bytes, p(frames), p(actions),
-                                     p(rewards), p(dones), p(policy), policy.stride(0), S, p(state) if S else None,
-                                     p(initials) if S else None, p(r["obs"]), p(r["actions"]), p(r["rewards"]), p(r["dones"]),
-                                     p(r["policy"]), p(r["state"]) if S else None, p(r["initials"]) if S else None, stream()),
-              "mirl_online_append")
+            raise ValueError("DeviceOnlineHistory: a vector step is contiguous frames [E, ...], int32 actions [E] (float32 [E, D] "
+                             "for a Box space), float32 rewards and uint8 dones [E]")
+        args = (E, self.capacity, p(self._head_word), int(k), self._obs_bytes, p(frames), p(actions), p(rewards), p(dones), p(policy),
+                policy.stride(0), S, p(state) if S else None, p(initials) if S else None, p(r["obs"]), p(r["actions"]),
+                p(r["rewards"]), p(r["dones"]), p(r["policy"]), p(r["state"]) if S else None, p(r["initials"]) if S else None)
+        if self._action_shape:        # Box actions: the same kernel body moving `_action_words` words per env
+            check(lib.mirl_online_append_box(*args, self._action_words, stream()), "mirl_online_append_box")
+        else:
+            check(lib.mirl_online_append(*args, stream()), "mirl_online_append")
 
     def _advance(self, steps):
         from rltime_amd._lib import lib, check, ptr as p, stream
