@@ -622,6 +622,59 @@ int mirl_conv1p3_u8_wrw_masked(int64_t N, int32_t H, int32_t W, const uint8_t* x
                                float scale, float* scratch, float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h,
                                int64_t ws_w, float* db, void* stream);
 
+/* ---- the input layer of the SMALL nature CNN (csrc/conv_in_f16.hip): Conv2d(P -> 16, kernel 8, stride 4) on uint8 frames
+ * of P = 1, 3 or 4 planes, the first layer of the reference's models/modules/nature_cnn_small.json (16 k8 s4 -> 32 k4 s2).
+ * 16 filters are one row tile of the 16x16x32 bf16 MFMA: one kernel family, written once on P, with the rows operand
+ * layout of the two families above for every plane count.  One prefix per plane count: mirl_conv1f16p_u8_* (one plane),
+ * mirl_conv1f16p3_u8_* (three), mirl_conv1f16p4_u8_* (four).  Argument lists, arithmetic (pixels exact in bf16, weight *
+ * scale or the gradient split exactly into three bf16 parts, f32 accumulators), wpk, flags, scratch and the masked form
+ * are those of mirl_conv1p_u8_* / mirl_conv1p3_u8_*: no channel stride for one plane, ws_c for three and four.
+ *   x       uint8 [N][P][H][W]
+ *   weight  float, logical [16][P][8][8] with element strides ws_o, (ws_c,) ws_h, ws_w (contiguous or channels_last memory)
+ *   y       float [N][OH][OW][16] = relu(conv(x * scale, weight) + bias), NHWC
+ *   wpk     scratch, *out of <prefix>wpk_floats() floats; flags bit 3 = wpk already holds these weights packed by an
+ *           earlier call of the same entry point (another block: MIRL_ERR_STATE); any other bit: MIRL_ERR_ARG
+ *   dw      float, logical [16][P][8][8] written with the same element strides; db float [16] (masked form)
+ *   scratch *out of <prefix>wrw_scratch_floats() floats (per-workgroup slabs of 1024 P + 16 sums)
+ * An output's summation order does not depend on N or on the launch shape; the weight gradient is a fixed partition summed
+ * in a fixed order (no float atomics, bit-identical reruns).
+ * <prefix>supported() (host logic only): F = 16, K = 8, S = 4, H >= 8, W >= 8, W % 4 == 0, H*W % 16 == 0 and the frame's
+ * planes staged as bf16 within the 64 KiB of LDS a launch asks for at most ((4, 84, 84) and (3, 120, 80) fit).  Anything
+ * else, a null or misaligned (16 B) pointer and N <= 0 return MIRL_ERR_ARG before anything is launched.                */
+int mirl_conv1f16p_u8_supported(int32_t H, int32_t W, int32_t F, int32_t K, int32_t S);
+int mirl_conv1f16p_u8_wpk_floats(int64_t* out);
+int mirl_conv1f16p_u8_fwd(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* weight,
+                          int64_t ws_o, int64_t ws_h, int64_t ws_w, const float* bias, float scale,
+                          float* wpk, float* y, int32_t flags, void* stream);
+int mirl_conv1f16p_u8_wrw_scratch_floats(int64_t* out);
+int mirl_conv1f16p_u8_wrw(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* g, float scale,
+                          float* scratch, float* dw, int64_t ws_o, int64_t ws_h, int64_t ws_w, void* stream);
+int mirl_conv1f16p_u8_wrw_masked(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* dy, const float* y,
+                                 float scale, float* scratch, float* dw, int64_t ws_o, int64_t ws_h, int64_t ws_w,
+                                 float* db, void* stream);
+int mirl_conv1f16p3_u8_supported(int32_t H, int32_t W, int32_t F, int32_t K, int32_t S);
+int mirl_conv1f16p3_u8_wpk_floats(int64_t* out);
+int mirl_conv1f16p3_u8_fwd(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* weight,
+                           int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w, const float* bias, float scale,
+                           float* wpk, float* y, int32_t flags, void* stream);
+int mirl_conv1f16p3_u8_wrw_scratch_floats(int64_t* out);
+int mirl_conv1f16p3_u8_wrw(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* g, float scale,
+                           float* scratch, float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w, void* stream);
+int mirl_conv1f16p3_u8_wrw_masked(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* dy, const float* y,
+                                  float scale, float* scratch, float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h,
+                                  int64_t ws_w, float* db, void* stream);
+int mirl_conv1f16p4_u8_supported(int32_t H, int32_t W, int32_t F, int32_t K, int32_t S);
+int mirl_conv1f16p4_u8_wpk_floats(int64_t* out);
+int mirl_conv1f16p4_u8_fwd(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* weight,
+                           int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w, const float* bias, float scale,
+                           float* wpk, float* y, int32_t flags, void* stream);
+int mirl_conv1f16p4_u8_wrw_scratch_floats(int64_t* out);
+int mirl_conv1f16p4_u8_wrw(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* g, float scale,
+                           float* scratch, float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h, int64_t ws_w, void* stream);
+int mirl_conv1f16p4_u8_wrw_masked(int64_t N, int32_t H, int32_t W, const uint8_t* x, const float* dy, const float* y,
+                                  float scale, float* scratch, float* dw, int64_t ws_o, int64_t ws_c, int64_t ws_h,
+                                  int64_t ws_w, float* db, void* stream);
+
 /* ---- data gradient of the second conv layer (csrc/conv_mid.hip).  For the backward
  * autograd derives for `F.relu(conv(x))` (rltime/models/torch/modules/cnn.py:47-49) at
  * Conv2d(32 -> 64, kernel 4, stride 2) (configs/models/cnn_*.json), input IH x IW =

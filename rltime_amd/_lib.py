@@ -195,6 +195,18 @@ _SIGNATURES = {
     "mirl_conv1p3_u8_wrw_scratch_floats": [_P(_i64)],
     "mirl_conv1p3_u8_wrw": [_i64, _i32, _i32, _vp, _vp, C.c_float, _vp, _vp, _i64, _i64, _i64, _i64, _vp],
     "mirl_conv1p3_u8_wrw_masked": [_i64, _i32, _i32, _vp, _vp, _vp, C.c_float, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp],
+    # the 16-filter input layer (csrc/conv_in_f16.hip): the rows family's argument lists under three prefixes
+    "mirl_conv1f16p_u8_supported": [_i32, _i32, _i32, _i32, _i32],
+    "mirl_conv1f16p_u8_wpk_floats": [_P(_i64)],
+    "mirl_conv1f16p_u8_fwd": [_i64, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _vp, C.c_float, _vp, _vp, _i32, _vp],
+    "mirl_conv1f16p_u8_wrw_scratch_floats": [_P(_i64)],
+    "mirl_conv1f16p_u8_wrw": [_i64, _i32, _i32, _vp, _vp, C.c_float, _vp, _vp, _i64, _i64, _i64, _vp],
+    "mirl_conv1f16p_u8_wrw_masked": [_i64, _i32, _i32, _vp, _vp, _vp, C.c_float, _vp, _vp, _i64, _i64, _i64, _vp, _vp],
+    **{"mirl_conv1f16p%d_u8_%s" % (p, name): sig for p in (3, 4) for name, sig in (
+        ("supported", [_i32, _i32, _i32, _i32, _i32]), ("wpk_floats", [_P(_i64)]), ("wrw_scratch_floats", [_P(_i64)]),
+        ("fwd", [_i64, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _i64, _vp, C.c_float, _vp, _vp, _i32, _vp]),
+        ("wrw", [_i64, _i32, _i32, _vp, _vp, C.c_float, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
+        ("wrw_masked", [_i64, _i32, _i32, _vp, _vp, _vp, C.c_float, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]))},
     "mirl_conv2_bwd_data_supported": [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32],
     "mirl_conv2_bwd_data": [_i64, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp],
     "mirl_conv2_bwd_data_wpk_floats": [_P(_i64)],

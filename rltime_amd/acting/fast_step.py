@@ -14,7 +14,8 @@ weight concatenations, rand / randint, fills).  Here one step is
     mirl_replay_ingest        1 copy + 1 launch  frames + state + scalars + plan + tree, straight
                                                from the static buffers (no clones)
     mirl_conv1_u8_fwd         2 launches       input layer from the env's uint8 frames (mirl_conv1p_u8_fwd for
-                                               one-plane observations, mirl_conv1p3_u8_fwd for three planes)
+                                               one-plane observations, mirl_conv1p3_u8_fwd for three planes;
+                                               mirl_conv1f16p*_u8_fwd for a 16-filter first layer)
     network                   6 launches       csrc/actnet.hip: conv 2, conv 3 (bias + ReLU in the epilogue, layer 3
                                                writes the LSTM product's input rows), [features | h] x [W_ih | W_hh]^T
                                                with the cell in the same launch, quantile embedding x features, hidden
@@ -217,7 +218,8 @@ class FastActingStep:
         _, hh, ww = obs0.shape[1:]
         k, s = c1.kernel_size[0], c1.stride[0]
         self.y1 = torch.empty((E, c1.out_channels, (hh - k) // s + 1, (ww - k) // s + 1), memory_format=torch.channels_last, **f32)
-        self.conv1_family = conv_u8_family(obs0.shape[1])        # by plane count: csrc/conv_in.hip (4), conv_in_rows.hip (1, 3)
+        # by plane and filter count: csrc/conv_in.hip (4), conv_in_rows.hip (1, 3), conv_in_f16.hip (16 filters)
+        self.conv1_family = conv_u8_family(obs0.shape[1], c1.out_channels)
         self.wpk = torch.empty(self.conv1_family.wpk_floats(), **f32)
         self.xh = torch.zeros((E, K), **f32)                     # [conv features (NCHW order) | extras | zeros | masked h]
         self.extra = torch.zeros((E, X), **f32) if X else None   # the compact rows the replay ingests as `extra`

@@ -137,4 +137,56 @@ inline C1FwdPlan c3p_fwd_plan(int64_t N, int H, int W) { return CRows<3>::fwd_pl
 inline C1WrwPlan c1p_wrw_plan(int64_t N, int H, int W) { return CRows<1>::wrw_plan(N, H, W); }
 inline C1WrwPlan c3p_wrw_plan(int64_t N, int H, int W) { return CRows<3>::wrw_plan(N, H, W); }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The 16-filter input layer, Conv2d(planes -> 16, kernel 8, stride 4), of the small nature CNN (csrc/conv_in_f16.hip):
+// sizes, launch parameters and launch plans by plane count P = 1, 3, 4.  The rows operand layout of CRows<P> for every P.
+constexpr int C16_F = 16;
+template <int P>
+struct CF16 {
+  static_assert(P == 1 || P == 3 || P == 4, "instantiated for one, three and four planes");
+  static constexpr int PLANES = P, TG = P * 4;        // tap groups of 16 taps = the weight gradient's accumulator tiles
+  static constexpr int DW = C16_F * P * C1_TAPS;      // 1024 / 3072 / 4096 weight-gradient elements
+  static constexpr int SLAB = DW + C16_F;             // floats per workgroup slab: weight sums, then the bias sums (masked form)
+  static constexpr int WAVES = P == 4 ? 3 : 4;        // forward: waves per SIMD = resident workgroups per CU (24 P weight VGPRs)
+  static constexpr int WRW_WAVES = P == 1 ? 4 : 2;    // weight gradient: likewise (two bf16 frames of 3 or 4 planes fill a CU's LDS)
+  static constexpr int LD = P == 3 ? 8 : 7;           // forward: staging loads in flight per lane (four 84x84 frames or one 84x84x4
+                                                      // frame = 6.9 x 256 vectors, one 120x80x3 frame = 7.03 x 256)
+  static constexpr int WGS = 256 * WRW_WAVES;         // weight gradient: most workgroups = most slabs
+  static constexpr int FWD_WGS = 256 * WAVES;         // forward: most resident workgroups
+  static constexpr int FPI = 4;                       // most frames per LDS fill
+  static constexpr int FILL = 32 * 1024;              // .. and most bytes of one: more than one frame only within this
+  static constexpr int WPK = 3 * 2 * P * 64 * 4;      // packed weight image in floats: [part][instruction q][lane] x 16 B
+  static constexpr size_t LDS = C1_LDS;               // what a launch may ask for: the 64 KiB a kernel gets unasked
+  static constexpr int64_t SCRATCH_FLOATS = (int64_t)WGS * SLAB;
+
+  // The weight gradient stages a plane as FOUR bf16 sub-planes, one per column residue (mod 4): pixel index i of the plane
+  // goes to sub-plane i & 3, halfword i >> 2, so that the 8 pixels of one tap over 8 consecutive ow are 8 consecutive
+  // halfwords.  Halfwords per sub-plane: H W / 4, the over-read of a row's tail octet (8 ceil(OW / 8) - OW positions that
+  // carry g = 0), one for the taps kw >= 4 and one for the dword the read is widened to; rounded to 16 bytes.
+  static int wrw_pitch(int HW, int OW) { return (HW / 4 + 8 * ((OW + 7) / 8) - OW + 2 + 7) / 8 * 8; }
+  // ((4, 84, 84) takes 56 832 bytes, (3, 120, 80) 57 792, (4, 100, 100) does not fit); the forward's raw bytes are half of that
+  static bool shape_ok(int H, int W) {
+    if (H < C1_K || W < C1_K || H > 4096 || W > 4096 || (W % 4) != 0 || ((H * W) % 16) != 0) return false;
+    return (size_t)P * 4 * wrw_pitch(H * W, c1_out(W)) * 2 <= LDS;
+  }
+  static C1FwdPlan fwd_plan(int64_t N, int H, int W) {
+    const int HWP = P * H * W, tiles = (c1_out(H) * c1_out(W) + 15) / 16;
+    // frames per LDS fill: more only once every resident workgroup has a group of its own, and within FILL
+    int fpi_max = FILL / HWP;
+    fpi_max = fpi_max < 1 ? 1 : (fpi_max > FPI ? FPI : fpi_max);
+    const int64_t fpi64 = N / FWD_WGS;
+    const int fpi = fpi64 < 1 ? 1 : (fpi64 > fpi_max ? fpi_max : (int)fpi64);
+    // few frames: `split` workgroups share one frame's tiles (at least one tile per wave)
+    const int max_split = (tiles + 3) / 4;
+    int split = N >= FWD_WGS ? 1 : (int)((FWD_WGS + N - 1) / N);
+    if (split > max_split) split = max_split;
+    return {fpi, split, capped_grid((N + fpi - 1) / fpi * split, FWD_WGS), (size_t)fpi * HWP};
+  }
+  // pitch: halfwords per sub-plane
+  static C1WrwPlan wrw_plan(int64_t N, int H, int W) {
+    const int Pd4 = wrw_pitch(H * W, c1_out(W));
+    return {true, 1, Pd4, SLAB, capped_grid(N, WGS), c1_at_least_slab((size_t)P * 4 * Pd4 * 2, SLAB)};
+  }
+};
+
 }  // namespace mirl

@@ -329,8 +329,8 @@ def frames_to_f32_nhwc(x, scale):
 
 
 class ConvU8Family:
-    """One kernel family of the input layer from uint8 frames, by plane count: what differs between csrc/conv_in.hip (four
-    planes) and csrc/conv_in_rows.hip (one and three) above the kernels.  `call(name, ...)` runs
+    """One kernel family of the input layer from uint8 frames, by plane (and filter) count: what differs between csrc/conv_in.hip
+    (four planes), csrc/conv_in_rows.hip (one and three) and csrc/conv_in_f16.hip (16 filters) above the kernels.  `call(name, ...)` runs
     `<prefix><name>` on the current stream."""
 
     def __init__(self, planes, prefix, fwd_flags, fwd_packed, planes_in_query=False):
@@ -361,22 +361,26 @@ class ConvU8Family:
 
 _CONV_U8 = {4: ConvU8Family(4, "mirl_conv1_u8_", (), "fwd_ex", planes_in_query=True), 1: ConvU8Family(1, "mirl_conv1p_u8_", (0,), "fwd"),
             3: ConvU8Family(3, "mirl_conv1p3_u8_", (0,), "fwd")}
+# by filter count, then plane count: 16 filters (the small nature CNN's first layer) are csrc/conv_in_f16.hip for every plane count
+_CONV_U8_BY_FILTERS = {32: _CONV_U8, 16: {1: ConvU8Family(1, "mirl_conv1f16p_u8_", (0,), "fwd"), 3: ConvU8Family(3, "mirl_conv1f16p3_u8_", (0,), "fwd"),
+                                          4: ConvU8Family(4, "mirl_conv1f16p4_u8_", (0,), "fwd")}}
 
 
-def conv_u8_family(planes):
-    """The family for frames of `planes` planes, or None."""
-    return _CONV_U8.get(planes)
+def conv_u8_family(planes, filters=32):
+    """The family for frames of `planes` planes into `filters` filters, or None."""
+    return _CONV_U8_BY_FILTERS.get(filters, {}).get(planes)
 
 
 def conv_u8_supported(x, conv):
-    """Does the one-pass input layer (mirl_conv1_u8_fwd / mirl_conv1p_u8_fwd / mirl_conv1p3_u8_fwd) cover this conv on this uint8 block?"""
+    """Does the one-pass input layer (mirl_conv1_u8_fwd / mirl_conv1p_u8_fwd / mirl_conv1p3_u8_fwd, at 16 filters mirl_conv1f16p*_u8_fwd)
+    cover this conv on this uint8 block?"""
     if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.uint8 and x.dim() == 4 and x.is_contiguous()
             and x.data_ptr() % 16 == 0 and conv.bias is not None and conv.weight.dtype == torch.float32
             and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1
             and conv.kernel_size[0] == conv.kernel_size[1] and conv.stride[0] == conv.stride[1]
             and conv.in_channels == x.shape[1] and not torch.is_autocast_enabled()):
         return False
-    fam = conv_u8_family(x.shape[1])             # no family for another plane count
+    fam = conv_u8_family(x.shape[1], conv.out_channels)      # no family for another plane or filter count
     return fam is not None and fam.supported(x.shape[2], x.shape[3], conv.out_channels, conv.kernel_size[0], conv.stride[0])
 
 
@@ -385,7 +389,7 @@ class _ConvU8(torch.autograd.Function):
     def forward(ctx, x, weight, bias, scale, stride):
         L = _lib()
         n, c, h, w = x.shape
-        fam = ctx.fam = conv_u8_family(c)
+        fam = ctx.fam = conv_u8_family(c, weight.shape[0])
         f, k = weight.shape[0], weight.shape[2]
         oh, ow = (h - k) // stride + 1, (w - k) // stride + 1
         y = torch.empty((n, f, oh, ow), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
