@@ -806,6 +806,28 @@ int mirl_conv_wrw_b3_scratch_bytes(int32_t C, int32_t F, int32_t KH, int32_t KW,
 int mirl_conv_wrw_b3(int64_t N, int32_t H, int32_t W, int32_t C, int32_t F, int32_t KH, int32_t KW, int32_t S,
                      const float* x, const float* g, void* scratch, int64_t scratch_bytes, float* dw, void* stream);
 
+/* ---- both gradients of the small nature CNN's second layer, Conv2d(16 -> 32, kernel 4, stride 2), valid padding
+ * (configs/models/modules/nature_cnn_small.json; autograd of cnn.py:47-49), on the bf16 matrix pipe with f32 results
+ * (csrc/conv_small.hip).  mirl_gemm3's arithmetic: both operands split exactly into three bf16 parts, six part products,
+ * f32 accumulation, fixed reduction order — bit-exact on small-integer operands, bit-identical reruns, fp32 tolerance
+ * otherwise (tests/test_conv2s_gpu.py).  NHWC memory throughout:
+ *   g   float [N][OH][OW][32]   gradient w.r.t. the conv output after the ReLU mask, OH = (H - 4) / 2 + 1, OW likewise
+ *   x   float [N][H][W][16]     the layer's input
+ *   mirl_conv2s_bwd_data   dx float [N][IH][IW][16], every element written; IH in {2 OH + 2, 2 OH + 3} and IW likewise: a
+ *                          last row / column the stride leaves uncovered is written as exact zeros.  weight: logical
+ *                          [32][16][4][4] by its element strides (plain and channels_last weights both without a copy);
+ *                          it is split in the kernel's prologue: no scratch.
+ *   mirl_conv2s_wrw        dw float [32][4][4][16] (channels_last weight memory).  scratch: mirl_conv2s_wrw_scratch_bytes()
+ *                          bytes, 16-byte aligned (one slab per workgroup, summed in slab order by a second launch).
+ * mirl_conv2s_supported(): C == 16, F == 32, K == 4, S == 2, H, W >= 4 and one frame inside both kernels' LDS plans (square
+ * frames up to 25 x 25); pure host logic.  Otherwise 0 / MIRL_ERR_ARG and the caller keeps the library path.            */
+int mirl_conv2s_supported(int32_t C, int32_t F, int32_t K, int32_t S, int32_t H, int32_t W);
+int mirl_conv2s_bwd_data(int64_t N, int32_t IH, int32_t IW, const float* g, const float* weight, int64_t ws_o,
+                         int64_t ws_c, int64_t ws_h, int64_t ws_w, float* dx, void* stream);
+int mirl_conv2s_wrw_scratch_bytes(int64_t* bytes);
+int mirl_conv2s_wrw(int64_t N, int32_t H, int32_t W, const float* x, const float* g, void* scratch,
+                    int64_t scratch_bytes, float* dw, void* stream);
+
 /* ---- non-contraction glue around the network's GEMMs / convolutions (csrc/nnops.hip).
  * All tensors row-major (rows, C), channel / feature index fastest (NHWC
  * activations, (M, features) matrices).  One HBM pass each; column sums are

@@ -219,6 +219,10 @@ _SIGNATURES = {
     "mirl_conv_wrw_b3_supported": [_i32, _i32, _i32, _i32, _i32, _i32, _i32],
     "mirl_conv_wrw_b3_scratch_bytes": [_i32, _i32, _i32, _i32, _P(_i64)],
     "mirl_conv_wrw_b3": [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp],
+    "mirl_conv2s_supported": [_i32, _i32, _i32, _i32, _i32, _i32],
+    "mirl_conv2s_bwd_data": [_i64, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp],
+    "mirl_conv2s_wrw_scratch_bytes": [_P(_i64)],
+    "mirl_conv2s_wrw": [_i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp],
     "mirl_gemm3_supported": [_i32, _i64, _i64, _i64],
     "mirl_gemm3_workspace_bytes": [_i32, _i64, _i64, _i64, _P(_i64)],
     "mirl_gemm3": [_i32, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _vp],

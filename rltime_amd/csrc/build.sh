@@ -7,7 +7,7 @@ HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="$HERE/../librltime_hip.so"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function ${MIRL_EXTRA_HIPCC_FLAGS:-}"
-UNITS="replay qmath c51 lstm lstm_seq lstm_multi lstm_extras convert nnops acting actnet conv_in conv_in_rows conv_in_f16 conv_mid gemm3 conv3 conv_wrw optim actor_critic act_mlp"
+UNITS="replay qmath c51 lstm lstm_seq lstm_multi lstm_extras convert nnops acting actnet conv_in conv_in_rows conv_in_f16 conv_mid gemm3 conv3 conv_wrw conv_small optim actor_critic act_mlp"
 # units compiled without packed-f32 VALU instructions (scalar v_add / v_mul / v_fma for their float4 arithmetic)
 NO_PK_F32="lstm_multi"
 newest_hdr=$(ls -t "$HERE"/*.h "$HERE"/*.hpp "$HERE"/../../include/*.h "$HERE/build.sh" | head -1)

@@ -218,6 +218,13 @@ class _ConvBiasReLU(torch.autograd.Function):
         if need_x and _CONV3_BWD and g.shape[0] and conv3_bwd_data_supported(x, weight, ctx.stride, g):
             dx = conv3_bwd_data(g, weight, x)          # the same on the bf16 pipe for the stride-1 3 x 3 layer
             need_x = False
+        if (need_x or need_w) and conv2s_supported(x, weight, ctx.stride, g):
+            # the small nature CNN's 16 -> 32 layer: both gradients on the bf16 pipe (csrc/conv_small.hip)
+            if need_x:
+                dx = conv2s_bwd_data(g, weight, x)
+            if need_w:
+                dw = conv2s_wgrad(g, x, weight)
+            need_x = need_w = False
         lib_dx, lib_dw, _ = torch.ops.aten.convolution_backward(
             g, x, weight, None, list(ctx.stride), [0, 0], [1, 1], False, [0, 0], 1, [need_x, need_w, False]) \
             if (need_x or need_w) else (None, None, None)
@@ -308,6 +315,53 @@ def conv2_bwd_data(g, weight, x_like):
     L.check(L.lib.mirl_conv2_bwd_data_ex(g.shape[0], g.shape[2], g.shape[3], L.ptr(g), L.ptr(weight), so, sc, sh, sw, L.ptr(wpk), wpk.numel(),
                                          L.ptr(dx), _CONV2_BWD_PIPE, L.stream()), "mirl_conv2_bwd_data_ex")
     return dx
+
+
+# frames below which the 16 -> 32 layer's gradients stay on the library: the smallest measured frame count from which
+# conv2s_bwd_data + conv2s_wgrad together are at least as fast as aten.convolution_backward in every window of
+# tools/conv2s_probe.py (docs/measurement.md, "The small nature CNN's second layer").  They win at 128 frames, the smallest
+# count measured (34 us against 80), so the floor is 0: catch_dqn_small.json's 128-frame minibatch takes them
+_CONV2S_MIN_FRAMES = 0
+_conv2s_scratch = {}
+
+
+def conv2s_supported(x, weight, stride, g, min_frames=None):
+    """Does csrc/conv_small.hip take both gradients of this NHWC Conv2d(16 -> 32, k 4, s 2)?"""
+    if not (x.is_cuda and x.dtype == torch.float32 and g.dtype == torch.float32 and weight.dtype == torch.float32
+            and x.dim() == 4 and tuple(stride) == (2, 2) and weight.shape[2] == weight.shape[3] and g.shape[0] > 0
+            and x.is_contiguous(memory_format=torch.channels_last) and g.is_contiguous(memory_format=torch.channels_last)
+            and x.data_ptr() % 16 == 0 and g.data_ptr() % 16 == 0 and not torch.is_autocast_enabled()):
+        return False
+    if g.shape[0] < (_CONV2S_MIN_FRAMES if min_frames is None else min_frames):
+        return False
+    return bool(_lib().lib.mirl_conv2s_supported(weight.shape[1], weight.shape[0], weight.shape[2], 2, x.shape[2], x.shape[3]))
+
+
+def conv2s_bwd_data(g, weight, x_like):
+    """d loss / d input of conv2d(x, weight, stride 2) for the (16 -> 32, k 4) layer; g is NHWC.  Rows / columns of x the
+    stride leaves uncovered get exact zeros."""
+    L = _lib()
+    dx = torch.empty_like(x_like, memory_format=torch.channels_last)
+    so, sc, sh, sw = weight.stride()
+    L.check(L.lib.mirl_conv2s_bwd_data(g.shape[0], x_like.shape[2], x_like.shape[3], L.ptr(g), L.ptr(weight), so, sc, sh, sw, L.ptr(dx),
+                                       L.stream()), "mirl_conv2s_bwd_data")
+    return dx
+
+
+def conv2s_wgrad(g, x, weight):
+    """d loss / d weight of the same layer in the weight's channels_last memory format."""
+    L = _lib()
+    n, c, h, w = x.shape
+    f, _, kh, kw = weight.shape
+    key = (x.device.index, torch.cuda.current_stream().cuda_stream)
+    scratch = _conv2s_scratch.get(key)
+    if scratch is None:
+        nbytes = C.c_int64()
+        L.check(L.lib.mirl_conv2s_wrw_scratch_bytes(C.byref(nbytes)), "mirl_conv2s_wrw_scratch_bytes")
+        scratch = _conv2s_scratch[key] = torch.empty(nbytes.value, dtype=torch.uint8, device=x.device)
+    dw = torch.empty((f, kh, kw, c), dtype=torch.float32, device=x.device)
+    L.check(L.lib.mirl_conv2s_wrw(n, h, w, L.ptr(x), L.ptr(g), L.ptr(scratch), scratch.numel(), L.ptr(dw), L.stream()), "mirl_conv2s_wrw")
+    return dw.permute(0, 3, 1, 2)                     # logical (F, C, KH, KW) with channels_last strides
 
 
 def conv_bias_relu(x, conv):
